@@ -8,11 +8,15 @@ creature of the batch (controller + PID + world.Step(1/50, 180, 60) + reward/don
 prints ONE JSON line.  `--scaling weak` (default): every rank steps its own 65 536 creatures; `--scaling strong`:
 BASELINE.json's 65 536 creatures are split over the ranks.  Either way the only collective is one all-gather of fp64
 fitness at the end of each timed block.  The K steps are timed as a BLOCK (barrier + synchronize on both sides, max over
-ranks); blocks are repeated until the timed region is >= --min-time seconds (default 5 s: long enough for an external
-utilisation sampler to see the GPU busy) and the MEDIAN block is
+ranks).  A plain run times exactly ONE block of K steps after --settle + --warmup untimed steps and prints the line;
+`--dump-outputs DIR` then also writes what the timed path returned in its last step (reward, done, fitness per creature).
+
+`--full` adds everything the headline figure does not need: blocks are repeated until the timed region is >= --min-time
+seconds (default 5 s there: long enough for an external utilisation sampler to see the GPU busy) and the MEDIAN block is
 reported (`config.blocks_ms` lists every block), so that a cold first block (fresh process on a fresh box) does not
-decide the figure.  Kernel-exact timing (HIP events) happens in a pass of its own AFTER the timed region; the secondary
-workloads (north_star's 8-module creatures, config 4) are measured in the same process and reported under `secondary`.
+decide the figure; kernel-exact timing (HIP events) in a pass of its own AFTER the timed region (`roofline`); the secondary
+workloads (north_star's 8-module creatures, config 4, the tolerance-mode build) measured in the same process and reported
+under `secondary`; and the CPU baseline (`cpu_baseline`).
 
 Workloads (BASELINE.json configs), all synthetic:
   lsystem  (default, the 65 536-creature config the metric is quoted on): random L-system
@@ -485,11 +489,12 @@ def make_env(morphs, dev, hard, flat, discrete, wide=False):
 
 def stepper(env, spl):
     def run(n):
-        left = n
+        left, out = n, None
         while left > 0:
             k = min(spl, left)
-            env.step(k)
+            out = env.step(k)
             left -= k
+        return out   # (reward, done) of the last step, as env.step returns them
     return run
 
 
@@ -508,8 +513,31 @@ def timed_blocks(run_block, steps, min_time, max_blocks, sync, reduce_max):
             return blocks
 
 
-def main():
-    t_start = time.perf_counter()
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all (a fixed, seeded sample of the creatures beyond it)
+
+
+def dump_outputs(path, arrays, suffix=""):
+    """--dump-outputs: the arrays the timed path returned in its last step (population order, one value per creature) as
+    <path>/<name><suffix>.npy -- float64 where the path returns float64, float32 otherwise (done: 0 / 1).  Above
+    DUMP_LIMIT_BYTES the same fixed, seeded sample of the creatures is taken from every array.  Returns the file names."""
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    n = len(next(iter(out.values())))
+    per_creature = sum(a.nbytes for a in out.values()) / max(1, n)
+    if n * per_creature > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, int(DUMP_LIMIT_BYTES // per_creature), replace=False))
+        out = {k: a[keep] for k, a in out.items()}
+    os.makedirs(path, exist_ok=True)
+    names = []
+    for name, a in out.items():
+        names.append(name + suffix + ".npy")
+        np.save(os.path.join(path, names[-1]), a)
+    return names
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -523,12 +551,20 @@ def main():
                     help="env-steps per C-ABI step call (one call = that many kernel sequences queued on the streams)")
     ap.add_argument("--settle", type=int, default=60,
                     help="untimed steps right after reset so that creatures have landed (spawn is 2 m up)")
-    ap.add_argument("--min-time", type=float, default=5.0,
-                    help="repeat the --steps block until the timed region is at least this long (seconds); the median block is reported")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="repeat the --steps block until the timed region is at least this long (seconds); the median block is reported "
+                         "(default: 0 = ONE block of exactly --steps steps; 5 with --full)")
     ap.add_argument("--max-blocks", type=int, default=400)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: blocks repeated for --min-time 5 s, the roofline "
+                         "(kernel-timing pass after the timed region), the secondary workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (reward, done, fitness) "
+                         "as DIR/<name>.npy; compare plain runs (with --full or --min-time the number of blocks, and so the "
+                         "step the outputs belong to, depends on the speed)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary workloads (chain8, cppn_hardcore) measured after the headline one")
+                    help="(with --full) skip the secondary workloads (chain8, cppn_hardcore) measured after the headline one")
     ap.add_argument("--step-groups", type=int, default=None,
                     help="independent parts of the population stepped on separate streams (default: automatic)")
     ap.add_argument("--graph", type=int, default=None, choices=[0, 1], help="replay every step call as a hipGraph (REM2D_GRAPH)")
@@ -537,7 +573,15 @@ def main():
                          "(launch option `pipeline` of every world, rem2d_world_set_option)")
     ap.add_argument("--discrete", action="store_true",
                     help="b2World(continuousPhysics=False): skip SolveTOI (the default follows pybox2d: continuous)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.min_time is None:
+        args.min_time = 5.0 if args.full else 0.0
+    return args
+
+
+def main():
+    t_start = time.perf_counter()
+    args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         launch_ranks(args)          # does not return
@@ -579,7 +623,7 @@ def main():
         prep = build_population("lsystem" if generation else args.workload, n_envs, first)
     # the secondary workloads' host-side input, also before the GPU is initialised (fork pool)
     secondary_in = {}
-    if args.workload == "lsystem" and world == 1 and not args.no_secondary and n_envs == 65536 and not args.discrete:
+    if args.full and args.workload == "lsystem" and world == 1 and not args.no_secondary and n_envs == 65536 and not args.discrete:
         for wl in ("chain8", "cppn_hardcore"):
             secondary_in[wl] = build_population(wl, 65536, 0)
     t_genomes = time.perf_counter()
@@ -629,9 +673,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    last = {}   # what the timed path returned in its last step (--dump-outputs)
+
     def block(n):
-        run(n)
-        fit = env.fitness
+        last["reward"], last["done"] = run(n)
+        fit = last["fitness"] = env.fitness
         if world > 1:
             all_gather_fitness(fit.to(cdev), per_rank * world)   # the job's only collective
 
@@ -659,12 +705,12 @@ def main():
         t0 = time.perf_counter()
         done_steps = 0
         while done_steps < EPISODE_CAP:
-            env.step(100)
+            last["reward"], last["done"] = env.step(100)
             done_steps += 100
             if bool((env.frozen != 0).all()):
                 break
         args.steps = done_steps
-        fit = env.fitness
+        fit = last["fitness"] = env.fitness
         if world > 1:
             all_gather_fitness(fit.to(cdev), per_rank * world)
         sync()
@@ -673,16 +719,18 @@ def main():
         blocks = timed_blocks(block, args.steps, args.min_time, args.max_blocks, sync, reduce_max)
     dt = float(np.median(blocks))
     err = int(env.errors().max())
+    if args.dump_outputs:   # (before anything steps these creatures again)
+        dump_outputs(args.dump_outputs, last, "_rank%d" % rank if world > 1 else "")
 
     # ---- roofline of the dominant kernel: a pass of its own AFTER the timed region, with HIP events recorded by the
     # library on the launch streams (one more block of K steps of the same population, continuing where the timed
     # region stopped).  Every launch covers one step group (all lane buckets of that part of the population in one
-    # grid); its time is booked on the group's first world. ----
+    # grid); its time is booked on the group's first world.  --full only: a plain run reports no roofline. ----
     pipeline = env.worlds[0][0].get_option("pipeline")   # (the launch option the library really runs with)
     ms = launches = 0
     ms_step = n_step = 0
     timing_steps = 0
-    if not generation:
+    if args.full and not generation:
         firsts = [env.worlds[g[0]][0] for g in env.groups] if env.groups else [env.worlds[0][0]]
         timing_steps = min(args.steps, 200)
         for w in firsts:          # event pairs are created here (as many as this pass records); only each group's first world records
@@ -828,6 +876,7 @@ def main():
                        "settle_steps": args.settle,
                        "velocity_iterations": 180, "position_iterations": 60, "dt": 0.02,
                        "continuous_physics": not args.discrete,
+                       "full": args.full,
                        "parallelism": "population sharded over %d rank(s), one per GPU, no per-step collective; one fp64 "
                                       "fitness all-gather per block (%s)" % (world, backend if world > 1 else "none at 1 rank"),
                        "ranks_share_one_gpu": bool(world > 1 and n_dev < world),
@@ -863,9 +912,12 @@ def main():
                                  "the 180+60 Gauss-Seidel sweeps (FP32 VALU; valu_issue.frac of the issue "
                                  "peak), not by HBM"},
         }
+        if not args.full:   # (no timing pass ran: nothing measured to put in it)
+            del out["roofline"]
         if secondary is not None:
             out["secondary"] = secondary
-        if not args.no_cpu_baseline and world == 1:
+        cpu_leg = args.full and not args.no_cpu_baseline
+        if cpu_leg and world == 1:
             from gym_rem2d_amd import make_terrain as _mt
             window = args.steps if not generation else 200
             # the real reference if the wheel and a checkout are there (kind "reference"), else the port
@@ -874,7 +926,7 @@ def main():
             out["cpu_baseline"] = ref if ref is not None else \
                 cpu_baseline(morphs, _mt(4, flat=flat, hardcore=hard), 0 if args.discrete else 1, args.settle + args.warmup, window)
             out["cpu_baseline"]["reference_python_overhead"] = REFERENCE_PYTHON_OVERHEAD
-        elif not args.no_cpu_baseline:
+        elif cpu_leg:
             out["cpu_baseline"] = None
         print(json.dumps(out))
     if world > 1:

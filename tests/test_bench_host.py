@@ -88,6 +88,39 @@ def test_timed_blocks_protocol():
     assert bench.METRIC == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
 
 
+def test_plain_run_is_one_block_and_full_keeps_the_extras():
+    """Without --full the timed region is ONE block of exactly --steps steps (--min-time 0) and nothing else is measured;
+    --full repeats blocks for 5 s as before, and an explicit --min-time holds either way."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "30", "--warmup", "4"])
+    assert (a.full, a.min_time, a.steps, a.warmup, a.dump_outputs) == (False, 0.0, 30, 4, None)
+    a = bench.parse_args(["--steps", "30", "--full", "--dump-outputs", "d"])
+    assert (a.full, a.min_time, a.dump_outputs) == (True, 5.0, "d")
+    assert bench.parse_args(["--min-time", "2"]).min_time == 2.0 == bench.parse_args(["--full", "--min-time", "2"]).min_time
+
+
+def test_dump_outputs_types_names_and_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one <name>.npy per array, float64 kept, everything else float32; above the cap the same fixed
+    sample of creatures from every array, the same from run to run."""
+    import bench
+    import torch
+    n = 1000
+    arrays = {"reward": torch.arange(n, dtype=torch.float32), "done": torch.arange(n) % 3 == 0,
+              "fitness": torch.arange(n, dtype=torch.float64) * 0.5}
+    names = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(names) == sorted(os.listdir(tmp_path / "a")) == ["done.npy", "fitness.npy", "reward.npy"]
+    r, d, f = (np.load(tmp_path / "a" / k) for k in names)
+    assert r.dtype == np.float32 and d.dtype == np.float32 and f.dtype == np.float64
+    assert np.array_equal(r, np.arange(n)) and np.array_equal(d, (np.arange(n) % 3 == 0)) and np.array_equal(f, np.arange(n) * 0.5)
+    assert bench.dump_outputs(str(tmp_path / "r"), arrays, "_rank1") == ["reward_rank1.npy", "done_rank1.npy", "fitness_rank1.npy"]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 100)      # 16 bytes per creature: room for 100
+    for k in "bc":
+        bench.dump_outputs(str(tmp_path / k), arrays)
+    rb, fb = np.load(tmp_path / "b" / "reward.npy"), np.load(tmp_path / "b" / "fitness.npy")
+    assert len(rb) == len(fb) == 100 and np.array_equal(fb, rb * 0.5) and (np.diff(rb) > 0).all()
+    assert all(np.array_equal(np.load(tmp_path / "b" / k), np.load(tmp_path / "c" / k)) for k in names)
+
+
 def test_bench_population_is_the_seeded_python_population(tmp_path, monkeypatch):
     """bench.py builds its populations with the native compilers (genomes by seed in Python, everything after natively):
     the lane buckets must be, word for word and in the same order, what Morphology.from_specs gives for

@@ -266,14 +266,14 @@ def test_compaction_of_the_survivors_keeps_every_fitness(need_gpu):
 
 
 def test_bench_json_contract(need_gpu):
-    """bench.py prints exactly one JSON line with the fields the driver reads (tiny sizes here)."""
+    """bench.py --full prints exactly one JSON line with the fields the driver reads (tiny sizes here)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-                        "--envs", "1024", "--settle", "10"], capture_output=True, text=True, timeout=900)
+                        "--envs", "1024", "--settle", "10", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -301,6 +301,41 @@ def test_bench_json_contract(need_gpu):
     from gym_rem2d_amd import _lib
     assert d["build_id"] == _lib.source_id() and d["world_size"] == 1 and d["backend"] is None
     assert cfg["shard_cost_bodies"] and len(cfg["shard_cost_bodies"]) == 1 and cfg["shard_cost_bodies"][0] > 1024
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_its_outputs(need_gpu, tmp_path):
+    """A plain bench.py run (no --full) times ONE block of exactly --steps steps and measures nothing else (no roofline, CPU
+    baseline or secondary workloads); --dump-outputs writes what the timed path returned in its last step, and two runs with the
+    same arguments write the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--envs", "1024", "--settle", "10", "--dump-outputs", str(tmp_path / ("out%d" % k))],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append([l for l in r.stdout.splitlines() if l.strip()])
+        assert len(lines[-1]) == 1
+    d = json.loads(lines[0][0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert "roofline" not in d and "cpu_baseline" not in d and "secondary" not in d
+    cfg = d["config"]
+    assert d["steps"] == 7 and cfg["blocks"] == len(cfg["blocks_ms"]) == 1 and cfg["full"] is False
+    assert abs(d["ms_per_step"] * d["steps"] - cfg["blocks_ms"][0]) < 1e-2
+    assert abs(d["value"] - 1024 * 7 / (d["ms_per_step"] * 7 * 1e-3)) < 1e-6 * d["value"]
+    assert d["metric"] == json.load(open(os.path.join(root, "BASELINE.json")))["metric"] and cfg["solver_errors"] == 0
+    a, b = tmp_path / "out0", tmp_path / "out1"
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == ["done.npy", "fitness.npy", "reward.npy"]
+    for name, dtype in (("reward", np.float32), ("done", np.float32), ("fitness", np.float64)):
+        x, y = np.load(a / (name + ".npy")), np.load(b / (name + ".npy"))
+        assert x.dtype == dtype and x.shape == (1024,) and np.array_equal(x, y), name
+    assert np.isfinite(np.load(a / "reward.npy")).all() and np.load(a / "fitness.npy").any()
 
 
 def test_bench_gpus_flag_starts_the_ranks_itself(need_gpu):

@@ -3,7 +3,7 @@
 # GPU with 65 536 each ran at 96.9 M where one rank with 131 072 runs at 71 M: is it the second dispatch queue?
 set -u
 O=gpurun_out/r06_gen_groups; mkdir -p $O
-run() { name=$1; shift; env "$@" timeout 400 python3 bench.py --workload generation --no-cpu-baseline $EXTRA > $O/$name.json 2>/dev/null; python3 -c "
+run() { name=$1; shift; env "$@" timeout 400 python3 bench.py --full --workload generation --no-cpu-baseline $EXTRA > $O/$name.json 2>/dev/null; python3 -c "
 import json
 try:
     d=json.load(open('$O/$name.json')); c=d['config']; print('$name', '%.2fM'%(d['value']/1e6), 'steps', d['steps'], '%.1f ms total'%(c['blocks_ms'][0]), c.get('launch'), 'groups', c.get('step_groups'), 'err', c.get('solver_errors'))

@@ -3,11 +3,11 @@
 # velocity-cost rebalance key (build/ab/librem2d_rbv{3,5}.so = -DREBALANCE_VEL=3 / 5).
 set -u
 O=gpurun_out/r06_c; mkdir -p $O
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default_20_cold.json 2> $O/bench_cold.err
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default_20_cold.json 2> $O/bench_cold.err
 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1; tail -5 $O/pytest_gpu.txt
-timeout 600 python3 bench.py > $O/bench_default.json 2>/dev/null
+timeout 600 python3 bench.py --full > $O/bench_default.json 2>/dev/null
 timeout 300 tools/ubench_latency.bin > $O/ubench_issue.txt 2>&1; tail -14 $O/ubench_issue.txt
-REM2D_TILE_SHAPE=1 timeout 300 python3 bench.py --steps 100 --warmup 40 --settle 60 --no-cpu-baseline --no-secondary --min-time 2 > $O/lsys_65536_shape1_train128.json 2>/dev/null
+REM2D_TILE_SHAPE=1 timeout 300 python3 bench.py --full --steps 100 --warmup 40 --settle 60 --no-cpu-baseline --no-secondary --min-time 2 > $O/lsys_65536_shape1_train128.json 2>/dev/null
 BENCH_ARGS="--steps 100 --warmup 40 --settle 60 --no-cpu-baseline --no-secondary --min-time 2" bash tools/lib_ab.sh r06_rbv 2 base rbv5 rbv3
 BENCH_ARGS="--workload cppn_hardcore --steps 100 --warmup 40 --settle 60 --no-cpu-baseline --no-secondary --min-time 2" bash tools/lib_ab.sh r06_rbv_cppn 1 base rbv5 rbv3
 for f in $O/bench_default_20_cold.json $O/bench_default.json $O/lsys_65536_shape1_train128.json; do python3 -c "

@@ -4,7 +4,7 @@
 set -u
 O=gpurun_out/r06_knobs; mkdir -p $O
 A="--steps 100 --warmup 40 --settle 60 --no-cpu-baseline --no-secondary --min-time 2"
-run() { name=$1; shift; env "$@" timeout 300 python3 bench.py $A > $O/$name.json 2>/dev/null; python3 -c "
+run() { name=$1; shift; env "$@" timeout 300 python3 bench.py --full $A > $O/$name.json 2>/dev/null; python3 -c "
 import json
 try:
     d=json.load(open('$O/$name.json')); c=d['config']; print('$name', '%.2fM'%(d['value']/1e6), '%.4f ms/step'%d['ms_per_step'], 'err', c.get('solver_errors'))

@@ -14,6 +14,6 @@ for spec in "lsystem 131072 1000 61" "direct 65536 800 62" "network_arrays 32768
 done; grep "individuals\|SOAK\|rc=" $O/soak_generation.txt
 timeout 900 python tools/fuzz_launch_shapes.py --rounds 200 --seed 7 --creatures 2000 > $O/fuzz_launch_shapes.txt 2>&1; tail -1 $O/fuzz_launch_shapes.txt
 timeout 900 python tools/fuzz_episode.py --rounds 100 --seed 7 --max-creatures 4000 > $O/fuzz_episode.txt 2>&1; tail -1 $O/fuzz_episode.txt
-timeout 600 python3 bench.py --workload generation --envs 1048576 --no-cpu-baseline > $O/bench_generation_1M_1gpu.json 2>/dev/null
+timeout 600 python3 bench.py --full --workload generation --envs 1048576 --no-cpu-baseline > $O/bench_generation_1M_1gpu.json 2>/dev/null
 python3 -c "
 import json; d=json.load(open('$O/bench_generation_1M_1gpu.json')); print('generation 1M', '%.2fM' % (d['value']/1e6), d['config'].get('launch'), 'err', d['config'].get('solver_errors'))"

@@ -5,10 +5,10 @@ set -u
 O=$GRAFT_REPO_ROOT/gpurun_out/r06_train128_prof; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 ARGS="--envs 131072 --steps 100 --warmup 50 --settle 50 --steps-per-launch 50 --no-cpu-baseline --no-secondary --min-time 0"
-python3 bench.py $ARGS > $O/bench_unprofiled.json 2>/dev/null
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py $ARGS > $O/bench_under_stats.json 2> $O/stats.err
+python3 bench.py --full $ARGS > $O/bench_unprofiled.json 2>/dev/null
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full $ARGS > $O/bench_under_stats.json 2> $O/stats.err
 f=$(find $O/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/r06_train128_kernel_stats.csv
-timeout 500 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_BUSY_CYCLES SQ_WAVES --kernel-trace --output-format csv -d $O/raw1 -- python3 bench.py $ARGS > /dev/null 2> $O/err1.txt
+timeout 500 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_BUSY_CYCLES SQ_WAVES --kernel-trace --output-format csv -d $O/raw1 -- python3 bench.py --full $ARGS > /dev/null 2> $O/err1.txt
 f=$(find $O/raw1 -name "*counter_collection.csv" | head -1); [ -n "$f" ] && cp $f $O/counters1.csv
 python3 - <<'PY' > $O/r06_train128_counters.json
 import collections, csv, json, os

@@ -24,7 +24,7 @@ for (f, d, g), cs in acc.items():
         for c, v in cs.items():
             per[c].append(v)
 launch = {c: sum(v) / len(v) for c, v in per.items()}
-res = {"command": "rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --steps 50 --warmup 40 --settle 60 --steps-per-launch 50 "
+res = {"command": "rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --full --steps 50 --warmup 40 --settle 60 --steps-per-launch 50 "
                   "--no-cpu-baseline --no-secondary --min-time 0 (one pass per counter group, tools/train_profile.sh)",
        "kernel": "rem2d_step_train_kernel", "steps_per_launch": STEPS, "grid_size": modal,
        "launches_averaged": {c: len(v) for c, v in per.items()}, "per_launch": launch, "step_groups": 1}
