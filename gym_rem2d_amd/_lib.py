@@ -182,12 +182,13 @@ _ID_MARKER = b"REM2D_BUILD_ID="
 
 def source_id(extra=()):
     """Identity of a build of the library as the sources stand NOW: sha256 over every file under csrc/ (name and bytes, in
-    name order), include/rem2d.h and the compile flags, 16 hex digits.  build() compiles it in (-DREM2D_BUILD_ID), lib()
+    name order), the headers under include/ and the compile flags, 16 hex digits.  build() compiles it in (-DREM2D_BUILD_ID), lib()
     compares it with rem2d_build_id() and refuses a library built from anything else."""
     import hashlib
     csrc = os.path.dirname(SRC_PATH)
     h = hashlib.sha256()
-    for path in sorted(os.path.join(csrc, f) for f in os.listdir(csrc)) + [os.path.join(INCLUDE_DIR, "rem2d.h")]:
+    headers = sorted(os.path.join(INCLUDE_DIR, f) for f in os.listdir(INCLUDE_DIR) if f.endswith(".h"))
+    for path in sorted(os.path.join(csrc, f) for f in os.listdir(csrc)) + headers:
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:
             h.update(f.read())
@@ -281,6 +282,7 @@ def lib(wide=False):
     L.rem2d_world_reset.argtypes = [C.c_void_p, C.POINTER(Morph), C.c_void_p]
     L.rem2d_world_set_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     L.rem2d_world_set_outputs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rem2d_world_gather.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
     L.rem2d_plan_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.rem2d_plan_tiles_shape.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_void_p, C.c_void_p]

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "rem2d.h"
+#include "rem2d_gather.h"
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -1355,6 +1356,37 @@ extern "C" int rem2d_world_field(const rem2d_world *w, int32_t field, size_t *of
     int dt = 0;
     field_place(w->L, field, offset_bytes, count, &dt);
     if (dtype) *dtype = dt;
+    return REM2D_OK;
+}
+
+// ---- population-order read-back of a per-creature field (include/rem2d_gather.h) ----
+// Part of this library's code object, which the first step has loaded: a caller's first read after the steps loads nothing.  (A torch
+// indexing kernel in its place loads its own code object at its first launch: 8-45 ms inside the first timed block of bench.py.)
+template <typename T>
+__global__ void rem2d_gather_kernel(const T *src, const int32_t *index, unsigned n, T *out, unsigned long long outCount) {
+    const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const int32_t i = index[e];
+    if (i >= 0 && (unsigned long long)i < outCount) out[i] = src[e];
+}
+extern "C" int rem2d_world_gather(const rem2d_world *w, int32_t field, void *out_dev, int64_t out_count, void *stream) {
+    if (!w) return fail(REM2D_E_INVALID, "world is NULL");
+    if (field < REM2D_F_WOD || field >= REM2D_F_COUNT) return fail(REM2D_E_INVALID, "gather: not a per-creature field");
+    if (!out_dev || out_count < 0) return fail(REM2D_E_INVALID, "gather: no output buffer");
+    if (!w->S.outIndex) return fail(REM2D_E_STATE, "gather: rem2d_world_set_outputs has installed no population index");
+    size_t off = 0;
+    int dt = 0;
+    field_place(w->L, field, &off, nullptr, &dt);
+    const unsigned n = (unsigned)w->cfg.n_envs;
+    HIP_TRY(hipSetDevice(w->cfg.device));
+    const dim3 grid((n + 255u) / 256u), block(256);
+    if (dt == REM2D_DT_F64)
+        hipLaunchKernelGGL(rem2d_gather_kernel<uint64_t>, grid, block, 0, (hipStream_t)stream, (const uint64_t *)(w->state + off),
+                           w->S.outIndex, n, (uint64_t *)out_dev, (unsigned long long)out_count);
+    else
+        hipLaunchKernelGGL(rem2d_gather_kernel<uint32_t>, grid, block, 0, (hipStream_t)stream, (const uint32_t *)(w->state + off),
+                           w->S.outIndex, n, (uint32_t *)out_dev, (unsigned long long)out_count);
+    HIP_TRY(hipGetLastError());
     return REM2D_OK;
 }
 

@@ -404,9 +404,11 @@ class BatchedModular2D:
     def _gather(self, name, out):
         if len(self.worlds) == 1 and not self._compacted:
             return self.worlds[0][0].view(name).clone()   # a snapshot, like the multi-world path
-        for wi, (w, idx) in enumerate(self.worlds):   # (creatures compact() has dropped keep the values it stored in `out`)
+        # (creatures compact() has dropped keep the values it stored in `out`; the others are copied by the library's own kernel --
+        # torch's index_copy_ here loaded a code object at its first launch, tens of ms inside a caller's first read)
+        for wi, (w, _) in enumerate(self.worlds):
             if wi not in self._inactive:
-                out.index_copy_(0, idx, w.view(name).to(out.dtype))
+                w.gather(name, out)
         return out.clone()   # (`out` is the persistent population-order buffer compact() writes to: callers get a snapshot)
 
     # ---- evaluate(): drop the creatures whose fitness is final ----

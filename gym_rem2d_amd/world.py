@@ -157,6 +157,15 @@ class BatchedWorld:
         self._outputs = (reward, done, index)
         self._check(self.L.rem2d_world_set_outputs(self.h, reward.data_ptr(), done.data_ptr(), index.data_ptr()))
 
+    def gather(self, name, out):
+        """out[index[e]] = field `name` of creature e, for a per-creature field, with the `index` of set_outputs (population order;
+        rem2d_world_gather, include/rem2d_gather.h): one kernel of this library on the current stream.  ``out``: a contiguous
+        device tensor of the field's own dtype."""
+        dtype = self.view(name).dtype
+        if out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("gather(%r): out must be a contiguous %s tensor on %s" % (name, dtype, self.device))
+        self._check(self.L.rem2d_world_gather(self.h, _lib.FIELD_ID[name], out.data_ptr(), out.numel(), self._stream()))
+
     def step(self, n_steps=1):
         self._check(self.L.rem2d_world_step(self.h, int(n_steps), self._stream()))
 
