@@ -86,6 +86,10 @@ MORPH_FIELDS = ("shape", "hx", "hy", "x", "y", "angle", "parent", "jround", "ax"
                 "lower", "upper", "amp", "phase", "freq", "offset", "istate")
 
 
+RENDER_ABI_VERSION = 1      # include/rem2d_render.h
+RENDER_MAX_SIZE = 8192      # REM2D_RENDER_MAX_SIZE
+
+
 class WorldCfg(C.Structure):
     _fields_ = [("n_envs", C.c_int32), ("lanes", C.c_int32), ("flags", C.c_uint32), ("device", C.c_int32)]
 
@@ -313,6 +317,12 @@ def lib(wide=False):
     L.rem2d_world_kernel_time_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.rem2d_world_step_time_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.rem2d_world_handover_failures.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
+    # the renderer (include/rem2d_render.h)
+    L.rem2d_render_abi_version.restype = C.c_int
+    L.rem2d_world_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p]
+    if L.rem2d_render_abi_version() != RENDER_ABI_VERSION:
+        raise Rem2dError("%s: render ABI version mismatch" % os.path.basename(path))
     if L.rem2d_abi_version() != 11:
         raise Rem2dError("%s: ABI version mismatch" % os.path.basename(path))
     L.rem2d_build_id.restype = C.c_char_p

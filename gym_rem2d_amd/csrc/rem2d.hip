@@ -38,6 +38,7 @@
 
 #include "rem2d.h"
 #include "rem2d_gather.h"
+#include "rem2d_render.h"
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -91,6 +92,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_pipeline.h"
 #include "rem2d_vel4.h"
 #include "rem2d_diversity.h"
+#include "rem2d_raster.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -1386,6 +1388,39 @@ extern "C" int rem2d_world_gather(const rem2d_world *w, int32_t field, void *out
     else
         hipLaunchKernelGGL(rem2d_gather_kernel<uint32_t>, grid, block, 0, (hipStream_t)stream, (const uint32_t *)(w->state + off),
                            w->S.outIndex, n, (uint32_t *)out_dev, (unsigned long long)out_count);
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
+}
+
+// ---- the creature renderer (include/rem2d_render.h, rem2d_raster.h) ----
+extern "C" int rem2d_render_abi_version(void) { return REM2D_RENDER_ABI_VERSION; }
+extern "C" int rem2d_world_render(const rem2d_world *w, const int32_t *creatures_dev, int32_t n, const float *cam_xy_dev,
+                                  const uint8_t *fill_rgb_dev, const uint8_t *line_rgb_dev, int32_t width, int32_t height,
+                                  uint8_t *out_dev, void *stream) {
+    if (!w) return fail(REM2D_E_INVALID, "render: world is NULL");
+    if (n < 0) return fail(REM2D_E_INVALID, "render: n < 0");
+    if (width < 1 || height < 1 || width > REM2D_RENDER_MAX_SIZE || height > REM2D_RENDER_MAX_SIZE)
+        return fail(REM2D_E_INVALID, "render: width and height must be 1.." + std::to_string(REM2D_RENDER_MAX_SIZE) + ", not " +
+                                         std::to_string(width) + " x " + std::to_string(height));
+    if (!w->haveTerrain) return fail(REM2D_E_STATE, "render: rem2d_world_set_terrain must be called before render");
+    if (n == 0) return REM2D_OK;
+    if (!creatures_dev || !cam_xy_dev || !out_dev) return fail(REM2D_E_INVALID, "render: NULL device pointer");
+    if (w->cfg.lanes > 64) return fail(REM2D_E_INVALID, "render: more than 64 lanes per creature");
+    static_assert(R_MAX_SIZE == REM2D_RENDER_MAX_SIZE, "one size limit");
+    HIP_TRY(hipSetDevice(w->cfg.device));
+    std::vector<int32_t> idx((size_t)n);
+    HIP_TRY(hipMemcpyAsync(idx.data(), creatures_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int32_t k = 0; k < n; ++k)
+        if (idx[k] < 0 || idx[k] >= w->cfg.n_envs)
+            return fail(REM2D_E_INVALID, "render: creature index " + std::to_string(idx[k]) + " (image " + std::to_string(k) +
+                                             ") outside the world's 0.." + std::to_string(w->cfg.n_envs - 1));
+    const int tilesX = (width + R_TILE_W - 1) / R_TILE_W, tilesY = (height + R_TILE_H - 1) / R_TILE_H;
+    const long long blocks = (long long)tilesX * tilesY * n;
+    if (blocks > 0x7fffffffLL) return fail(REM2D_E_INVALID, "render: too many images for one launch");
+    hipLaunchKernelGGL(rem2d_render_kernel, dim3((unsigned)blocks), dim3(R_THREADS), 0, (hipStream_t)stream, w->S, w->T, w->cfg.lanes,
+                       w->cfg.n_envs, creatures_dev, cam_xy_dev, fill_rgb_dev, line_rgb_dev, (int)width, (int)height, tilesX,
+                       tilesX * tilesY, out_dev);
     HIP_TRY(hipGetLastError());
     return REM2D_OK;
 }

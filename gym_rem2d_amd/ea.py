@@ -79,15 +79,48 @@ def make_config(**kw):
             "experiment": {"checkpoint_frequency": p["checkpoint_frequency"]}}
 
 
+def show_best_episode(individual, tree_depth=None, interval=5, frames_dir=None, max_steps=None, width=800, height=600,
+                      device=None):
+    """Re-evaluates one individual in a 1-creature env and renders it every ``interval`` steps -- the reference's ``show_best``
+    (``toolbox.evaluate(bestOffspring, INTERVAL=5, HEADLESS=False)``, REM2D_main.py:331-344) and ``load_best``
+    (:162-167).  The frames (render.record_frames: the reference's scrolling camera) go to ``frames_dir`` as
+    ``frame<step>.png`` when it is given.  Returns (fitness, number of frames); the fitness is evaluate()'s rule on the same
+    episode cap as the batched evaluation."""
+    from . import _lib
+    from .env import BatchedModular2D
+    from .evaluate import EPISODE_CAP
+    from .render import record_frames, write_png
+    if tree_depth is None:
+        tree_depth = individual.tree_depth
+    env = BatchedModular2D(flags=_lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN, device=device)
+    try:
+        env.reset([individual.genome.create(tree_depth)], [individual.genome.moduleList])
+        n = 0
+        for step, frames in record_frames(env, EPISODE_CAP if max_steps is None else max_steps, [0], every=interval,
+                                          width=width, height=height):
+            if frames_dir is not None:
+                write_png(frames, frames_dir, prefix="frame", start=step)
+            n += 1
+        fit = float(env.fitness[0])
+    finally:
+        env.close()
+    return fit, n
+
+
 def run_ea(config=None, population=None, evaluate_batch=None, seed=None, save_dir=None, n_generations=None,
-           log=print, fitness_data=None):
+           log=print, fitness_data=None, show_best=False, interval=5, frames_dir=None):
     """Run the generational loop.  ``evaluate_batch(list[Individual]) -> list[float]`` defaults to one
     batched GPU episode.  Returns (population, history) with history rows (gen, min, max, mean, seconds).
 
     With ``save_dir`` the run leaves the reference's files in the reference's pickle format
     (REM2D_main.py:192-194,310-329; compat.dump_reference_pickle): ``s_`` (FitnessData: percentiles per generation),
     ``s_pop<gen>`` every ``checkpoint_frequency`` generations and ``s_elite<gen>`` whenever the best fitness is
-    positive -- the reference can resume from them or replay the elite (REM2D_main.py:165,177-178)."""
+    positive -- the reference can resume from them or replay the elite (REM2D_main.py:165,177-178).
+
+    With ``show_best`` (the reference's ``[ea] show_best``, on in its 0.cfg) the best offspring of every generation is evaluated
+    again in a 1-creature env and rendered every ``interval`` steps (:func:`show_best_episode`), its frames written under
+    ``frames_dir/gen<i>/`` when ``frames_dir`` is given, and ``Fitness of best = ...`` logged (REM2D_main.py:331-344).
+    ``run_ea.last_show_best`` keeps (generation, fitness, frames) per generation."""
     from .compat import FitnessData, dump_reference_pickle
     fitness_data = fitness_data if fitness_data is not None else FitnessData()
     config = config or make_config()
@@ -115,6 +148,7 @@ def run_ea(config=None, population=None, evaluate_batch=None, seed=None, save_di
             return fits
 
     run_ea.last_unresolved = []
+    run_ea.last_show_best = []
     if population is None:
         population = [Individual.random(config=config) for _ in range(pop_size)]
         for ind, fit in zip(population, evaluate_batch(population)):
@@ -136,6 +170,13 @@ def run_ea(config=None, population=None, evaluate_batch=None, seed=None, save_di
         if log:
             log("Generation %d evaluated ( %.2fs ) : Min %s, Max %s, Avg %s" % (row[0], row[4], row[1], row[2], row[3]))
         fitness_data.addFitnessData(fits, gen)
+        if show_best:
+            best = offspring[int(np.argmax(fits))]
+            out = os.path.join(frames_dir, "gen%d" % gen) if frames_dir is not None else None
+            fit, n_frames = show_best_episode(best, tree_depth, interval=interval, frames_dir=out)
+            run_ea.last_show_best.append((gen, fit, n_frames))
+            if log:
+                log("Fitness of best =  %r" % fit)
         if save_dir is not None:
             os.makedirs(save_dir, exist_ok=True)
             prefix = os.path.join(save_dir, "s_")            # SAVE_FILE_DIRECTORY (REM2D_main.py:194)

@@ -8,8 +8,8 @@
 ``BatchedModular2D`` is the same environment for N creatures at once: ``reset(trees,
 module_lists)`` compiles every tree into the SoA layout, groups creatures by lane count
 (homogeneous waves) and uploads them; ``step(n)`` advances all of them n steps on the GPU and
-returns ``reward[N]`` / ``done[N]`` torch tensors.  Rendering (pyglet, ``:655-768``) is out of
-scope.
+returns ``reward[N]`` / ``done[N]`` torch tensors.  ``render()`` draws them on the device (gym_rem2d_amd.render);
+the reference's pyglet window (``:655-768``) is out of scope.
 """
 import copy
 import ctypes as C
@@ -144,6 +144,7 @@ class BatchedModular2D:
         Like the reference, each tree is deep-copied so that the env owns controller state."""
         if module_lists is None or (len(module_lists) > 0 and not isinstance(module_lists[0], (list, tuple))):
             module_lists = [module_lists] * len(trees)
+        self.module_lists = list(module_lists)   # (render.tree_colors: the reference colours a body by node.type / len(module_list))
         self.trees, self.robots, specs = [], [], []
         for tree, ml in zip(trees, module_lists):
             t = copy.deepcopy(tree)
@@ -495,6 +496,15 @@ class BatchedModular2D:
         """REM2D_ERR_* bits per creature, int32 [N] (the one read that never raises HandoverError: it is how a caller finds the
         creatures concerned)."""
         return self._gather("err", self._err_pop)
+
+    def render(self, creatures=None, mode='rgb_array', **kw):
+        """Frames of the creatures as they stand now: uint8 [n, H, W, 3] on the device (gym's rgb_array layout, one image per
+        creature), drawn by the library's renderer (render.render_frames, which takes the keyword arguments: width, height,
+        camera, fill, line).  ``creatures``: population indices, default all.  Only ``mode='rgb_array'`` exists here."""
+        if mode != 'rgb_array':
+            raise NotImplementedError("BatchedModular2D.render: only mode='rgb_array'")
+        from .render import render_frames
+        return render_frames(self, range(self.n_envs) if creatures is None else creatures, **kw)
 
     def close(self):
         for w, _ in self.worlds:
