@@ -31,6 +31,11 @@ DEV float fabs32(float a) { return a > 0.0f ? a : -a; }
 // follows (sums, products, comparisons against 0 -- there is no division by it), and -0 == +0 in every comparison the
 // tests make (the digests add +0.0 first).
 DEV float fclamp(float a, float lo, float hi) { return __builtin_amdgcn_fmed3f(a, lo, hi); }
+// b2Clamp(a, -m, m) for EITHER sign of m: the friction bound m = friction * normalImpulse is negative while a warm-start normal
+// impulse is (only a state written from outside has one: the solver leaves none), and b2Max(-m, b2Min(a, m)) is then -m
+// whatever a is -- the median of (a, -m, m) is not.  With |m| as the upper bound the median is b2Clamp's value in both
+// cases (m >= 0: the same three numbers; m < 0: two of the three are -m).  The |.| is a source modifier of v_med3_f32.
+DEV float fclamp_sym(float a, float m) { return __builtin_amdgcn_fmed3f(a, -m, __builtin_fabsf(m)); }
 DEV V2 vmin2(V2 a, V2 b) { return mk(fmin32(a.x, b.x), fmin32(a.y, b.y)); }
 DEV V2 vmax2(V2 a, V2 b) { return mk(fmax32(a.x, b.x), fmax32(a.y, b.y)); }
 DEV float vnormalize(V2 &a) {

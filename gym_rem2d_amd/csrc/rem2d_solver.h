@@ -192,7 +192,7 @@ DEV void contact_solve(ContactC &c, float mB, float iB, float friction, float &v
         float vt = vdot(dv, tangent) - 0.0f;
         float lambda = c.tm0 * (-vt);
         float maxFriction = friction * c.n0;
-        float newImpulse = fclamp(c.t0 + lambda, -maxFriction, maxFriction);
+        float newImpulse = fclamp_sym(c.t0 + lambda, maxFriction);
         lambda = newImpulse - c.t0;
         c.t0 = newImpulse;
         V2 P = vscale(lambda, tangent);
@@ -204,7 +204,7 @@ DEV void contact_solve(ContactC &c, float mB, float iB, float friction, float &v
         float vt = vdot(dv, tangent) - 0.0f;
         float lambda = c.tm1 * (-vt);
         float maxFriction = friction * c.n1;
-        float newImpulse = fclamp(c.t1 + lambda, -maxFriction, maxFriction);
+        float newImpulse = fclamp_sym(c.t1 + lambda, maxFriction);
         lambda = newImpulse - c.t1;
         c.t1 = newImpulse;
         V2 P = vscale(lambda, tangent);
@@ -291,7 +291,7 @@ DEV void contact_solve_quad(ContactC &c, const QuadRole &r, float mB, float iB, 
         float vt = p + quad_swap1(p);
         float lambda = c.tm0 * (-vt);
         float maxFriction = friction * c.n0;
-        float newImpulse = fclamp(c.t0 + lambda, -maxFriction, maxFriction);
+        float newImpulse = fclamp_sym(c.t0 + lambda, maxFriction);
         lambda = newImpulse - c.t0;
         c.t0 = newImpulse;
         float P = lambda * r.tq;
@@ -305,7 +305,7 @@ DEV void contact_solve_quad(ContactC &c, const QuadRole &r, float mB, float iB, 
         float vt = p + quad_swap1(p);
         float lambda = c.tm1 * (-vt);
         float maxFriction = friction * c.n1;
-        float newImpulse = fclamp(c.t1 + lambda, -maxFriction, maxFriction);
+        float newImpulse = fclamp_sym(c.t1 + lambda, maxFriction);
         lambda = newImpulse - c.t1;
         c.t1 = newImpulse;
         float P = lambda * r.tq;
@@ -377,7 +377,7 @@ DEV void contact_solve_pair(ContactC &c, const QuadRole &r, float mB, float iB, 
         float vt = p + quad_swap1(p);
         float lambda = c.tm0 * (-vt);
         float maxFriction = friction * c.n0;
-        float newImpulse = fclamp(c.t0 + lambda, -maxFriction, maxFriction);
+        float newImpulse = fclamp_sym(c.t0 + lambda, maxFriction);
         lambda = newImpulse - c.t0;
         c.t0 = newImpulse;
         float P = lambda * r.tq;
@@ -391,7 +391,7 @@ DEV void contact_solve_pair(ContactC &c, const QuadRole &r, float mB, float iB, 
         float vt = p + quad_swap1(p);
         float lambda = c.tm1 * (-vt);
         float maxFriction = friction * c.n1;
-        float newImpulse = fclamp(c.t1 + lambda, -maxFriction, maxFriction);
+        float newImpulse = fclamp_sym(c.t1 + lambda, maxFriction);
         lambda = newImpulse - c.t1;
         c.t1 = newImpulse;
         float P = lambda * r.tq;
