@@ -88,6 +88,7 @@ MORPH_FIELDS = ("shape", "hx", "hy", "x", "y", "angle", "parent", "jround", "ax"
 
 RENDER_ABI_VERSION = 1      # include/rem2d_render.h
 RENDER_MAX_SIZE = 8192      # REM2D_RENDER_MAX_SIZE
+CONTROL_ABI_VERSION = 1     # include/rem2d_control.h
 
 
 class WorldCfg(C.Structure):
@@ -323,6 +324,13 @@ def lib(wide=False):
                                      C.c_void_p, C.c_void_p]
     if L.rem2d_render_abi_version() != RENDER_ABI_VERSION:
         raise Rem2dError("%s: render ABI version mismatch" % os.path.basename(path))
+    # closed-loop control (include/rem2d_control.h)
+    L.rem2d_control_abi_version.restype = C.c_int
+    L.rem2d_worlds_observe.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    L.rem2d_worlds_control.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                       C.c_void_p]
+    if L.rem2d_control_abi_version() != CONTROL_ABI_VERSION:
+        raise Rem2dError("%s: control ABI version mismatch" % os.path.basename(path))
     if L.rem2d_abi_version() != 11:
         raise Rem2dError("%s: ABI version mismatch" % os.path.basename(path))
     L.rem2d_build_id.restype = C.c_char_p

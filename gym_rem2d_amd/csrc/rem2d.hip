@@ -39,6 +39,7 @@
 #include "rem2d.h"
 #include "rem2d_gather.h"
 #include "rem2d_render.h"
+#include <rem2d_control.h> // the public header (include/); the quoted name below is the kernels' file beside this one
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -93,6 +94,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_vel4.h"
 #include "rem2d_diversity.h"
 #include "rem2d_raster.h"
+#include "rem2d_control.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -1422,6 +1424,73 @@ extern "C" int rem2d_world_render(const rem2d_world *w, const int32_t *creatures
                        w->cfg.n_envs, creatures_dev, cam_xy_dev, fill_rgb_dev, line_rgb_dev, (int)width, (int)height, tilesX,
                        tilesX * tilesY, out_dev);
     HIP_TRY(hipGetLastError());
+    return REM2D_OK;
+}
+
+// ---- closed-loop control (include/rem2d_control.h, csrc/rem2d_control.h) ----
+extern "C" int rem2d_control_abi_version(void) { return REM2D_CONTROL_ABI_VERSION; }
+// Checks the worlds of a control call; `what` prefixes the message.
+static int control_worlds_ok(const char *what, rem2d_world *const *worlds, int32_t n_worlds, int32_t max_bodies, int64_t rows,
+                             const void *buffer_dev) {
+    const std::string p = std::string(what) + ": ";
+    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, p + "no worlds");
+    if (!buffer_dev) return fail(REM2D_E_INVALID, p + "NULL device pointer");
+    if (max_bodies < 1 || max_bodies > REM2D_CONTROL_MAX_BODIES)
+        return fail(REM2D_E_INVALID, p + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(max_bodies));
+    if (rows < 0) return fail(REM2D_E_INVALID, p + "negative row count");
+    for (int32_t i = 0; i < n_worlds; ++i) {
+        if (!worlds[i]) return fail(REM2D_E_INVALID, p + "world " + std::to_string(i) + " is NULL");
+        if (worlds[i]->cfg.lanes > 64) return fail(REM2D_E_INVALID, p + "more than 64 lanes per creature");
+        if (worlds[i]->cfg.device != worlds[0]->cfg.device) return fail(REM2D_E_INVALID, p + "the worlds must share a device");
+        if (!worlds[i]->haveReset) return fail(REM2D_E_STATE, p + "rem2d_world_reset (or adopt) must be called first");
+    }
+    return REM2D_OK;
+}
+// The table of worlds [first, first + n) of a call (n <= CTL_TABLE) -> the 64-lane blocks of the launch.
+static unsigned control_table(CtlTable &Tb, rem2d_world *const *worlds, int first, int n) {
+    memset(&Tb, 0, sizeof(Tb));
+    unsigned blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const rem2d_world *w = worlds[first + i];
+        CtlWorld &c = Tb.w[i];
+        c.lane4 = w->S.lane4; c.lane8 = w->S.lane8; c.slot4 = w->S.slot4; c.env8 = w->S.env8;
+        c.index = w->S.outIndex;
+        c.Lp = w->S.Lp; c.Np = w->S.Np; c.nEnvs = w->S.nEnvs; c.lanes = (unsigned)w->cfg.lanes;
+        blocks += (unsigned)w->L.Lp / WAVE;
+        c.blockEnd = blocks;
+    }
+    Tb.n = n;
+    return blocks;
+}
+extern "C" int rem2d_worlds_observe(rem2d_world *const *worlds, int32_t n_worlds, int32_t max_bodies, float *out_dev, int64_t out_rows,
+                                    void *stream) {
+    const int rc = control_worlds_ok("observe", worlds, n_worlds, max_bodies, out_rows, out_dev);
+    if (rc != REM2D_OK) return rc;
+    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
+    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
+        CtlTable Tb;
+        const unsigned blocks = control_table(Tb, worlds, first, std::min(CTL_TABLE, (int)n_worlds - first));
+        const unsigned per = CTL_THREADS / WAVE;
+        hipLaunchKernelGGL(rem2d_observe_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb,
+                           (int)max_bodies, out_dev, (long long)out_rows);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+extern "C" int rem2d_worlds_control(rem2d_world *const *worlds, int32_t n_worlds, int32_t mode, const double *values_dev,
+                                    int32_t max_bodies, int64_t n_rows, const uint8_t *mask_dev, void *stream) {
+    if (mode != REM2D_CTRL_TARGET && mode != REM2D_CTRL_PARAMS) return fail(REM2D_E_INVALID, "control: unknown mode " + std::to_string(mode));
+    const int rc = control_worlds_ok("control", worlds, n_worlds, max_bodies, n_rows, values_dev);
+    if (rc != REM2D_OK) return rc;
+    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
+    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
+        CtlTable Tb;
+        const unsigned blocks = control_table(Tb, worlds, first, std::min(CTL_TABLE, (int)n_worlds - first));
+        const unsigned per = CTL_THREADS / WAVE;
+        hipLaunchKernelGGL(rem2d_control_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb,
+                           (int)mode, values_dev, (int)max_bodies, (long long)n_rows, (const unsigned char *)mask_dev);
+        HIP_TRY(hipGetLastError());
+    }
     return REM2D_OK;
 }
 

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, gymshim
+from . import _lib, control, gymshim
 from .compiler import Morphology, build_creature, lanes_for
 from .terrain import make_terrain
 from .world import BatchedWorld
@@ -185,6 +185,9 @@ class BatchedModular2D:
         self._group_args = None
         self.n_envs = n_envs
         self.streams = []
+        self._obs = None                                       # observe()'s persistent buffer: made (zeroed) on first use after a reset
+        self._obs_bodies = max(m.lanes for m, _ in batches)    # default max_bodies of observe(): the largest lane bucket
+        self._ctl_keep = None
         # Step groups: a step is a chain of four launches, each as long as its slowest wavefront; independent parts of the
         # population on their own streams let one part's tail run under another part's kernels.  (Creatures are
         # independent, so any split is legal.)  What counts is the number of 64-lane blocks and how long a step is: below
@@ -295,6 +298,11 @@ class BatchedModular2D:
             # step() returns them without a gather per world
             for w, idx in self.worlds:
                 w.set_outputs(self._reward, self._done, idx.to(torch.int32))
+        elif not np.array_equal(self._uploaded[0][1], np.arange(n_envs)):
+            # one world whose creature order is not the population's (reset_specs sorts a lane bucket by schedule): observe() and
+            # set_joint_targets() find the population row of a creature through the same index (decided here, on the host array)
+            w, idx = self.worlds[0]
+            w.set_outputs(self._reward, self._done, idx.to(torch.int32))
 
     def _world_options(self):
         opts = dict(getattr(self, "_launch_options", {}), **self.options)
@@ -497,6 +505,62 @@ class BatchedModular2D:
         creatures concerned)."""
         return self._gather("err", self._err_pop)
 
+    # ---- closed loop: what the creatures sense, what the caller sets on their joints (include/rem2d_control.h) ----
+    def _control_worlds(self):
+        """The worlds still being stepped (the population index each of them carries was installed by _upload / compact)."""
+        return [w for wi, (w, _) in enumerate(self.worlds) if wi not in self._inactive and getattr(w, "h", None)]
+
+    @property
+    def max_bodies(self):
+        """observe()'s default ``max_bodies``: the lanes of the population's largest lane bucket."""
+        return self._obs_bodies
+
+    def observe(self, max_bodies=None, out=None):
+        """What every creature senses now: float32 ``[N, 8 + 6 * max_bodies]`` on the device, rows in population order, columns as
+        ``control.layout(max_bodies)`` names them (root pose and velocity, distance to the wall of death, body count; per body in
+        ``robot.components`` order: joint angle, joint speed, limit state, touching contacts, position relative to the root).
+        One kernel of the library for the whole population, queued on the current stream like step(); nothing synchronises.
+        ``max_bodies``: default the population's largest lane bucket; bodies beyond it are dropped, missing ones read 0.
+        ``out``: a contiguous float32 tensor of that shape to write into; without it the env's persistent buffer is returned (zeroed
+        at reset, overwritten by the next call: clone what must last).  Rows of creatures that compact() has retired are not
+        written any more: they keep their last written observation."""
+        M = self._obs_bodies if max_bodies is None else int(max_bodies)
+        if out is None:
+            if self._obs is None or self._obs.shape[1] != control.width(M):
+                self._obs = torch.zeros((self.n_envs, control.width(M)), dtype=torch.float32, device=self.worlds[0][0].device)
+            out = self._obs
+        worlds = self._control_worlds()
+        if worlds:
+            control.observe(worlds, M, out)
+        return out
+
+    def set_joint_targets(self, targets, mask=None):
+        """Closed-loop joint targets for the steps that follow: ``targets`` ``[N, M]`` (float32 or float64, population order), column
+        b the target angle (radians) of the joint between body b and its parent, column 0 ignored; ``mask`` ``[N, M]``, false =
+        leave that joint as it is.  The joint's controller becomes amp = 0, offset = target, so the step's own PID drives the motor
+        towards it (motorSpeed = (target - jointAngle) * 1.9); its phase, frequency and i_state stay.  Values are written as given:
+        keep them finite and inside the joint limits (+-pi/2).  Queued on the current stream; with ``targets`` (and ``mask``) on the
+        env's device nothing synchronises -- a host array is accepted too, at the price of a blocking upload.
+
+        A creature that overflows the default build's contact slots (errors() & ERR_CAPACITY) cannot be replayed from reset in the
+        wide build under external actions, as evaluate.run_episode does for open-loop creatures: read errors(), or construct the env
+        with wide=True."""
+        self._control(control.CTRL_TARGET, targets, mask)
+
+    def set_controllers(self, params, mask=None):
+        """Oscillator parameters for the steps that follow: ``params`` ``[N, M, 4]`` = (amp, phase, freq, offset) of the joint between
+        body b and its parent (column 0 ignored), ``mask`` as in set_joint_targets.  The running i_state is never written: a changed
+        frequency bends the phase from where it is.  The capacity note of set_joint_targets holds here too."""
+        self._control(control.CTRL_PARAMS, params, mask)
+
+    def _control(self, mode, values, mask):
+        values = torch.as_tensor(values)
+        if values.shape[0] != self.n_envs:
+            raise ValueError("expected one row per creature (%d), got %d" % (self.n_envs, values.shape[0]))
+        worlds = self._control_worlds()
+        if worlds:
+            self._ctl_keep = control.control(worlds, mode, values, mask)   # (the tensors the queued kernel reads)
+
     def render(self, creatures=None, mode='rgb_array', **kw):
         """Frames of the creatures as they stand now: uint8 [n, H, W, 3] on the device (gym's rgb_array layout, one image per
         creature), drawn by the library's renderer (render.render_frames, which takes the keyword arguments: width, height,
@@ -517,8 +581,18 @@ class Modular2D(gymshim.Env):
     metadata = {'render.modes': ['human', 'rgb_array'], 'video.frames_per_second': FPS}
     hardcore = False
 
-    def __init__(self, random_seed=None, device=None):
+    DEFAULT_MAX_BODIES = 32
+
+    def __init__(self, random_seed=None, device=None, closed_loop=False, max_bodies=DEFAULT_MAX_BODIES, wide=False):
+        """closed_loop=False: the reference's surface -- step(action) ignores the action and returns observation 0.
+        closed_loop=True: ``observation_space`` is the ``8 + 6 * max_bodies`` floats of BatchedModular2D.observe (columns:
+        control.layout(max_bodies)), ``action_space`` ``max_bodies`` joint target angles within +-pi/2 (column b: the joint between
+        ``robot.components[b]`` and its parent; column 0 is ignored); reset() returns the first observation and step(action)
+        applies the action (None: leave the joints as they are) and returns the next one as a numpy array.  A creature that
+        overflows the default build's contact slots cannot be replayed in the wide build under external actions: read
+        ``env._batch.errors()``, or construct the env with wide=True."""
         self._device = device
+        self.closed_loop, self.max_bodies, self._wide = bool(closed_loop), int(max_bodies), wide
         self.seed(random_seed)
         self.viewer = None
         self.tree_morphology = None
@@ -529,6 +603,13 @@ class Modular2D(gymshim.Env):
         high = np.array([np.inf] * 24)
         self.action_space = gymshim.Box(np.array([-1, -1, -1, -1]), np.array([1, 1, 1, 1]), dtype=np.float32)
         self.observation_space = gymshim.Box(-high, high, dtype=np.float32)
+        if self.closed_loop:
+            if not 1 <= self.max_bodies <= control.MAX_BODIES:
+                raise ValueError("max_bodies must be 1..%d" % control.MAX_BODIES)
+            high = np.full(control.width(self.max_bodies), np.inf)
+            self.observation_space = gymshim.Box(-high, high, dtype=np.float32)
+            lim = np.full(self.max_bodies, np.pi / 2)
+            self.action_space = gymshim.Box(-lim, lim, dtype=np.float32)
         self._batch = None
 
     def seed(self, seed=None):
@@ -546,7 +627,7 @@ class Modular2D(gymshim.Env):
         self.robot = ModularRobotBox2D()
         if tree is None:
             return
-        self._batch = BatchedModular2D(hardcore=self.hardcore, seed=self._seed_value, device=self._device)
+        self._batch = BatchedModular2D(hardcore=self.hardcore, seed=self._seed_value, device=self._device, wide=self._wide)
         self._batch.reset([tree], [module_list])
         self.tree_morphology = self._batch.trees[0]
         self.robot = self._batch.robots[0]
@@ -561,7 +642,18 @@ class Modular2D(gymshim.Env):
         self._pin_done = torch.zeros(1, dtype=torch.bool).pin_memory()
         self._pin_index = torch.zeros(1, dtype=torch.int32, device=self.world.device)
         self.world.set_outputs(self._pin_reward, self._pin_done, self._pin_index)
+        if self.closed_loop:
+            self._obs_dev = torch.zeros((1, control.width(self.max_bodies)), dtype=torch.float32, device=self.world.device)
+            self._pin_obs = torch.zeros(control.width(self.max_bodies), dtype=torch.float32).pin_memory()
+            return self._observe()
         return
+
+    def _observe(self):
+        """The creature's observation row as a numpy array (closed loop): observe kernel, copy to pinned memory, one wait."""
+        self._batch.observe(self.max_bodies, out=self._obs_dev)
+        self._pin_obs.copy_(self._obs_dev[0], non_blocking=True)
+        torch.cuda.current_stream(self.world.device).synchronize()
+        return self._pin_obs.numpy().copy()
 
     def step(self, action):
         if self.wod:
@@ -569,10 +661,16 @@ class Modular2D(gymshim.Env):
         if self.tree_morphology is None:
             raise Exception("no tree_morphology")
         assert self._n_ctrl - 1 == len(self.robot.joints)
+        if self.closed_loop and action is not None:
+            a = np.asarray(action, dtype=np.float64).reshape(1, -1)
+            if a.shape[1] != self.max_bodies:
+                raise ValueError("action must have %d entries (max_bodies), got %d" % (self.max_bodies, a.shape[1]))
+            self._batch.set_joint_targets(torch.from_numpy(a))
         self.world.step(1)                      # one creature: straight to the C ABI, no bucket / group bookkeeping
+        obs = self._observe() if self.closed_loop else 0   # (waits for the stream like the line below)
         torch.cuda.current_stream(self.world.device).synchronize()
         r, d = float(self._pin_reward[0]), bool(self._pin_done[0])   # (host reads of the mapped buffer the kernels wrote)
-        return 0, (r if not d else -100), (True if d else 0), 0
+        return obs, (r if not d else -100), (True if d else 0), 0
 
     def render(self, mode='human'):
         """The reference paints into a pyglet window (Modular2DEnv.py:655-738; pyglet is not a dependency here).

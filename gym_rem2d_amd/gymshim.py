@@ -94,4 +94,9 @@ def make(id, **kwargs):
 # gym_rem2D/__init__.py:5-7
 register(id="Modular2DLocomotion-v0", entry_point="gym_rem2d_amd.env:Modular2D", max_episode_steps=240 * 20)
 
+# the same env with its observation and action spaces filled (gym_rem2d_amd.env.Modular2D(closed_loop=True); no counterpart in
+# the reference, whose step() ignores the action and returns observation 0)
+register(id="Modular2DLocomotionControl-v0", entry_point="gym_rem2d_amd.env:Modular2D", max_episode_steps=240 * 20,
+         kwargs={"closed_loop": True})
+
 __all__ = ["Env", "Box", "np_random", "TimeLimit", "register", "make"]
