@@ -47,6 +47,9 @@
 #define V4_PHASES 4
 #endif
 #endif
+#ifndef V4_STEADY
+#define V4_STEADY 1     // 0: every period group of the tick loop on the general code (experiments: what the steady body is worth)
+#endif
 #define V4_MAX_BODIES 256  // bodies per tile in the widest shape (LDS mailbox size)
 #define V4_MAX_PASSES (V4_MAX_BODIES / WAVE)
 
@@ -214,43 +217,74 @@ static_assert(KT <= 16, "manifold index: 4 bits");
 #define V4_COFF(k) (((k) >> 16) & 0xff)
 #define V4_CPHASE(k) (((k) >> 24) & 0x7)
 
+// one register-resident manifold's solve on its body's mailbox record (the body of a contact sub-slot, for the lanes the gate lets in)
+template <bool CPAIR, typename SH> DEV void v4_contact_lane(ContactT &c, SH &sh, bool pair, float mu) {
+    const int b = V4_CBODY(c.key);
+    V4Vel v = sh.vel[b];
+    if (!CPAIR || !pair) {
+        contact_solve(c.c, c.mB, v.invI, mu, v.x, v.y, v.w);
+        sh.vel[b] = v;
+    } else { // two lanes per manifold: this one carries component (lane & 1) of the body's velocity
+        float vq = c.r.isY ? v.y : v.x;
+        contact_solve_pair(c.c, c.r, c.mB, v.invI, mu, vq, v.w);
+        if (!c.r.isY) sh.vel[b].x = vq;
+        else { sh.vel[b].y = vq; sh.vel[b].w = v.w; }
+    }
+}
+
+// the same for a manifold beyond the register sets (key e of the tile's contact map): constraint and impulses through scratch
+template <typename SH> DEV void v4_contact_spilled(const State &S, SH &sh, int e, float mu) {
+    const unsigned Lp = S.Lp;
+    const int b = V4_CBODY(e);
+    const unsigned gl = sh.glmap[b];
+    const unsigned cb = (unsigned)(SCR_CC_BASE + V4_CT(e) * CC_WORDS) * Lp + gl;
+    ContactC c;
+    cc_load(S, cb, c);
+    V4Vel v = sh.vel[b];
+    contact_solve(c, LF(L_INVM), v.invI, mu, v.x, v.y, v.w);
+    sh.vel[b] = v;
+    SW(cb, 10) = c.n0; SW(cb, 11) = c.n1; SW(cb, 12) = c.t0; SW(cb, 13) = c.t1;
+}
+
 // the contact sub-slots of the tick `tick` (phase ph): every manifold scheduled here, in the order of its body's list
 template <int CSETS, bool CPAIR, typename SH>
 DEV void v4_contact_subslots(const State &S, ContactT (&C)[CSETS], SH &sh, int lane, int NC, bool spill,
                              bool pair, int nsub, int ph, int tick, int span, float mu) {
-    const unsigned Lp = S.Lp;
     for (int t = 0; t < nsub; ++t) {
 #pragma unroll
         for (int cs = 0; cs < CSETS; ++cs) {
             // off = ph (mod P) and off <= tick < off + iters P: the manifold runs in this tick, in sub-slot `sub`
             if (V4_VALID(C[cs].key) && V4_CSUB(C[cs].key) == t && V4_CPHASE(C[cs].key) == ph &&
-                (unsigned)(tick - V4_COFF(C[cs].key)) < (unsigned)span) {
-                const int b = V4_CBODY(C[cs].key);
-                V4Vel v = sh.vel[b];
-                if (!CPAIR || !pair) {
-                    contact_solve(C[cs].c, C[cs].mB, v.invI, mu, v.x, v.y, v.w);
-                    sh.vel[b] = v;
-                } else { // two lanes per manifold: this one carries component (lane & 1) of the body's velocity
-                    float vq = C[cs].r.isY ? v.y : v.x;
-                    contact_solve_pair(C[cs].c, C[cs].r, C[cs].mB, v.invI, mu, vq, v.w);
-                    if (!C[cs].r.isY) sh.vel[b].x = vq;
-                    else { sh.vel[b].y = vq; sh.vel[b].w = v.w; }
-                }
-            }
+                (unsigned)(tick - V4_COFF(C[cs].key)) < (unsigned)span) v4_contact_lane<CPAIR>(C[cs], sh, pair, mu);
         }
         if (spill) {
             for (int ci = CSETS * WAVE + lane; ci < NC; ci += WAVE) { // (a tile that spills is not in pair mode)
                 const int e = (int)sh.cmap[ci];
-                const int b = V4_CBODY(e);
                 if (V4_CSUB(e) != t || V4_CPHASE(e) != ph || !((unsigned)(tick - V4_COFF(e)) < (unsigned)span)) continue;
-                const unsigned gl = sh.glmap[b];
-                const unsigned cb = (unsigned)(SCR_CC_BASE + V4_CT(e) * CC_WORDS) * Lp + gl;
-                ContactC c;
-                cc_load(S, cb, c);
-                V4Vel v = sh.vel[b];
-                contact_solve(c, LF(L_INVM), v.invI, mu, v.x, v.y, v.w);
-                sh.vel[b] = v;
-                SW(cb, 10) = c.n0; SW(cb, 11) = c.n1; SW(cb, 12) = c.t0; SW(cb, 13) = c.t1;
+                v4_contact_spilled(S, sh, e, mu);
+            }
+        }
+        lds_sync();
+    }
+}
+
+// The same sub-slots in a STEADY period group (vel4_body: every constraint of the tile is inside its window of ticks there, so who
+// runs in (phase, sub-slot) does not depend on the tick): the gate is one comparison of the lane's slot code -- phase << 4 | sub-slot,
+// -1 without a manifold -- with the slot's; a manifold beyond the register sets compares its key's two fields.
+#define V4_CCODE(ph, t) (((ph) << 4) | (t))
+template <bool B> struct V4Bool { static constexpr bool value = B; };
+template <int CSETS, bool CPAIR, bool SPILL, typename SH>
+DEV void v4_contact_subslots_steady(const State &S, ContactT (&C)[CSETS], const int (&ccode)[CSETS], SH &sh, int lane, int NC,
+                                    bool pair, int nsub, int ph, float mu) {
+    for (int t = 0; t < nsub; ++t) {
+#pragma unroll
+        for (int cs = 0; cs < CSETS; ++cs)
+            if (ccode[cs] == V4_CCODE(ph, t)) v4_contact_lane<CPAIR>(C[cs], sh, pair, mu);
+        if (SPILL) {
+            for (int ci = CSETS * WAVE + lane; ci < NC; ci += WAVE) {
+                const int e = (int)sh.cmap[ci];
+                if (V4_CSUB(e) != t || V4_CPHASE(e) != ph) continue;
+                v4_contact_spilled(S, sh, e, mu);
             }
         }
         lds_sync();
@@ -337,12 +371,13 @@ DEV void vel4_body(const State &S, const float friction, const Vel4Args &A, unsi
     //     sub-slot.
     // (2) creatures are independent, so each one may run its whole schedule -- joint rounds and contact ticks alike --
     //     any number of ticks late: every creature is rotated so that its heaviest contact phase (the most manifolds on
-    //     one body) falls on phase 0 of the tile.  Only with one joint register set: the host packed the others by phase.
+    //     one body) falls on phase 0 of the tile.  Only in the flexible shapes (FLEX: up to three register sets, joints placed by the
+    //     kernel): the static shapes' sets were packed by phase on the host.
     // (3) the period itself is a choice: the schedule is valid for any period >= the creatures' own (compiler.pipeline_schedule),
     //     and one more tick per iteration widens every body's window by one, so that bodies whose windows did not meet can
     //     share a contact tick.  A tile whose contact sub-slots outweigh a joint slot takes the longer period: the slowest
     //     tiles of a launch are such tiles (period 3-4 with 5-6 sub-slots per iteration, profiles/archive/r03_slow_tiles.txt).
-    //     Again only with one joint register set.
+    //     Again only in the flexible shapes.
     const unsigned long long groupLanes = (K >= WAVE ? ~0ull : ((1ull << K) - 1ull)) << (lane & ~(K - 1) & (WAVE - 1));
     int offB[PASSES], delta[PASSES];
     // the plan for period Pc: every body's contact tick offB (iteration 0) and its creature's rotation delta; returns the
@@ -436,6 +471,7 @@ DEV void vel4_body(const State &S, const float friction, const Vel4Args &A, unsi
     lds_sync();
 
     int NC = 0, lastTick = -1, maxRound = -1, err = 0, maxT = 0;
+    int firstHi = 0, firstLo = 0x7fffff; // the latest / earliest first tick of any joint or manifold of the tile (the steady ticks lie between)
     int jcount[SETS]; // lanes handed out in every register set (the phases ph = s mod SETS share set s)
 #pragma unroll
     for (int s = 0; s < SETS; ++s) jcount[s] = 0;
@@ -487,6 +523,7 @@ DEV void vel4_body(const State &S, const float friction, const Vel4Args &A, unsi
                 if (cph == s) subMax[s] = max(subMax[s], nT);
             if (cph >= V4_PHASES) err = REM2D_ERR_SOLVER_OVERFLOW;
             if (iters > 0) lastTick = max(lastTick, off + (iters - 1) * P);
+            firstHi = max(firstHi, off); firstLo = min(firstLo, off);
         }
 #pragma unroll
         for (int t = 0; t < KT; ++t) { // manifold t of every body: ranks in (pass, t, lane) order, sub-slot t
@@ -496,10 +533,14 @@ DEV void vel4_body(const State &S, const float friction, const Vel4Args &A, unsi
         }
         maxT = max(maxT, nT);
         if (iters > 0 && hasJ) lastTick = max(lastTick, jr + (iters - 1) * P);
-        if (hasJ) maxRound = max(maxRound, jr);
+        if (hasJ) { maxRound = max(maxRound, jr); firstHi = max(firstHi, jr); firstLo = min(firstLo, jr); }
     }
     const int nTicks = wave_max(lastTick) + 1;
     const int nRounds = wave_max(maxRound) + 1;
+    // (tLo / tHi are made of the first ticks themselves, the gates of the general code of their 8-bit copies in the keys, V4_JROUND /
+    // V4_COFF: the same numbers while first ticks stay below 256, which the key layout has always required -- a round count plus
+    // two periods: a creature has at most 64 bodies)
+    const int tLo = wave_max(firstHi), tHi = -wave_max(-firstLo) + iters * P; // every constraint fires in each tick of its phase in [tLo, tHi)
     maxT = wave_max(maxT);
 #pragma unroll
     for (int s = 0; s < V4_PHASES; ++s) subMax[s] = (V4_DBG(A) & 1) ? 0 : wave_max(subMax[s]);
@@ -605,7 +646,68 @@ DEV void vel4_body(const State &S, const float friction, const Vel4Args &A, unsi
         unsigned long long tJ = 0, tC = 0, t0 = 0, t1 = 0, nSub = 0;
         const unsigned long long tStart = stamp ? __builtin_amdgcn_s_memtime() : 0;
         const unsigned long long rStart = stamp ? __builtin_amdgcn_s_memrealtime() : 0; // constant 100 MHz
-        for (int base = 0; base < nTicks; base += P) {
+        // Ramp / steady split.  The window test of a slot's gate changes its answer only while the tile's constraints start up (ticks
+        // below tLo) and run out (from tHi on).  A period group [base, base + P) inside [tLo, tHi) is STEADY: every valid
+        // constraint of phase s fires in it, so the fire set of a slot is a constant of the tile.  Steady groups -- all but the
+        // first and last few of the ~180 -- run a body whose gates are one comparison each of a per-lane slot code made here
+        // (joints: the phase; manifolds: V4_CCODE), without window arithmetic, phase decode or a tick; FLEX's look at another
+        // set that no lane of the tile takes -- most of them -- is skipped on a scalar bit.  The slot bodies, their
+        // order and the lds_sync()s are those of the general code below, which runs the other groups: same bits.  The
+        // probe builds' stamped loop stays on the general code.
+        const bool steadyOK = V4_STEADY && joints && !stamp && tLo < tHi;
+        int jcode[SETS], ccode[CSETS];
+        unsigned jlook = 0; // bit q * 8 + s, q >= 1: some lane of set (s + q) mod SETS holds a joint of phase s
+#pragma unroll
+        for (int q = 0; q < SETS; ++q) jcode[q] = -1;
+#pragma unroll
+        for (int cs = 0; cs < CSETS; ++cs) ccode[cs] = -1;
+        if (steadyOK) { // (a tile without a steady group does not pay for the codes)
+#pragma unroll
+            for (int q = 0; q < SETS; ++q)
+                jcode[q] = !V4_VALID(J[q].key) ? -1 : SETS == V4_PHASES ? q : V4_JPHASE(J[q].key);
+#pragma unroll
+            for (int cs = 0; cs < CSETS; ++cs)
+                ccode[cs] = V4_VALID(C[cs].key) ? V4_CCODE(V4_CPHASE(C[cs].key), V4_CSUB(C[cs].key)) : -1;
+#pragma unroll
+            for (int s = 0; s < V4_PHASES; ++s) {
+#pragma unroll
+                for (int q = 1; q < ((FLEX && SETS > 1) ? SETS : 1); ++q)
+                    if (__ballot(jcode[(s + q) % SETS] == s)) jlook |= 1u << (q * 8 + s);
+            }
+        }
+        // (the steady groups of a tile, instantiated with and without the scratch path of the manifolds beyond the register sets: the
+        // loop that nearly every tile runs stays as short as it can be)
+        int base = 0;
+        auto steady_groups = [&](auto withSpill) {
+                for (; base + P <= tHi; base += P) { // (the steady groups: all of them lie below nTicks)
+#pragma unroll
+                    for (int s = 0; s < V4_PHASES; ++s) {
+                        if (s < P) {
+                            {
+                                JointT &Js = J[s % SETS];
+                                if (jcode[s % SETS] == s) v4_joint_slot(Js, sh);
+                            }
+                            if (FLEX && SETS > 1) {
+#pragma unroll
+                                for (int q = 1; q < SETS; ++q) {
+                                    if (jlook & (1u << (q * 8 + s))) {
+                                        JointT &Jo = J[(s + q) % SETS];
+                                        if (jcode[(s + q) % SETS] == s) v4_joint_slot(Jo, sh);
+                                    }
+                                }
+                            }
+                            lds_sync();
+                            v4_contact_subslots_steady<CSETS, CPAIR, decltype(withSpill)::value>(S, C, ccode, sh, lane, NC, pair, subMax[s], s, mu);
+                        }
+                    }
+                }
+        };
+        for (; base < nTicks; base += P) {
+            if (steadyOK && base >= tLo) {
+                if (spill) steady_groups(V4Bool<true>());
+                else steady_groups(V4Bool<false>());
+                if (base >= nTicks) break;
+            }
 #pragma unroll
             for (int s = 0; s < V4_PHASES; ++s) {
                 if (s < P) {
