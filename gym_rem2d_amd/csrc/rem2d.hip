@@ -19,8 +19,9 @@
 //   * the per-body broadphase pair list (edge index, feature keys, warm-start impulses) is
 //     SoA in HBM ([slot][lane], coalesced) and walked with rolled loops.
 //
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize (every binary32 operation rounded
-// separately, like an x86-64 Box2D build; this is what makes bit-exact parity possible).
+// Build: hipcc with the flags of gym_rem2d_amd/_lib.py BUILD_FLAGS (-Os --offload-arch=gfx950 -ffp-contract=off
+// -fno-slp-vectorize ...: every binary32 operation rounded separately, like an x86-64 Box2D build; this is what makes bit-exact
+// parity possible).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -110,6 +111,68 @@ static int fail(int code, const std::string &msg) {
         if (e_ != hipSuccess) return fail(REM2D_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// Pairs of timing events: made by rem2d_world_enable_timing (outside any timed region), recorded by the step calls, read back by
+// rem2d_world_kernel_time_ms / rem2d_world_step_time_ms.  Launches beyond the pool go untimed.
+typedef std::pair<hipEvent_t, hipEvent_t> EventPair;
+struct EventPool {
+    std::vector<EventPair> pairs;
+    std::vector<int> weight; // what pair i adds to `count` once read (a step train's step bracket holds a whole launch of env-steps)
+    int used = 0;
+    double ms = 0.0; // read back and not yet reported
+    int64_t count = 0;
+    int fill(size_t want) {
+        while (pairs.size() < want) {
+            hipEvent_t a = nullptr, b = nullptr;
+            HIP_TRY(hipEventCreate(&a));
+            hipError_t e = hipEventCreate(&b);
+            if (e != hipSuccess) {
+                (void)hipEventDestroy(a);
+                return fail(REM2D_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+            }
+            pairs.emplace_back(a, b);
+        }
+        weight.resize(pairs.size(), 1);
+        return REM2D_OK;
+    }
+    // the next free pair (counted as used, weight 1) for a launch that records it itself, or nullptr
+    const EventPair *take(bool on) {
+        if (!on || used >= (int)pairs.size()) return nullptr;
+        weight[(size_t)used] = 1;
+        return &pairs[(size_t)used++];
+    }
+    // a bracket of stream events around what is queued between open and close; false: nothing opened, do not close
+    bool open(bool on, hipStream_t st) { return on && used < (int)pairs.size() && hipEventRecord(pairs[(size_t)used].first, st) == hipSuccess; }
+    void close(hipStream_t st, int w) {
+        (void)hipEventRecord(pairs[(size_t)used].second, st);
+        weight[(size_t)used] = w;
+        used += 1;
+    }
+    void drain() { // (the device has been drained: every recorded pair is complete)
+        for (int i = 0; i < used; ++i) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, pairs[(size_t)i].first, pairs[(size_t)i].second) == hipSuccess) {
+                ms += t;
+                count += weight[(size_t)i];
+            }
+        }
+        used = 0;
+    }
+    void report(double *total_ms, int64_t *n) {
+        if (total_ms) *total_ms = ms;
+        if (n) *n = count;
+        ms = 0.0;
+        count = 0;
+    }
+    void free() {
+        for (auto &p : pairs) {
+            (void)hipEventDestroy(p.first);
+            (void)hipEventDestroy(p.second);
+        }
+        pairs.clear();
+        used = 0;
+    }
+};
+
 struct rem2d_world {
     rem2d_world_cfg cfg;
     Layout L;
@@ -119,28 +182,18 @@ struct rem2d_world {
     float *terrainBuf;
     int *tilesDev; // [nTiles + 1] creature index where each tile of rem2d_vel4_kernel starts
     int nTiles;
+    int tileShape; // REM2D_TILE_SHAPE id of rem2d_vel4_kernel for this world's tiles
     bool haveTerrain, haveReset;
     bool timing;
-    double accumMs;
-    int64_t launches;
-    // event pairs around the dominant kernel of each launch; created by rem2d_world_enable_timing (outside any timed
-    // region), recorded by the step calls, read back by rem2d_world_kernel_time_ms
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> evPool;
-    int evUsed;
-    // second bracket: all kernels of one env-step (pre .. toi_heavy) of the tile pipeline
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> evPoolStep;
-    int tileShape; // REM2D_TILE_SHAPE id of rem2d_vel4_kernel for this world's tiles
-    int evUsedStep;
-    double accumMsStep;
-    int64_t launchesStep;
+    EventPool evKernel; // around the dominant kernel of each launch; count = launches
+    EventPool evStep;   // around all kernels of an env-step (re-ordering .. toi_heavy) of the tile pipeline, or of a train launch; count = env-steps
     hipEvent_t evFork, evJoin; // fork / join edges of rem2d_groups_step (created on first use)
     uint64_t epoch;            // bumped whenever something the kernel arguments embed changes (graph replay key)
     int32_t opt[REM2D_OPT_COUNT]; // launch options (rem2d_world_set_option); results never depend on them
     int64_t stepsQueued;          // env-steps queued so far (the cadence of REM2D_OPT_REBALANCE)
     int64_t stepsAtOrder;         // ... at the step train's last re-ordering launch
-    unsigned *trainFlags; size_t trainCap; // rem2d_step_train_kernel's hand-over flags (device; grown on demand, as the first world of a launch)
+    unsigned *trainFlags; size_t trainCap; // the step train's hand-over flags (device; grown on demand, as the first world of a launch)
     unsigned *trainFailures;      // pinned host word: hand-overs of this world's trains that failed (rem2d_world_handover_failures)
-    std::vector<int> evStepCount; // env-steps inside each bracket of evPoolStep (a step train's bracket holds a whole launch)
     bool hostOrder;               // rem2d_world_set_order installed an order (REM2D_STATE_ORDERED = hostOrder || REBALANCE > 0)
 };
 // the kernels go through State::order while the host has installed an order OR the library re-makes one every N steps
@@ -156,24 +209,59 @@ static void order_flag_update(rem2d_world *w) {
 //   4: 128 bodies, 2 + 1 sets, 3 waves/SIMD with the static phase -> set map of rounds 2-3: what fixed-morphology populations
 //      want (every creature the same schedule: nothing to rotate, and the 8-module chains are 5 % faster with it, 186 vs 176 M)
 // Shapes 1-3 place joints flexibly (rem2d_vel4.h FLEX): any tile within 64 joints per set IN ALL fits.
-struct TileShape { int sets, passes, csets, flex; };
+#ifndef REM2D_SHAPE1_WPS
+#define REM2D_SHAPE1_WPS 4 // wavefronts per SIMD the 128-body tile shape is compiled for
+#endif
+#ifndef REM2D_SHAPE4_WPS
+#define REM2D_SHAPE4_WPS 3 // the same for the static 128-body shape of the fixed-morphology populations (4: 128 VGPRs, 3 spilled; 65 536 8-module chains 164 instead of 185 M)
+#endif
+#ifndef REM2D_SHAPE1_PAIR
+#define REM2D_SHAPE1_PAIR false // (lane-pair contact solves: a 128-body tile's manifolds rarely fit 32 lanes; without them 3 VGPR spills instead of 7, +2.7 % at 393 216 creatures)
+#endif
+typedef void (*PreKernel)(Batch, StepArgs);
+typedef void (*Vel4Kernel)(Vel4Batch, Vel4Args);
+typedef void (*TrainKernel)(Batch, StepArgs, Vel4Args, unsigned *, unsigned, int, unsigned *);
+// The instantiations, named once -- in the order the launch code has always first named them, which is their order inside the code
+// object (pre 4 3, velocity tiles 0 1 2 4 3, trains 4 1): the table below may list them by shape id without moving a kernel.
+static constexpr PreKernel kPre4 = rem2d_pre_multi_kernel<4>, kPre3 = rem2d_pre_multi_kernel<3>;
+static constexpr Vel4Kernel kVel0 = rem2d_vel4_kernel<4, 4, 2, 2, false>, kVel1 = rem2d_vel4_kernel<2, 2, 1, REM2D_SHAPE1_WPS, REM2D_SHAPE1_PAIR>,
+                            kVel2 = rem2d_vel4_kernel<3, 3, 1, 3, true>, kVel4 = rem2d_vel4_kernel<2, 2, 1, REM2D_SHAPE4_WPS, false, false>,
+                            kVel3 = rem2d_vel4_kernel<1, 1, 1, 4, true>;
+static constexpr TrainKernel kTrain4 = rem2d_step_train128_kernel<false, REM2D_SHAPE4_WPS>, kTrain1 = rem2d_step_train128_kernel<true, REM2D_SHAPE1_WPS>;
+// One row per shape: all that planning and launching know about it.  A new shape is a row here (and its instantiations above).
+struct TileShape {
+    int sets, passes, csets, flex;
+    // which kernel runs a merged launch of worlds planned for different shapes: the highest rank, whose kernel takes every world's
+    // tiles (a tile planned under the static phase -> set map fits a flexible kernel of the same size, not the other way round)
+    int rank;
+    Vel4Kernel vel4;   // the velocity tiles
+    PreKernel pre;     // pre beside them, compiled for the same wavefronts per SIMD (4, or 3: rem2d_pipeline.h)
+    TrainKernel train; // all steps of a call in one launch for tiles of this shape (REM2D_OPT_FUSE_VELPOST = 2), or nullptr
+};
 #define REM2D_TILE_SHAPES 5
 #define DEFAULT_TILE_SHAPE 3
-static TileShape tile_shape(int id) {
-    static const TileShape shapes[REM2D_TILE_SHAPES] = {{4, 4, 2, 0}, {2, 2, 1, 1}, {3, 3, 1, 1}, {1, 1, 1, 1}, {2, 2, 1, 0}};
-    return shapes[(id >= 0 && id < REM2D_TILE_SHAPES) ? id : 3];
-}
+static const TileShape kTileShapes[REM2D_TILE_SHAPES] = {
+    {4, 4, 2, 0, 4, kVel0, kPre3, nullptr},
+    {2, 2, 1, 1, 2, kVel1, REM2D_SHAPE1_WPS >= 4 ? kPre4 : kPre3, kTrain1},
+    {3, 3, 1, 1, 3, kVel2, kPre3, nullptr},
+    {1, 1, 1, 1, 0, kVel3, kPre4, rem2d_step_train_kernel},
+    {2, 2, 1, 0, 1, kVel4, kPre3, kTrain4},
+};
 static bool tile_shape_ok(int id) { return id >= 0 && id < REM2D_TILE_SHAPES; }
-// which kernel runs a merged launch of worlds planned for different shapes: the one that takes every world's tiles (a tile
-// planned under the static phase -> set map fits a flexible kernel of the same size, not the other way round)
-static int tile_shape_rank(int id) { return id == 3 ? 0 : (id == 4 ? 1 : (id == 1 ? 2 : (id == 2 ? 3 : 4))); }
-// creatures per tile of the default plan (valid for every morphology of `lanes` lanes per creature)
-static int default_tile_creatures(const TileShape &shp, int lanes) {
+static const TileShape &tile_shape(int id) { return kTileShapes[tile_shape_ok(id) ? id : DEFAULT_TILE_SHAPE]; }
+// the default plan as a tile table: valid for every morphology of the world's lanes per creature
+static std::vector<int32_t> default_tiles(const rem2d_world *w) {
+    const TileShape &shp = tile_shape(w->tileShape);
+    const int lanes = w->cfg.lanes;
     // flexible shapes: a creature has fewer joints than lanes, so passes * 64 lanes never exceed sets * 64 joints (passes <= sets);
     // four sets = one phase per set: 128 / lanes creatures never have more than 64 joints in a phase
     int per = (shp.flex ? shp.passes * WAVE : (shp.sets >= 4 ? 128 : 64)) / lanes;
     if (per * lanes > shp.passes * WAVE) per = shp.passes * WAVE / lanes;
-    return per < 1 ? 1 : per;
+    if (per < 1) per = 1;
+    std::vector<int32_t> ts;
+    for (int c = 0; c < w->L.Np; c += per) ts.push_back(c);
+    ts.push_back(w->L.Np);
+    return ts;
 }
 // Launch options of a world (include/rem2d.h REM2D_OPT_*): defaults and valid ranges.  None of them changes a result; the
 // library reads no environment variable -- hosts that want overrides for experiments pass them here (gym_rem2d_amd._lib
@@ -277,12 +365,6 @@ extern "C" int rem2d_world_create(const rem2d_world_cfg *cfg, void *state_dev, s
     w->terrainBuf = nullptr;
     w->haveTerrain = w->haveReset = false;
     w->timing = false;
-    w->evUsed = 0;
-    w->evUsedStep = 0;
-    w->accumMsStep = 0.0;
-    w->launchesStep = 0;
-    w->accumMs = 0.0;
-    w->launches = 0;
     w->evFork = w->evJoin = nullptr;
     w->epoch = next_epoch();
     for (int k = 0; k < REM2D_OPT_COUNT; ++k) w->opt[k] = kOptDefault[k];
@@ -325,10 +407,7 @@ extern "C" int rem2d_world_create(const rem2d_world_cfg *cfg, void *state_dev, s
     // rem2d_world_set_tiles lets the host pack tiles tighter from the actual morphologies.
     {
         w->tileShape = DEFAULT_TILE_SHAPE;
-        const int per = default_tile_creatures(tile_shape(w->tileShape), cfg->lanes);
-        std::vector<int32_t> ts;
-        for (int c = 0; c < L.Np; c += per) ts.push_back(c);
-        ts.push_back(L.Np);
+        const std::vector<int32_t> ts = default_tiles(w);
         w->tilesDev = nullptr;
         w->nTiles = 0;
         int rc = rem2d_world_set_tiles(w, ts.data(), (int32_t)ts.size() - 1);
@@ -367,10 +446,7 @@ extern "C" int rem2d_world_set_tile_shape(rem2d_world *w, int32_t tile_shape_sel
     if (w->tileShape == tile_shape_sel) return REM2D_OK;
     w->tileShape = tile_shape_sel;
     // the tile table in place may not fit the new shape: back to the default plan, valid for every morphology
-    const int per = default_tile_creatures(tile_shape(w->tileShape), w->cfg.lanes);
-    std::vector<int32_t> ts;
-    for (int c = 0; c < w->L.Np; c += per) ts.push_back(c);
-    ts.push_back(w->L.Np);
+    const std::vector<int32_t> ts = default_tiles(w);
     return rem2d_world_set_tiles(w, ts.data(), (int32_t)ts.size() - 1);
 }
 
@@ -469,7 +545,7 @@ extern "C" int rem2d_plan_tiles_shape(const int32_t *parent, const int32_t *jrou
     if (!parent || !jround || !tile_start_out || !n_tiles_out) return fail(REM2D_E_INVALID, "plan_tiles: NULL argument");
     if (tile_shape_sel != -1 && !tile_shape_ok(tile_shape_sel))
         return fail(REM2D_E_INVALID, "plan_tiles: tile shape must be 0 .. 4 or -1 (the default, 3)");
-    const TileShape sh = tile_shape(tile_shape_sel < 0 ? DEFAULT_TILE_SHAPE : tile_shape_sel);
+    const TileShape &sh = tile_shape(tile_shape_sel < 0 ? DEFAULT_TILE_SHAPE : tile_shape_sel);
     const int maxLanes = sh.passes * WAVE;
     if (n_envs <= 0 || n_padded < n_envs || lanes <= 0 || lanes > maxLanes) return fail(REM2D_E_INVALID, "plan_tiles: bad shape");
     if (max_creatures <= 0) {
@@ -543,45 +619,10 @@ extern "C" int rem2d_plan_tiles_shape(const int32_t *parent, const int32_t *jrou
 static void drain_timing(rem2d_world *w) {
     // the device is drained once; after that every recorded pair is complete.  (No hipEventSynchronize per event: the
     // start / stop events of hipExtLaunchKernelGGL are not stream records, and waiting on one can block for ever.)
-    if (w->evUsed > 0 || w->evUsedStep > 0) (void)hipDeviceSynchronize();
-    for (int i = 0; i < w->evUsed; ++i) {
-        auto &p = w->evPool[i];
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) {
-            w->accumMs += ms;
-            w->launches += 1;
-        }
-    }
-    w->evUsed = 0;
-    for (int i = 0; i < w->evUsedStep; ++i) {
-        auto &p = w->evPoolStep[i];
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) {
-            w->accumMsStep += ms;
-            w->launchesStep += (size_t)i < w->evStepCount.size() ? w->evStepCount[(size_t)i] : 1;
-        }
-    }
-    w->evUsedStep = 0;
+    if (w->evKernel.used > 0 || w->evStep.used > 0) (void)hipDeviceSynchronize();
+    w->evKernel.drain();
+    w->evStep.drain();
     (void)hipGetLastError(); // an event pair that was never reached leaves hipErrorInvalidHandle / NotReady behind
-}
-static void free_timing(rem2d_world *w) {
-    for (auto *pool : {&w->evPool, &w->evPoolStep}) {
-        for (auto &p : *pool) {
-            (void)hipEventDestroy(p.first);
-            (void)hipEventDestroy(p.second);
-        }
-        pool->clear();
-    }
-    w->evUsed = w->evUsedStep = 0;
-}
-// first event of the next free pair, or nullptr when timing is off / the pool is used up (those launches go untimed)
-static bool timing_begin(rem2d_world *w, hipStream_t st) {
-    if (!w->timing || w->evUsed >= (int)w->evPool.size()) return false;
-    return hipEventRecord(w->evPool[w->evUsed].first, st) == hipSuccess;
-}
-static void timing_end(rem2d_world *w, hipStream_t st) {
-    (void)hipEventRecord(w->evPool[w->evUsed].second, st);
-    w->evUsed += 1;
 }
 
 static void graphs_forget(const rem2d_world *w); // (the hipGraph replays of rem2d_groups_step, below)
@@ -589,7 +630,8 @@ extern "C" int rem2d_world_destroy(rem2d_world *w) {
     if (!w) return REM2D_OK;
     (void)hipSetDevice(w->cfg.device);
     graphs_forget(w);
-    free_timing(w);
+    w->evKernel.free();
+    w->evStep.free();
     if (w->evFork) (void)hipEventDestroy(w->evFork);
     if (w->evJoin) (void)hipEventDestroy(w->evJoin);
     if (w->S.scr) (void)hipFree(w->S.scr);
@@ -734,19 +776,75 @@ extern "C" int rem2d_world_reset(rem2d_world *w, const rem2d_morph *m, void *str
 }
 
 static int pipeline_mode(const rem2d_world *w) { return w->opt[REM2D_OPT_PIPELINE] == 0 ? 0 : 3; }
-// Worlds of one merged launch run in ONE kernel shape (tiles_plan: the highest tile_shape_rank).  Every mix is sound but one: a
-// tile planned for shape 2 (192 bodies, <= 192 joints IN ALL, flexibly placed) may hold more than 64 joints in one schedule
-// phase, which the static four-set kernel of shape 0 (one phase per register set) cannot take -- that launch would drop joints.
+// Worlds of one merged launch run in ONE kernel shape: the highest TileShape::rank among theirs.
+static int launch_shape(rem2d_world *const *ws, int n_worlds) {
+    int id = DEFAULT_TILE_SHAPE;
+    for (int i = 0; i < n_worlds; ++i)
+        if (tile_shape(ws[i]->tileShape).rank > tile_shape(id).rank) id = ws[i]->tileShape;
+    return id;
+}
+// Every mix is sound but one kind: a flexibly placed tile of more than two passes (shape 2: 192 bodies, <= 192 joints IN ALL) may hold
+// more than 64 joints in one schedule phase -- a phase is a matching, up to 32 joints per pass --, which a static kernel (shape 0: one
+// phase per register set) cannot take: that launch would drop joints.
 static bool shapes_mix_ok(rem2d_world *const *ws, int n_worlds) {
-    bool has0 = false, has2 = false;
+    const TileShape &run = tile_shape(launch_shape(ws, n_worlds));
     for (int i = 0; i < n_worlds; ++i) {
-        has0 = has0 || ws[i]->tileShape == 0;
-        has2 = has2 || ws[i]->tileShape == 2;
+        const TileShape &planned = tile_shape(ws[i]->tileShape);
+        if (!run.flex && planned.flex && planned.passes > 2) return false;
     }
-    return !(has0 && has2);
+    return true;
 }
 #define SHAPES_TRY(ws, n) \
     do { if (!shapes_mix_ok((ws), (n))) return fail(REM2D_E_INVALID, "worlds of tile shapes 0 and 2 cannot share a launch (step them in separate calls / groups)"); } while (0)
+
+// The worlds of one launch (a step call, one step group): a list of 1 .. REM2D_MAX_BATCH worlds on the device of `same_device`
+// (nullptr: of the first) that agree on REM2D_FLAG_CONTINUOUS and have their terrain and their creatures; !to_step: a list of worlds.
+static int worlds_ok(rem2d_world *const *ws, int n_worlds, const rem2d_world *same_device, bool to_step) {
+    if (!ws || n_worlds <= 0) return fail(REM2D_E_INVALID, "no worlds");
+    static_assert(REM2D_MAX_WORLDS_PER_STEP == REM2D_MAX_BATCH, "batch size");
+    if (n_worlds > REM2D_MAX_BATCH) return fail(REM2D_E_INVALID, "too many worlds for one launch");
+    for (int i = 0; i < n_worlds; ++i) {
+        const rem2d_world *w = ws[i];
+        if (!w) return fail(REM2D_E_INVALID, "world is NULL");
+        if (!to_step) continue; // (rem2d_worlds_launch_info answers for any list of worlds)
+        if (!w->haveTerrain) return fail(REM2D_E_STATE, "rem2d_world_set_terrain must be called before step");
+        if (!w->haveReset) return fail(REM2D_E_STATE, "rem2d_world_reset must be called before step");
+        if (w->cfg.device != (same_device ? same_device : ws[0])->cfg.device) return fail(REM2D_E_INVALID, "worlds of one call must share the device");
+        if ((w->cfg.flags & REM2D_FLAG_CONTINUOUS) != (ws[0]->cfg.flags & REM2D_FLAG_CONTINUOUS))
+            return fail(REM2D_E_INVALID, "worlds of one launch must agree on REM2D_FLAG_CONTINUOUS");
+    }
+    return REM2D_OK;
+}
+
+// Kernel, grid, block, stream, arguments: the one way a step kernel is launched.  With an event pair the kernel gets its own begin /
+// end timestamps (hipExtLaunchKernelGGL's start / stop events bracket exactly the kernel, which is what rocprofv3 --kernel-trace
+// reports; events recorded on the stream around the launch also count the dispatch gaps).
+template <typename... Params, typename... Args>
+static void launch(void (*kernel)(Params...), dim3 grid, dim3 block, hipStream_t st, const EventPair *timed, const Args &...args) {
+    if (timed) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, timed->first, timed->second, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+}
+// the worlds' Batch in the order given; returns the 64-lane blocks
+static unsigned batch_fill(Batch &B, rem2d_world *const *ws, const int *order, int n_worlds) {
+    memset(&B, 0, sizeof(B));
+    unsigned blocks = 0;
+    for (int i = 0; i < n_worlds; ++i) {
+        const rem2d_world *w = ws[order ? order[i] : i];
+        B.S[i] = w->S;
+        B.T[i] = w->T;
+        B.lanes[i] = w->cfg.lanes;
+        blocks += (unsigned)w->L.Lp / WAVE;
+        B.blockEnd[i] = blocks;
+    }
+    B.n = n_worlds;
+    return blocks;
+}
+// REM2D_OPT_REBALANCE: a new creature order, made from the last step's state (the callers know when one is due)
+static void launch_rebalance(rem2d_world *w, hipStream_t st, int pos_iters) {
+    int threads = WAVE;
+    while (threads < REBALANCE_MAX_THREADS && threads * 256 < w->cfg.n_envs) threads *= 2;
+    hipLaunchKernelGGL(rem2d_rebalance_kernel, dim3(1), dim3(threads), 0, st, w->S, pos_iters);
+}
 
 // The tile pipeline for one or several worlds (lane buckets) in one grid per kernel: pre and post run one body per
 // lane; the velocity iterations run one tile per wavefront (rem2d_vel4.h).  TilePlan = the launch arguments of one env-step of
@@ -760,19 +858,17 @@ struct TilePlan {
     int launchShape;
     bool continuous;
     bool velpost; // one launch for the velocity iterations and post (rem2d_velpost_kernel)
-    bool train;   // ... and ONE launch for all steps of a call, pre and the TOI solve included (rem2d_step_train_kernel; REM2D_OPT_FUSE_VELPOST = 2)
-    bool train128; // ... the same for the 128-lane tile shapes 1 / 4 (rem2d_step_train128_kernel: an item = a tile's one or two blocks)
+    bool train;   // ... and ONE launch for all steps of a call, pre and the TOI solve included (TileShape::train; REM2D_OPT_FUSE_VELPOST = 2)
+    bool train128; // ... of the 128-lane tile shapes 1 / 4 (rem2d_step_train128_kernel: an item = a tile's one or two blocks)
     unsigned items; // items per step of that launch: blocks (64-lane train) / tile-sized groups of blocks summed over the worlds (128-lane)
+    size_t flagWords; // ... and the hand-over flag words it needs
     rem2d_world *w0;
     rem2d_world *ws[REM2D_MAX_BATCH]; // the group's worlds (REM2D_OPT_REBALANCE runs per world)
     int nw;
 };
 static void tiles_plan(TilePlan &P, rem2d_world *const *ws, int n_worlds, float dt, int vel_iters, int pos_iters) {
-    Batch &B = P.B;
     Vel4Batch &VB = P.VB;
-    memset(&B, 0, sizeof(B));
     memset(&VB, 0, sizeof(VB));
-    unsigned blocks = 0, tiles = 0;
     // tiles of the widest creatures first: their chains are the longest (period 3-4, more joint rounds), so they must
     // not start last
     int order[REM2D_MAX_BATCH];
@@ -781,20 +877,17 @@ static void tiles_plan(TilePlan &P, rem2d_world *const *ws, int n_worlds, float 
         for (int j = i; j > 0 && ws[order[j]]->cfg.lanes > ws[order[j - 1]]->cfg.lanes; --j) {
             const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t;
         }
+    const unsigned blocks = batch_fill(P.B, ws, order, n_worlds);
+    unsigned tiles = 0;
     for (int i = 0; i < n_worlds; ++i) {
-        rem2d_world *w = ws[order[i]];
-        B.S[i] = w->S;
-        B.T[i] = w->T;
-        B.lanes[i] = w->cfg.lanes;
-        blocks += (unsigned)w->L.Lp / WAVE;
-        B.blockEnd[i] = blocks;
+        const rem2d_world *w = ws[order[i]];
         VB.S[i] = w->S;
         VB.friction[i] = w->T.friction;
         VB.lanes[i] = w->cfg.lanes;
         tiles += (unsigned)w->nTiles;
         VB.tileEnd[i] = tiles;
     }
-    B.n = VB.n = n_worlds;
+    VB.n = n_worlds;
     P.blocks = blocks;
     P.tiles = tiles;
     P.w0 = ws[0];
@@ -802,11 +895,7 @@ static void tiles_plan(TilePlan &P, rem2d_world *const *ws, int n_worlds, float 
     for (int i = 0; i < n_worlds; ++i) P.ws[i] = ws[i];
     // worlds planned for different tile shapes in one grid: the largest shape runs the smaller ones' tiles as well
     // (a tile within 64 joints fits any shape; one within 64 joints per phase pair fits the four-set shape)
-    P.launchShape = 3;
-    for (int i = 0; i < n_worlds; ++i) {
-        const int id = ws[i]->tileShape;
-        if (tile_shape_rank(id) > tile_shape_rank(P.launchShape)) P.launchShape = id;
-    }
+    P.launchShape = launch_shape(ws, n_worlds);
     P.velpost = ws[0]->opt[REM2D_OPT_FUSE_VELPOST] != 0 && P.launchShape == 3;
     for (int i = 0; i < n_worlds; ++i) // (a tile within a block: cap <= the creatures of a block)
         P.velpost = P.velpost && ws[i]->S.tileCap > 0 && ws[i]->S.tileCap * ws[i]->cfg.lanes <= WAVE && ws[i]->tileShape == 3; // (REM2D_FLAG_RETILE: tile slots and block slots go through the same creature order)
@@ -834,6 +923,7 @@ static void tiles_plan(TilePlan &P, rem2d_world *const *ws, int n_worlds, float 
         if (P.train128) P.items = items;
     }
     P.train = P.train || P.train128;
+    P.flagWords = TRAIN_FLAG_WORDS + (size_t)P.items;
     P.continuous = (ws[0]->cfg.flags & REM2D_FLAG_CONTINUOUS) != 0;
     P.A.nSteps = 1;
     P.A.dt = dt;
@@ -851,84 +941,37 @@ static void tiles_plan(TilePlan &P, rem2d_world *const *ws, int n_worlds, float 
 }
 // one env-step of one step group.  With timing on (rem2d_world_enable_timing; never inside a region whose wall time is
 // being measured -- bench.py times kernels in a pass of its own) the dominant kernel gets its own begin / end timestamps
-// (hipExtLaunchKernelGGL's start / stop events bracket exactly the kernel, which is what rocprofv3 --kernel-trace
-// reports; events recorded on the stream around the launch also count the dispatch gaps) and the whole sequence a pair
-// of stream events.
-#ifndef REM2D_SHAPE1_WPS
-#define REM2D_SHAPE1_WPS 4 // wavefronts per SIMD the 128-body tile shape is compiled for
-#endif
-#ifndef REM2D_SHAPE4_WPS
-#define REM2D_SHAPE4_WPS 3 // the same for the static 128-body shape of the fixed-morphology populations (4: 128 VGPRs, 3 spilled; 65 536 8-module chains 164 instead of 185 M)
-#endif
-#ifndef REM2D_SHAPE1_PAIR
-#define REM2D_SHAPE1_PAIR false // (lane-pair contact solves: a 128-body tile's manifolds rarely fit 32 lanes; without them 3 VGPR spills instead of 7, +2.7 % at 393 216 creatures)
-#endif
+// (launch) and the whole sequence a pair of stream events.
 static void tiles_launch_step(const TilePlan &P, hipStream_t st) {
     rem2d_world *w0 = P.w0;
+    const TileShape &shape = tile_shape(P.launchShape); // (a merged launch of shapes 1 and 4: rank picks 1, whose flexible kernel takes the statically planned tiles too)
     const dim3 grid(P.blocks), block(WAVE);
     // (the step's time bracket opens in front of the re-ordering launches: they belong to the step that needs them)
-    const bool timedStep = w0->timing && w0->evUsedStep < (int)w0->evPoolStep.size() &&
-                           hipEventRecord(w0->evPoolStep[w0->evUsedStep].first, st) == hipSuccess;
-    for (int i = 0; i < P.nw; ++i) { // REM2D_OPT_REBALANCE: a new creature order every N env-steps, made from the last step's state
+    const bool timedStep = w0->evStep.open(w0->timing, st);
+    for (int i = 0; i < P.nw; ++i) { // REM2D_OPT_REBALANCE: a new creature order every N env-steps
         rem2d_world *w = P.ws[i];
         const int every = w->opt[REM2D_OPT_REBALANCE];
-        if (every > 0 && w->stepsQueued > 0 && w->stepsQueued % every == 0 && (w->S.flags & REM2D_STATE_ORDERED))
-        {
-            int threads = WAVE;
-            while (threads < REBALANCE_MAX_THREADS && threads * 256 < w->cfg.n_envs) threads *= 2;
-            hipLaunchKernelGGL(rem2d_rebalance_kernel, dim3(1), dim3(threads), 0, st, w->S, P.A.posIters);
-        }
+        if (every > 0 && w->stepsQueued > 0 && w->stepsQueued % every == 0 && (w->S.flags & REM2D_STATE_ORDERED)) launch_rebalance(w, st, P.A.posIters);
         w->stepsQueued += 1;
     }
-    // (a merged launch of shapes 1 and 4: rank picks 1, whose flexible kernel takes the statically planned tiles too)
-    if (P.launchShape == 3 || (P.launchShape == 1 && REM2D_SHAPE1_WPS >= 4)) hipLaunchKernelGGL(rem2d_pre_multi_kernel<4>, grid, block, 0, st, P.B, P.A);
-    else hipLaunchKernelGGL(rem2d_pre_multi_kernel<3>, grid, block, 0, st, P.B, P.A);
-    const bool timed = w0->timing && w0->evUsed < (int)w0->evPool.size();
+    launch(shape.pre, grid, block, st, nullptr, P.B, P.A);
+    const EventPair *timed = w0->evKernel.take(w0->timing);
     if (P.velpost) {
-        if (timed) {
-            hipExtLaunchKernelGGL(rem2d_velpost_kernel, grid, dim3(WAVE * REM2D_VELPOST_WAVES), 0, st, w0->evPool[w0->evUsed].first,
-                                  w0->evPool[w0->evUsed].second, 0, P.B, P.A, P.V);
-            w0->evUsed += 1;
-        } else {
-            hipLaunchKernelGGL(rem2d_velpost_kernel, grid, dim3(WAVE * REM2D_VELPOST_WAVES), 0, st, P.B, P.A, P.V);
-        }
+        launch(rem2d_velpost_kernel, grid, dim3(WAVE * REM2D_VELPOST_WAVES), st, timed, P.B, P.A, P.V);
     } else {
-        if (timed) {
-            hipEvent_t e0 = w0->evPool[w0->evUsed].first, e1 = w0->evPool[w0->evUsed].second;
-            switch (P.launchShape) {
-            case 0: hipExtLaunchKernelGGL((rem2d_vel4_kernel<4, 4, 2, 2, false>), dim3(P.tiles), block, 0, st, e0, e1, 0, P.VB, P.V); break;
-            case 1: hipExtLaunchKernelGGL((rem2d_vel4_kernel<2, 2, 1, REM2D_SHAPE1_WPS, REM2D_SHAPE1_PAIR>), dim3(P.tiles), block, 0, st, e0, e1, 0, P.VB, P.V); break;
-            case 2: hipExtLaunchKernelGGL((rem2d_vel4_kernel<3, 3, 1, 3, true>), dim3(P.tiles), block, 0, st, e0, e1, 0, P.VB, P.V); break;
-            case 4: hipExtLaunchKernelGGL((rem2d_vel4_kernel<2, 2, 1, REM2D_SHAPE4_WPS, false, false>), dim3(P.tiles), block, 0, st, e0, e1, 0, P.VB, P.V); break;
-            default: hipExtLaunchKernelGGL((rem2d_vel4_kernel<1, 1, 1, 4, true>), dim3(P.tiles), block, 0, st, e0, e1, 0, P.VB, P.V); break;
-            }
-            w0->evUsed += 1;
-        } else {
-            switch (P.launchShape) {
-            case 0: hipLaunchKernelGGL((rem2d_vel4_kernel<4, 4, 2, 2, false>), dim3(P.tiles), block, 0, st, P.VB, P.V); break;
-            case 1: hipLaunchKernelGGL((rem2d_vel4_kernel<2, 2, 1, REM2D_SHAPE1_WPS, REM2D_SHAPE1_PAIR>), dim3(P.tiles), block, 0, st, P.VB, P.V); break;
-            case 2: hipLaunchKernelGGL((rem2d_vel4_kernel<3, 3, 1, 3, true>), dim3(P.tiles), block, 0, st, P.VB, P.V); break;
-            case 4: hipLaunchKernelGGL((rem2d_vel4_kernel<2, 2, 1, REM2D_SHAPE4_WPS, false, false>), dim3(P.tiles), block, 0, st, P.VB, P.V); break;
-            default: hipLaunchKernelGGL((rem2d_vel4_kernel<1, 1, 1, 4, true>), dim3(P.tiles), block, 0, st, P.VB, P.V); break;
-            }
-        }
-        hipLaunchKernelGGL(rem2d_post_multi_kernel, grid, block, 0, st, P.B, P.A);
+        launch(shape.vel4, dim3(P.tiles), block, st, timed, P.VB, P.V);
+        launch(rem2d_post_multi_kernel, grid, block, st, nullptr, P.B, P.A);
     }
-    if (P.continuous) hipLaunchKernelGGL(rem2d_toi_heavy_multi_kernel, grid, block, 0, st, P.B, P.A);
-    if (timedStep) {
-        (void)hipEventRecord(w0->evPoolStep[w0->evUsedStep].second, st);
-        if (w0->evStepCount.size() < w0->evPoolStep.size()) w0->evStepCount.resize(w0->evPoolStep.size(), 1);
-        w0->evStepCount[(size_t)w0->evUsedStep] = 1;
-        w0->evUsedStep += 1;
-    }
+    if (P.continuous) launch(rem2d_toi_heavy_multi_kernel, grid, block, st, nullptr, P.B, P.A);
+    if (timedStep) w0->evStep.close(st, 1);
 }
-// The step train (rem2d_step_train_kernel): the steps of a call in one launch -- or in one launch per stretch between two
+// The step train (TileShape::train): the steps of a call in one launch -- or in one launch per stretch between two
 // re-orderings of the creature order (REM2D_OPT_REBALANCE), which run in front of the stretch they are due for.
 // (the flag buffer and the failure counter of a train's first world: sized before anything of the launch is queued -- growing frees
 // the old buffer, which waits for the launches that use it)
-static int train_reserve(TilePlan &P) {
+static int train_reserve(const TilePlan &P) {
     rem2d_world *w0 = P.w0;
-    const size_t need = TRAIN_FLAG_WORDS + (size_t)P.items;
+    const size_t need = P.flagWords;
     if (w0->trainCap < need) {
         if (w0->trainFlags) HIP_TRY(hipFree(w0->trainFlags));
         w0->trainFlags = nullptr; w0->trainCap = 0;
@@ -943,7 +986,6 @@ static int train_reserve(TilePlan &P) {
 }
 static int tiles_launch_train(TilePlan &P, hipStream_t st, int n_steps) {
     rem2d_world *w0 = P.w0;
-    const size_t need = TRAIN_FLAG_WORDS + (size_t)P.items;
     { int rc = train_reserve(P); if (rc != REM2D_OK) return rc; }
     const unsigned nPad = (P.items + 7u) & ~7u;
     const int fault = w0->opt[REM2D_OPT_TRAIN_FAULT];
@@ -959,40 +1001,21 @@ static int tiles_launch_train(TilePlan &P, hipStream_t st, int n_steps) {
             const int every = P.ws[i]->opt[REM2D_OPT_REBALANCE];
             if (every > 0 && seg > every) seg = every;
         }
-        const bool timedStep = w0->timing && w0->evUsedStep < (int)w0->evPoolStep.size() &&
-                               hipEventRecord(w0->evPoolStep[w0->evUsedStep].first, st) == hipSuccess;
+        const bool timedStep = w0->evStep.open(w0->timing, st);
         for (int i = 0; i < P.nw; ++i) {
             rem2d_world *w = P.ws[i];
             const int every = w->opt[REM2D_OPT_REBALANCE];
             if (every > 0 && w->stepsQueued > 0 && w->stepsQueued - w->stepsAtOrder >= every && (w->S.flags & REM2D_STATE_ORDERED)) {
-                int threads = WAVE;
-                while (threads < REBALANCE_MAX_THREADS && threads * 256 < w->cfg.n_envs) threads *= 2;
-                hipLaunchKernelGGL(rem2d_rebalance_kernel, dim3(1), dim3(threads), 0, st, w->S, P.A.posIters);
+                launch_rebalance(w, st, P.A.posIters);
                 w->stepsAtOrder = w->stepsQueued;
             }
             w->stepsQueued += seg;
         }
-        HIP_TRY(hipMemsetAsync(w0->trainFlags, 0, need * sizeof(unsigned), st));
+        HIP_TRY(hipMemsetAsync(w0->trainFlags, 0, P.flagWords * sizeof(unsigned), st));
         P.A.nSteps = seg;
-        const dim3 grid(nPad * (unsigned)seg), block(WAVE);
-        const bool timed = w0->timing && w0->evUsed < (int)w0->evPool.size();
-        hipEvent_t e0 = timed ? w0->evPool[w0->evUsed].first : nullptr, e1 = timed ? w0->evPool[w0->evUsed].second : nullptr;
-#define TRAIN_LAUNCH(KERNEL)                                                                                                              \
-        do {                                                                                                                              \
-            if (timed) hipExtLaunchKernelGGL(KERNEL, grid, block, 0, st, e0, e1, 0, P.B, P.A, P.V, w0->trainFlags, P.items, fault, w0->trainFailures); \
-            else hipLaunchKernelGGL(KERNEL, grid, block, 0, st, P.B, P.A, P.V, w0->trainFlags, P.items, fault, w0->trainFailures);          \
-        } while (0)
-        if (!P.train128) TRAIN_LAUNCH(rem2d_step_train_kernel);
-        else if (P.launchShape == 4) TRAIN_LAUNCH((rem2d_step_train128_kernel<false, REM2D_SHAPE4_WPS>));
-        else TRAIN_LAUNCH((rem2d_step_train128_kernel<true, REM2D_SHAPE1_WPS>));
-#undef TRAIN_LAUNCH
-        if (timed) w0->evUsed += 1;
-        if (timedStep) {
-            (void)hipEventRecord(w0->evPoolStep[w0->evUsedStep].second, st);
-            if (w0->evStepCount.size() < w0->evPoolStep.size()) w0->evStepCount.resize(w0->evPoolStep.size(), 1);
-            w0->evStepCount[(size_t)w0->evUsedStep] = seg; // (this bracket holds `seg` env-steps)
-            w0->evUsedStep += 1;
-        }
+        launch(tile_shape(P.launchShape).train, dim3(nPad * (unsigned)seg), dim3(WAVE), st, w0->evKernel.take(w0->timing), P.B, P.A, P.V,
+               w0->trainFlags, P.items, fault, w0->trainFailures);
+        if (timedStep) w0->evStep.close(st, seg); // (this bracket holds `seg` env-steps)
         l += seg;
     }
     P.A.nSteps = 1;
@@ -1012,17 +1035,7 @@ static int step_tiles(rem2d_world *const *ws, int n_worlds, int n_steps, float d
 // worlds in one grid per kernel: n_steps env-steps per launch in discrete mode, one per launch when the TOI kernels follow.
 static int step_fused(rem2d_world *const *ws, int n_worlds, int n_steps, float dt, int vel_iters, int pos_iters, hipStream_t st) {
     Batch B;
-    memset(&B, 0, sizeof(B));
-    unsigned blocks = 0;
-    for (int i = 0; i < n_worlds; ++i) {
-        rem2d_world *w = ws[i];
-        B.S[i] = w->S;
-        B.T[i] = w->T;
-        B.lanes[i] = w->cfg.lanes;
-        blocks += (unsigned)w->L.Lp / WAVE;
-        B.blockEnd[i] = blocks;
-    }
-    B.n = n_worlds;
+    const dim3 grid(batch_fill(B, ws, nullptr, n_worlds)), block(WAVE);
     rem2d_world *w0 = ws[0];
     const bool continuous = (w0->cfg.flags & REM2D_FLAG_CONTINUOUS) != 0;
     StepArgs A;
@@ -1033,15 +1046,14 @@ static int step_fused(rem2d_world *const *ws, int n_worlds, int n_steps, float d
     A.heavyPerWave = w0->opt[REM2D_OPT_HEAVY_PER_WAVE];
     A.prio = w0->opt[REM2D_OPT_PRIO];
     A.defer = continuous ? 1 : 0;
-    dim3 grid(blocks), block(WAVE);
     const int launches = continuous ? n_steps : 1;
     for (int l = 0; l < launches; ++l) {
-        const bool timed = timing_begin(w0, st);
-        hipLaunchKernelGGL(rem2d_step_multi_kernel, grid, block, 0, st, B, A);
-        if (timed) timing_end(w0, st);
+        const bool timed = w0->evKernel.open(w0->timing, st); // (stream events around the kernel: the form this path has always reported)
+        launch(rem2d_step_multi_kernel, grid, block, st, nullptr, B, A);
+        if (timed) w0->evKernel.close(st, 1);
         if (continuous) {
-            hipLaunchKernelGGL(rem2d_toi_scan_multi_kernel, grid, block, 0, st, B, A);
-            hipLaunchKernelGGL(rem2d_toi_heavy_multi_kernel, grid, block, 0, st, B, A);
+            launch(rem2d_toi_scan_multi_kernel, grid, block, st, nullptr, B, A);
+            launch(rem2d_toi_heavy_multi_kernel, grid, block, st, nullptr, B, A);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1049,18 +1061,14 @@ static int step_fused(rem2d_world *const *ws, int n_worlds, int n_steps, float d
 }
 
 extern "C" int rem2d_worlds_launch_info(rem2d_world *const *ws, int32_t n_worlds, int32_t *tile_shape_out, int32_t *fused_velpost) {
-    if (!ws || n_worlds <= 0 || n_worlds > REM2D_MAX_BATCH) return fail(REM2D_E_INVALID, "launch_info: bad world list");
-    for (int i = 0; i < n_worlds; ++i)
-        if (!ws[i]) return fail(REM2D_E_INVALID, "world is NULL");
+    { int rc = worlds_ok(ws, n_worlds, nullptr, false); if (rc != REM2D_OK) return rc; }
     if (pipeline_mode(ws[0]) != 3) { // the fused step kernel: no tiles
         if (tile_shape_out) *tile_shape_out = -1;
         if (fused_velpost) *fused_velpost = 0;
         return REM2D_OK;
     }
-    static TilePlan P; // (large: kernel arguments of a whole group)
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
     SHAPES_TRY(ws, n_worlds);
+    TilePlan P;
     tiles_plan(P, ws, n_worlds, 1.0f / 50.0f, 180, 60);
     if (tile_shape_out) *tile_shape_out = P.launchShape;
     if (fused_velpost) *fused_velpost = P.train ? 2 : (P.velpost ? 1 : 0); // (2 with tile shape 1 / 4: rem2d_step_train128_kernel)
@@ -1079,39 +1087,17 @@ static bool iters_ok(int vel_iters, int pos_iters) {
 
 extern "C" int rem2d_world_step_ex(rem2d_world *w, int32_t n_steps, float dt, int32_t vel_iters, int32_t pos_iters,
                                    void *stream) {
-    if (!w) return fail(REM2D_E_INVALID, "world is NULL");
-    ITERS_TRY(vel_iters, pos_iters);
-    if (!w->haveTerrain) return fail(REM2D_E_STATE, "rem2d_world_set_terrain must be called before step");
-    if (!w->haveReset) return fail(REM2D_E_STATE, "rem2d_world_reset must be called before step");
-    if (n_steps <= 0) return REM2D_OK;
-    HIP_TRY(hipSetDevice(w->cfg.device));
-    if (pipeline_mode(w) == 3) return step_tiles(&w, 1, n_steps, dt, vel_iters, pos_iters, (hipStream_t)stream);
-    return step_fused(&w, 1, n_steps, dt, vel_iters, pos_iters, (hipStream_t)stream);
+    return rem2d_worlds_step_ex(&w, 1, n_steps, dt, vel_iters, pos_iters, stream);
 }
 extern "C" int rem2d_worlds_step_ex(rem2d_world *const *ws, int32_t n_worlds, int32_t n_steps, float dt, int32_t vel_iters,
                                     int32_t pos_iters, void *stream) {
-    if (!ws || n_worlds <= 0) return fail(REM2D_E_INVALID, "no worlds");
-    ITERS_TRY(vel_iters, pos_iters);
-    if (n_worlds == 1) return rem2d_world_step_ex(ws[0], n_steps, dt, vel_iters, pos_iters, stream);
-    if (n_worlds > REM2D_MAX_WORLDS_PER_STEP) return fail(REM2D_E_INVALID, "too many worlds for one launch");
-    static_assert(REM2D_MAX_WORLDS_PER_STEP == REM2D_MAX_BATCH, "batch size");
-    for (int i = 0; i < n_worlds; ++i) {
-        rem2d_world *w = ws[i];
-        if (!w) return fail(REM2D_E_INVALID, "world is NULL");
-        if (!w->haveTerrain) return fail(REM2D_E_STATE, "rem2d_world_set_terrain must be called before step");
-        if (!w->haveReset) return fail(REM2D_E_STATE, "rem2d_world_reset must be called before step");
-        if (w->cfg.device != ws[0]->cfg.device) return fail(REM2D_E_INVALID, "worlds of one launch must share the device");
-        if ((w->cfg.flags & REM2D_FLAG_CONTINUOUS) != (ws[0]->cfg.flags & REM2D_FLAG_CONTINUOUS))
-            return fail(REM2D_E_INVALID, "worlds of one launch must agree on REM2D_FLAG_CONTINUOUS");
-    }
+    ITERS_TRY(vel_iters, pos_iters); // (first: what a caller passes for the worlds is not looked at behind bad counts)
+    { int rc = worlds_ok(ws, n_worlds, nullptr, true); if (rc != REM2D_OK) return rc; }
     if (n_steps <= 0) return REM2D_OK;
-    rem2d_world *w0 = ws[0];
-    HIP_TRY(hipSetDevice(w0->cfg.device));
-    if (pipeline_mode(w0) == 3) {
-        SHAPES_TRY(ws, n_worlds);
-        return step_tiles(ws, n_worlds, n_steps, dt, vel_iters, pos_iters, (hipStream_t)stream);
-    }
-    return step_fused(ws, n_worlds, n_steps, dt, vel_iters, pos_iters, (hipStream_t)stream);
+    HIP_TRY(hipSetDevice(ws[0]->cfg.device));
+    if (pipeline_mode(ws[0]) != 3) return step_fused(ws, n_worlds, n_steps, dt, vel_iters, pos_iters, (hipStream_t)stream);
+    SHAPES_TRY(ws, n_worlds);
+    return step_tiles(ws, n_worlds, n_steps, dt, vel_iters, pos_iters, (hipStream_t)stream);
 }
 extern "C" int rem2d_worlds_step(rem2d_world *const *ws, int32_t n_worlds, int32_t n_steps, void *stream) {
     return rem2d_worlds_step_ex(ws, n_worlds, n_steps, (float)(1.0 / 50), 6 * 30, 2 * 30, stream);
@@ -1161,22 +1147,20 @@ static uint64_t mix64(uint64_t h, uint64_t v) {
     return h;
 }
 
-static int groups_enqueue(const rem2d_step_group *groups, int n_groups, int n_steps, float dt, int vel_iters, int pos_iters,
-                          hipStream_t origin, bool tiles) {
+static hipStream_t group_stream(const rem2d_step_group &g, hipStream_t origin) { return g.stream ? (hipStream_t)g.stream : origin; }
+// `plans`: the groups' TilePlans (tiles_plan), or nullptr for the fused kernel
+static int groups_enqueue(const rem2d_step_group *groups, int n_groups, TilePlan *plans, int n_steps, float dt, int vel_iters,
+                          int pos_iters, hipStream_t origin) {
     // (a step train's flag buffer is sized BEFORE the fork: growing it frees the old one, a device-wide wait that does not belong
     // between a fork and its join, and an error here must not leave forked streams behind)
-    std::vector<TilePlan> plans(tiles ? (size_t)n_groups : (size_t)0);
-    if (tiles)
-        for (int g = 0; g < n_groups; ++g) {
-            tiles_plan(plans[g], groups[g].worlds, groups[g].n_worlds, dt, vel_iters, pos_iters);
-            if (plans[g].train) { int rc = train_reserve(plans[g]); if (rc != REM2D_OK) return rc; }
-        }
+    for (int g = 0; plans && g < n_groups; ++g)
+        if (plans[g].train) { int rc = train_reserve(plans[g]); if (rc != REM2D_OK) return rc; }
     // fork: every group stream waits for what the origin stream has queued so far
     rem2d_world *w00 = groups[0].worlds[0];
     bool forked = false;
     int rcAll = REM2D_OK; // (an error after the fork still runs the join: no group stream is left un-joined behind an error return)
     for (int g = 0; g < n_groups; ++g) {
-        hipStream_t sg = groups[g].stream ? (hipStream_t)groups[g].stream : origin;
+        hipStream_t sg = group_stream(groups[g], origin);
         if (sg == origin) continue;
         if (!forked) {
             HIP_TRY(hipEventRecord(w00->evFork, origin));
@@ -1184,26 +1168,25 @@ static int groups_enqueue(const rem2d_step_group *groups, int n_groups, int n_st
         }
         HIP_TRY(hipStreamWaitEvent(sg, w00->evFork, 0));
     }
-    if (tiles) {
+    if (plans) {
         // round-robin: step l of every group is queued before step l + 1 of any, so that no group's stream runs dry while
         // the host is still busy queueing another group's whole train (and the groups start together)
         for (int g = 0; g < n_groups && rcAll == REM2D_OK; ++g) // (a group whose steps go in one launch: queued whole)
-            if (plans[g].train) rcAll = tiles_launch_train(plans[g], groups[g].stream ? (hipStream_t)groups[g].stream : origin, n_steps);
+            if (plans[g].train) rcAll = tiles_launch_train(plans[g], group_stream(groups[g], origin), n_steps);
         for (int l = 0; l < n_steps && rcAll == REM2D_OK; ++l)
             for (int g = 0; g < n_groups; ++g)
-                if (!plans[g].train) tiles_launch_step(plans[g], groups[g].stream ? (hipStream_t)groups[g].stream : origin);
+                if (!plans[g].train) tiles_launch_step(plans[g], group_stream(groups[g], origin));
         if (rcAll == REM2D_OK) {
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) rcAll = fail(REM2D_E_HIP, std::string("groups_enqueue: ") + hipGetErrorString(e));
         }
     } else {
         for (int g = 0; g < n_groups && rcAll == REM2D_OK; ++g)
-            rcAll = step_fused(groups[g].worlds, groups[g].n_worlds, n_steps, dt, vel_iters, pos_iters,
-                               groups[g].stream ? (hipStream_t)groups[g].stream : origin);
+            rcAll = step_fused(groups[g].worlds, groups[g].n_worlds, n_steps, dt, vel_iters, pos_iters, group_stream(groups[g], origin));
     }
     // join: the origin stream waits for every group
     for (int g = 0; g < n_groups; ++g) {
-        hipStream_t sg = groups[g].stream ? (hipStream_t)groups[g].stream : origin;
+        hipStream_t sg = group_stream(groups[g], origin);
         if (sg == origin) continue;
         rem2d_world *wg = groups[g].worlds[0];
         hipError_t e = hipEventRecord(wg->evJoin, sg);
@@ -1218,43 +1201,32 @@ extern "C" int rem2d_groups_step_ex(const rem2d_step_group *groups, int32_t n_gr
     if (!groups || n_groups <= 0) return fail(REM2D_E_INVALID, "no step groups");
     if (n_groups > REM2D_MAX_STEP_GROUPS) return fail(REM2D_E_INVALID, "too many step groups");
     ITERS_TRY(vel_iters, pos_iters);
-    rem2d_world *w00 = nullptr;
     bool timing = false;
     for (int g = 0; g < n_groups; ++g) {
-        if (!groups[g].worlds || groups[g].n_worlds <= 0) return fail(REM2D_E_INVALID, "a step group has no worlds");
-        if (groups[g].n_worlds > REM2D_MAX_WORLDS_PER_STEP) return fail(REM2D_E_INVALID, "too many worlds in one step group");
-        for (int i = 0; i < groups[g].n_worlds; ++i) {
-            rem2d_world *w = groups[g].worlds[i];
-            if (!w) return fail(REM2D_E_INVALID, "world is NULL");
-            if (!w00) w00 = w;
-            if (!w->haveTerrain) return fail(REM2D_E_STATE, "rem2d_world_set_terrain must be called before step");
-            if (!w->haveReset) return fail(REM2D_E_STATE, "rem2d_world_reset must be called before step");
-            if (w->cfg.device != w00->cfg.device) return fail(REM2D_E_INVALID, "step groups of one call must share the device");
-            if ((w->cfg.flags & REM2D_FLAG_CONTINUOUS) != (groups[g].worlds[0]->cfg.flags & REM2D_FLAG_CONTINUOUS))
-                return fail(REM2D_E_INVALID, "worlds of one launch must agree on REM2D_FLAG_CONTINUOUS");
-            timing = timing || w->timing;
-        }
+        int rc = worlds_ok(groups[g].worlds, groups[g].n_worlds, g > 0 ? groups[0].worlds[0] : nullptr, true);
+        if (rc != REM2D_OK) return rc;
+        for (int i = 0; i < groups[g].n_worlds; ++i) timing = timing || groups[g].worlds[i]->timing;
     }
     if (n_steps <= 0) return REM2D_OK;
+    rem2d_world *w00 = groups[0].worlds[0];
     HIP_TRY(hipSetDevice(w00->cfg.device));
     for (int g = 0; g < n_groups; ++g) {
         rem2d_world *wg = groups[g].worlds[0];
         if (!wg->evFork) HIP_TRY(hipEventCreateWithFlags(&wg->evFork, hipEventDisableTiming));
         if (!wg->evJoin) HIP_TRY(hipEventCreateWithFlags(&wg->evJoin, hipEventDisableTiming));
     }
-    const bool tiles = pipeline_mode(w00) == 3;
-    if (tiles)
-        for (int g = 0; g < n_groups; ++g) SHAPES_TRY(groups[g].worlds, groups[g].n_worlds);
     hipStream_t origin = (hipStream_t)stream;
+    if (pipeline_mode(w00) != 3) return groups_enqueue(groups, n_groups, nullptr, n_steps, dt, vel_iters, pos_iters, origin);
+    // the groups' plans, made once: the plain enqueue, the capture and the choice between them read the same ones
+    TilePlan plans[REM2D_MAX_STEP_GROUPS];
     bool train = false; // (a step train is one launch per call already, and sizes its flag buffer while it is queued: never captured)
-    if (tiles)
-        for (int g = 0; g < n_groups; ++g) {
-            TilePlan P;
-            tiles_plan(P, groups[g].worlds, groups[g].n_worlds, dt, vel_iters, pos_iters);
-            train = train || P.train;
-        }
-    if (!(flags & REM2D_STEP_GRAPH) || timing || !tiles || train)
-        return groups_enqueue(groups, n_groups, n_steps, dt, vel_iters, pos_iters, origin, tiles);
+    for (int g = 0; g < n_groups; ++g) {
+        SHAPES_TRY(groups[g].worlds, groups[g].n_worlds);
+        tiles_plan(plans[g], groups[g].worlds, groups[g].n_worlds, dt, vel_iters, pos_iters);
+        train = train || plans[g].train;
+    }
+    if (!(flags & REM2D_STEP_GRAPH) || timing || train)
+        return groups_enqueue(groups, n_groups, plans, n_steps, dt, vel_iters, pos_iters, origin);
 
     // ---- graph replay ----
     std::lock_guard<std::mutex> graphLock(g_graphMu);
@@ -1281,9 +1253,8 @@ extern "C" int rem2d_groups_step_ex(const rem2d_step_group *groups, int32_t n_gr
         if (!g_captureStream) HIP_TRY(hipStreamCreateWithFlags(&g_captureStream, hipStreamNonBlocking));
         // the capture starts on a stream of the library's own (the caller's may be the NULL stream, which cannot capture);
         // group streams are pulled into the capture by the fork events
-        std::vector<rem2d_step_group> cg(groups, groups + n_groups);
         HIP_TRY(hipStreamBeginCapture(g_captureStream, hipStreamCaptureModeRelaxed));
-        int rc = groups_enqueue(cg.data(), n_groups, n_steps, dt, vel_iters, pos_iters, g_captureStream, true);
+        int rc = groups_enqueue(groups, n_groups, plans, n_steps, dt, vel_iters, pos_iters, g_captureStream);
         hipGraph_t graph = nullptr;
         hipError_t e = hipStreamEndCapture(g_captureStream, &graph);
         if (rc != REM2D_OK) {
@@ -1500,25 +1471,9 @@ extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {
     if (on) {
         drain_timing(w);
         const size_t want = on > 1 ? (size_t)on : 4096; // launches that can be timed before the next read-back
-        while (w->evPool.size() < want) {
-            hipEvent_t a = nullptr, b = nullptr;
-            HIP_TRY(hipEventCreate(&a));
-            hipError_t e = hipEventCreate(&b);
-            if (e != hipSuccess) {
-                (void)hipEventDestroy(a);
-                return fail(REM2D_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-            }
-            w->evPool.emplace_back(a, b);
-        }
-        while (w->evPoolStep.size() < want) {
-            hipEvent_t a = nullptr, b = nullptr;
-            HIP_TRY(hipEventCreate(&a));
-            hipError_t e = hipEventCreate(&b);
-            if (e != hipSuccess) {
-                (void)hipEventDestroy(a);
-                return fail(REM2D_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-            }
-            w->evPoolStep.emplace_back(a, b);
+        for (EventPool *pool : {&w->evKernel, &w->evStep}) {
+            int rc = pool->fill(want);
+            if (rc != REM2D_OK) return rc;
         }
     }
     w->timing = on != 0;
@@ -1528,10 +1483,7 @@ extern "C" int rem2d_world_kernel_time_ms(rem2d_world *w, double *total_ms, int6
     if (!w) return fail(REM2D_E_INVALID, "world is NULL");
     HIP_TRY(hipSetDevice(w->cfg.device));
     drain_timing(w);
-    if (total_ms) *total_ms = w->accumMs;
-    if (launches) *launches = w->launches;
-    w->accumMs = 0.0;
-    w->launches = 0;
+    w->evKernel.report(total_ms, launches);
     return REM2D_OK;
 }
 #if defined(REM2D_TOI_STAMPS) || defined(REM2D_POS_STAMPS)
@@ -1556,9 +1508,6 @@ extern "C" int rem2d_world_step_time_ms(rem2d_world *w, double *total_ms, int64_
     if (!w) return fail(REM2D_E_INVALID, "world is NULL");
     HIP_TRY(hipSetDevice(w->cfg.device));
     drain_timing(w);
-    if (total_ms) *total_ms = w->accumMsStep;
-    if (steps) *steps = w->launchesStep;
-    w->accumMsStep = 0.0;
-    w->launchesStep = 0;
+    w->evStep.report(total_ms, steps);
     return REM2D_OK;
 }
