@@ -89,6 +89,8 @@ MORPH_FIELDS = ("shape", "hx", "hy", "x", "y", "angle", "parent", "jround", "ax"
 RENDER_ABI_VERSION = 1      # include/rem2d_render.h
 RENDER_MAX_SIZE = 8192      # REM2D_RENDER_MAX_SIZE
 CONTROL_ABI_VERSION = 1     # include/rem2d_control.h
+SENSE_ABI_VERSION = 1       # include/rem2d_sense.h
+SENSE_MAX_RAYS = 64         # REM2D_SENSE_MAX_RAYS
 
 
 class WorldCfg(C.Structure):
@@ -331,6 +333,12 @@ def lib(wide=False):
                                        C.c_void_p]
     if L.rem2d_control_abi_version() != CONTROL_ABI_VERSION:
         raise Rem2dError("%s: control ABI version mismatch" % os.path.basename(path))
+    # terrain range sensing (include/rem2d_sense.h)
+    L.rem2d_sense_abi_version.restype = C.c_int
+    L.rem2d_worlds_sense.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p]
+    if L.rem2d_sense_abi_version() != SENSE_ABI_VERSION:
+        raise Rem2dError("%s: sense ABI version mismatch" % os.path.basename(path))
     if L.rem2d_abi_version() != 11:
         raise Rem2dError("%s: ABI version mismatch" % os.path.basename(path))
     L.rem2d_build_id.restype = C.c_char_p

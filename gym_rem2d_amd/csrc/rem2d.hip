@@ -41,6 +41,7 @@
 #include "rem2d_gather.h"
 #include "rem2d_render.h"
 #include <rem2d_control.h> // the public header (include/); the quoted name below is the kernels' file beside this one
+#include <rem2d_sense.h>   // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -96,6 +97,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_diversity.h"
 #include "rem2d_raster.h"
 #include "rem2d_control.h"
+#include "rem2d_sense.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -1460,6 +1462,45 @@ extern "C" int rem2d_worlds_control(rem2d_world *const *worlds, int32_t n_worlds
         const unsigned per = CTL_THREADS / WAVE;
         hipLaunchKernelGGL(rem2d_control_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb,
                            (int)mode, values_dev, (int)max_bodies, (long long)n_rows, (const unsigned char *)mask_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+
+// ---- terrain range sensing (include/rem2d_sense.h, csrc/rem2d_sense.h) ----
+extern "C" int rem2d_sense_abi_version(void) { return REM2D_SENSE_ABI_VERSION; }
+extern "C" int rem2d_worlds_sense(rem2d_world *const *worlds, int32_t n_worlds, const double *ray_offsets_dev, int32_t n_rays,
+                                  float *frac_dev, int32_t *hit_dev, int64_t rows, void *stream) {
+    // (arguments first, worlds after: nothing is dereferenced before it has been checked)
+    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "sense: no worlds");
+    if (!ray_offsets_dev || !frac_dev) return fail(REM2D_E_INVALID, "sense: NULL device pointer");
+    if (n_rays < 1 || n_rays > REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, "sense: n_rays must be 1.." + std::to_string(REM2D_SENSE_MAX_RAYS) + ", not " + std::to_string(n_rays));
+    if (rows < 0) return fail(REM2D_E_INVALID, "sense: negative row count");
+    for (int32_t i = 0; i < n_worlds; ++i)
+        if (!worlds[i]) return fail(REM2D_E_INVALID, "sense: world " + std::to_string(i) + " is NULL");
+    for (int32_t i = 0; i < n_worlds; ++i) {
+        if (worlds[i]->cfg.lanes > 64) return fail(REM2D_E_INVALID, "sense: more than 64 lanes per creature");
+        if (worlds[i]->cfg.device != worlds[0]->cfg.device) return fail(REM2D_E_INVALID, "sense: the worlds must share a device");
+        if (!worlds[i]->haveTerrain) return fail(REM2D_E_STATE, "sense: rem2d_world_set_terrain must be called first");
+        if (!worlds[i]->haveReset) return fail(REM2D_E_STATE, "sense: rem2d_world_reset (or adopt) must be called first");
+    }
+    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
+    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
+        CtlTable Tb;
+        SenseTable Ts;
+        const int n = std::min(CTL_TABLE, (int)n_worlds - first);
+        const unsigned blocks = control_table(Tb, worlds, first, n);
+        memset(&Ts, 0, sizeof(Ts));
+        for (int i = 0; i < n; ++i) {
+            const Terrain &T = worlds[first + i]->T; // (flx is the start of the 20 planes rem2d_world_set_terrain uploads)
+            Ts.t[i].base = T.flx;
+            Ts.t[i].nEdge = T.nEdge; Ts.t[i].nPoly = T.nPoly;
+            Ts.t[i].x0 = T.x0; Ts.t[i].invPitch = T.invPitch;
+        }
+        const unsigned per = CTL_THREADS / WAVE;
+        hipLaunchKernelGGL(rem2d_sense_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Ts,
+                           ray_offsets_dev, (int)n_rays, frac_dev, (int *)hit_dev, (long long)rows);
         HIP_TRY(hipGetLastError());
     }
     return REM2D_OK;

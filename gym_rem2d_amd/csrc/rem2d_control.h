@@ -35,6 +35,7 @@ struct CtlTable {
 // Which world and which of its lanes a thread serves.
 struct CtlLane {
     CtlWorld S;        // the world of this wavefront
+    int world;         // ... and its index in the launch's table
     unsigned gl, env;  // arena lane (< Lp) and creature of this thread
     int K, base, sub;  // lanes per creature; first lane of the creature's group inside the wavefront; lane inside the group
     bool inWorld, live; // a creature of the world (not padding); ... and a body (shape != 0)
@@ -48,6 +49,7 @@ __device__ __forceinline__ bool ctl_locate(const CtlTable &Tb, CtlLane &c) {
     while (wi < Tb.n && wv >= Tb.w[wi].blockEnd) firstBlock = Tb.w[wi++].blockEnd;
     if (wi >= Tb.n) return false;
     c.S = Tb.w[wi];
+    c.world = wi;
     const CtlWorld &S = c.S;
     c.K = (int)S.lanes;
     const int lane = (int)(threadIdx.x & (WAVE - 1));

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, control, gymshim
+from . import _lib, control, gymshim, sense
 from .compiler import Morphology, build_creature, lanes_for
 from .terrain import make_terrain
 from .world import BatchedWorld
@@ -188,6 +188,8 @@ class BatchedModular2D:
         self._obs = None                                       # observe()'s persistent buffer: made (zeroed) on first use after a reset
         self._obs_bodies = max(m.lanes for m, _ in batches)    # default max_bodies of observe(): the largest lane bucket
         self._ctl_keep = None
+        self._sense = None                                     # sense_terrain()'s persistent (frac, hit) buffers, made on first use
+        self._sense_rays = {}                                  # ray tables on the device, by content
         # Step groups: a step is a chain of four launches, each as long as its slowest wavefront; independent parts of the
         # population on their own streams let one part's tail run under another part's kernels.  (Creatures are
         # independent, so any split is legal.)  What counts is the number of 64-lane blocks and how long a step is: below
@@ -561,6 +563,42 @@ class BatchedModular2D:
         if worlds:
             self._ctl_keep = control.control(worlds, mode, values, mask)   # (the tensors the queued kernel reads)
 
+    def _ray_table(self, rays):
+        """The ray table on the device: uploaded once, then found again by its bytes."""
+        rays = sense.check_rays(sense.bipedal_rays() if rays is None else
+                                (rays.detach().cpu().numpy() if isinstance(rays, torch.Tensor) else rays))
+        key = rays.tobytes()
+        dev = self._sense_rays.get(key)
+        if dev is None:
+            if len(self._sense_rays) >= 16:      # (a caller that makes a new table per call must not grow this without bound)
+                self._sense_rays.clear()
+            dev = self._sense_rays[key] = torch.from_numpy(rays.copy()).to(self.worlds[0][0].device)
+        return dev
+
+    def sense_terrain(self, rays=None, out=None, hits=False):
+        """How far the ground is along rays cast from every creature's root body: float32 ``[N, R]`` on the device, rows in
+        population order, column r the fraction of ray r at which it first meets the track's edges or hardcore boxes, 1.0 where it
+        meets nothing.  ``rays``: float64 ``[R, 2]`` offsets from the root in the world frame (they do not turn with the root), R
+        up to 64; default ``sense.bipedal_rays()``, BipedalWalker's 10-ray fan of length ``sense.LIDAR_RANGE``.  A table is
+        uploaded once and found again by its content (passing one blocks for the upload the first time).  ``hits=True`` returns
+        ``(frac, hit)``, hit int32 ``[N, R]``: the static proxy met -- hardcore boxes first, then edge i as ``n_polys + i`` -- or
+        -1.  One kernel of the library for the whole population, queued on the current stream like step() and observe().
+        ``out``: a contiguous float32 ``[N, R]`` tensor to write the fractions into; without it the env's persistent buffer is
+        returned (1.0 / -1 at first use, overwritten by the next call: clone what must last).  Rows of creatures that compact() has
+        retired are not written any more: they keep their last value."""
+        dev_rays = self._ray_table(rays)
+        R = int(dev_rays.shape[0])
+        dev = self.worlds[0][0].device
+        if self._sense is None or self._sense[0].shape[1] != R:
+            self._sense = (torch.ones((self.n_envs, R), dtype=torch.float32, device=dev),
+                           torch.full((self.n_envs, R), sense.NO_HIT, dtype=torch.int32, device=dev))
+        frac = self._sense[0] if out is None else out
+        hit = self._sense[1] if hits else None
+        worlds = self._control_worlds()
+        if worlds:
+            sense.sense(worlds, dev_rays, frac, hit)
+        return (frac, hit) if hits else frac
+
     def render(self, creatures=None, mode='rgb_array', **kw):
         """Frames of the creatures as they stand now: uint8 [n, H, W, 3] on the device (gym's rgb_array layout, one image per
         creature), drawn by the library's renderer (render.render_frames, which takes the keyword arguments: width, height,
@@ -583,16 +621,23 @@ class Modular2D(gymshim.Env):
 
     DEFAULT_MAX_BODIES = 32
 
-    def __init__(self, random_seed=None, device=None, closed_loop=False, max_bodies=DEFAULT_MAX_BODIES, wide=False):
+    def __init__(self, random_seed=None, device=None, closed_loop=False, max_bodies=DEFAULT_MAX_BODIES, wide=False, lidar=False):
         """closed_loop=False: the reference's surface -- step(action) ignores the action and returns observation 0.
         closed_loop=True: ``observation_space`` is the ``8 + 6 * max_bodies`` floats of BatchedModular2D.observe (columns:
         control.layout(max_bodies)), ``action_space`` ``max_bodies`` joint target angles within +-pi/2 (column b: the joint between
         ``robot.components[b]`` and its parent; column 0 is ignored); reset() returns the first observation and step(action)
         applies the action (None: leave the joints as they are) and returns the next one as a numpy array.  A creature that
         overflows the default build's contact slots cannot be replayed in the wide build under external actions: read
-        ``env._batch.errors()``, or construct the env with wide=True."""
+        ``env._batch.errors()``, or construct the env with wide=True.
+        lidar=True (closed loop only): BipedalWalker's 10 lidar fractions (BatchedModular2D.sense_terrain with sense.bipedal_rays())
+        follow the ``8 + 6 * max_bodies`` words; ``observation_space`` is that much wider.  The reference advertises them
+        (24 = 14 + 10 floats) and never fills them."""
         self._device = device
         self.closed_loop, self.max_bodies, self._wide = bool(closed_loop), int(max_bodies), wide
+        self.lidar = bool(lidar)
+        if self.lidar and not self.closed_loop:
+            raise ValueError("lidar=True needs closed_loop=True (the open-loop env returns observation 0, like the reference)")
+        self._n_lidar = len(sense.bipedal_rays()) if self.lidar else 0
         self.seed(random_seed)
         self.viewer = None
         self.tree_morphology = None
@@ -606,7 +651,7 @@ class Modular2D(gymshim.Env):
         if self.closed_loop:
             if not 1 <= self.max_bodies <= control.MAX_BODIES:
                 raise ValueError("max_bodies must be 1..%d" % control.MAX_BODIES)
-            high = np.full(control.width(self.max_bodies), np.inf)
+            high = np.full(control.width(self.max_bodies) + self._n_lidar, np.inf)
             self.observation_space = gymshim.Box(-high, high, dtype=np.float32)
             lim = np.full(self.max_bodies, np.pi / 2)
             self.action_space = gymshim.Box(-lim, lim, dtype=np.float32)
@@ -644,14 +689,17 @@ class Modular2D(gymshim.Env):
         self.world.set_outputs(self._pin_reward, self._pin_done, self._pin_index)
         if self.closed_loop:
             self._obs_dev = torch.zeros((1, control.width(self.max_bodies)), dtype=torch.float32, device=self.world.device)
-            self._pin_obs = torch.zeros(control.width(self.max_bodies), dtype=torch.float32).pin_memory()
+            self._pin_obs = torch.zeros(control.width(self.max_bodies) + self._n_lidar, dtype=torch.float32).pin_memory()
             return self._observe()
         return
 
     def _observe(self):
         """The creature's observation row as a numpy array (closed loop): observe kernel, copy to pinned memory, one wait."""
         self._batch.observe(self.max_bodies, out=self._obs_dev)
-        self._pin_obs.copy_(self._obs_dev[0], non_blocking=True)
+        W = self._obs_dev.shape[1]
+        self._pin_obs[:W].copy_(self._obs_dev[0], non_blocking=True)
+        if self.lidar:
+            self._pin_obs[W:].copy_(self._batch.sense_terrain()[0], non_blocking=True)
         torch.cuda.current_stream(self.world.device).synchronize()
         return self._pin_obs.numpy().copy()
 

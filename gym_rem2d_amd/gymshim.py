@@ -99,4 +99,8 @@ register(id="Modular2DLocomotion-v0", entry_point="gym_rem2d_amd.env:Modular2D",
 register(id="Modular2DLocomotionControl-v0", entry_point="gym_rem2d_amd.env:Modular2D", max_episode_steps=240 * 20,
          kwargs={"closed_loop": True})
 
+# ... and with BipedalWalker's 10 lidar fractions behind the observation (Modular2D(closed_loop=True, lidar=True): gym_rem2d_amd.sense)
+register(id="Modular2DLocomotionLidar-v0", entry_point="gym_rem2d_amd.env:Modular2D", max_episode_steps=240 * 20,
+         kwargs={"closed_loop": True, "lidar": True})
+
 __all__ = ["Env", "Box", "np_random", "TimeLimit", "register", "make"]

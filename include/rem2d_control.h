@@ -39,7 +39,8 @@ extern "C" {
  * root: its words 0..2 and 4..5 are 0.  Body slots beyond the creature's count are 0, bodies beyond max_bodies are dropped.
  * Every word is a copy, an exact int -> float conversion or ONE separately rounded binary32 operation, so the
  * -ffp-contract=fast build writes the same bits as the default one.  (Room for range sensing is left behind the body
- * block: a later version appends, it does not move these words.) */
+ * block: a later version appends, it does not move these words.  The ray fractions themselves come from a call of their own,
+ * include/rem2d_sense.h, as rows of their own in the same population order; the gym facade puts them behind these words.) */
 #define REM2D_OBS_HEAD 8
 #define REM2D_OBS_BODY 6
 
