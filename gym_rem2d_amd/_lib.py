@@ -373,6 +373,12 @@ def plan_tiles(parent, jround, n_envs, lanes, n_padded, max_creatures=0, tile_sh
     return out[:n.value + 1].copy()
 
 
+def world_array(worlds):
+    """The `rem2d_world *` array of a list of BatchedWorld, as the rem2d_worlds_* calls and rem2d_step_group take it."""
+    handles = [w.h for w in worlds]
+    return (C.c_void_p * len(handles))(*handles)
+
+
 def check(rc, wide=False):
     if rc != 0:
         raise Rem2dError("librem2d: error %d: %s" % (rc, lib(wide).rem2d_last_error().decode()))

@@ -6,8 +6,6 @@ wall of death and the body count, then six words per body in ``robot.components`
 columns.  A joint target is a write to two controller words between two steps (amp := 0, offset := target): the step kernels
 compute ``(amp * sin(i_state + phase)) + offset`` as before and find ``offset``.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -49,10 +47,6 @@ def layout(max_bodies):
     return Layout(max_bodies)
 
 
-def _world_array(worlds):
-    return (C.c_void_p * len(worlds))(*[w.h for w in worlds])
-
-
 def _check_bodies(max_bodies):
     if not 1 <= int(max_bodies) <= MAX_BODIES:
         raise ValueError("max_bodies must be 1..%d, not %r" % (MAX_BODIES, max_bodies))
@@ -66,7 +60,7 @@ def observe(worlds, max_bodies, out):
     if out.dtype != torch.float32 or not out.is_contiguous() or out.device != w0.device or out.dim() != 2 \
             or out.shape[1] != width(max_bodies):
         raise ValueError("observe: out must be a contiguous float32 [rows, %d] tensor on %s" % (width(max_bodies), w0.device))
-    _lib.check(w0.L.rem2d_worlds_observe(_world_array(worlds), len(worlds), int(max_bodies), out.data_ptr(), out.shape[0],
+    _lib.check(w0.L.rem2d_worlds_observe(_lib.world_array(worlds), len(worlds), int(max_bodies), out.data_ptr(), out.shape[0],
                                          w0._stream()), w0.wide)
     return out
 
@@ -92,6 +86,6 @@ def control(worlds, mode, values, mask=None):
             raise ValueError("control: mask must be [rows, max_bodies] like the values")
         mask = (mask != 0).to(device=w0.device, dtype=torch.uint8).contiguous()
         mask_ptr = mask.data_ptr()
-    _lib.check(w0.L.rem2d_worlds_control(_world_array(worlds), len(worlds), int(mode), values.data_ptr(), int(values.shape[1]),
+    _lib.check(w0.L.rem2d_worlds_control(_lib.world_array(worlds), len(worlds), int(mode), values.data_ptr(), int(values.shape[1]),
                                          int(values.shape[0]), mask_ptr, w0._stream()), w0.wide)
     return values, mask

@@ -13,13 +13,13 @@ the reference's pyglet window (``:655-768``) is out of scope (SURVEY.md section 
 """
 import copy
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
-from . import _lib, control, gymshim, sense
+from . import _lib, control, gymshim, launch_policy, sense
 from .compiler import Morphology, build_creature, lanes_for
+from .launch_policy import _uniform  # noqa: F401  (its home now; still importable from here)
 from .terrain import make_terrain
 from .world import BatchedWorld
 
@@ -48,12 +48,6 @@ class WallOfDeath:
 
     def update(self):
         self.position += self.speed
-
-
-def _uniform(m):
-    """Every creature of the batch has the same tree and solver schedule (fixed-morphology population)."""
-    n, K = m.n_envs, m.lanes
-    return all(bool((m.arrays[k].reshape(n, K) == m.arrays[k][:K]).all()) for k in ("shape", "parent", "jround"))
 
 
 _GROUP_STREAMS = {}   # device -> the step-group streams of this process
@@ -104,9 +98,9 @@ class BatchedModular2D:
         self.trees = None
         self.robots = None
         self._reward = self._done = None
-        # REM2D_MERGED_LAUNCH=0: step every lane bucket on its own stream instead of one merged grid
-        self.merged_launch = os.environ.get("REM2D_MERGED_LAUNCH", "1") != "0"
-        self.step_groups = int(os.environ.get("REM2D_STEP_GROUPS", "0"))  # 0 = automatic
+        over = launch_policy.read_overrides()   # (REM2D_MERGED_LAUNCH, REM2D_STEP_GROUPS, REM2D_GRAPH, REM2D_REBALANCE: read here, once)
+        self.merged_launch = over.merged_launch   # False: step every lane bucket on its own stream instead of one merged grid
+        self.step_groups = over.step_groups       # 0 = automatic
         # launch shape of the velocity kernel (rem2d_world_set_tile_shape): None = automatic, unless the experiment
         # override REM2D_TILE_SHAPE fixes it (_lib.env_tile_shape).  Up to ~150 000 creatures a step is bound by its chain of stragglers and the
         # 64-lane tiles (4 wavefronts per SIMD) win; beyond that the chip's instruction issue saturates and the 256-lane
@@ -114,7 +108,8 @@ class BatchedModular2D:
         self.tile_shape = None
         self.groups, self.group_streams = [], []
         self._group_args = None
-        self.use_graph = os.environ.get("REM2D_GRAPH", "0") == "1"   # replay every step call as a hipGraph
+        self._plan = None             # launch_policy.Plan of the population in place (made by _upload)
+        self.use_graph = over.use_graph   # replay every step call as a hipGraph
         # Creature order by current cost: every `rebalance_every` env-steps the creatures that used every position iteration in
         # the last step are moved to the front of their world's order (a stable partition: the static schedule order survives
         # within both classes), so that they share velocity tiles and position blocks -- a tile costs what its most expensive
@@ -122,7 +117,7 @@ class BatchedModular2D:
         # small launch per world every N steps).  -1: automatic (50 for mixed populations: +3.3 % on config 3, +3 % on the
         # 131 072-creature generation against REM2D_FLAG_RETILE, which it replaces as the policy; +0.5 % on config 4; -0.8 % at
         # 1 M creatures), 0: off.  REM2D_REBALANCE overrides (experiments); rebalance() does the same from the host.
-        self.rebalance_every = int(os.environ.get("REM2D_REBALANCE", "-1"))
+        self.rebalance_every = over.rebalance_every
         self.options = dict(options or {})
         if on_handover not in ("raise", "flag"):
             raise ValueError("on_handover must be 'raise' or 'flag'")
@@ -160,11 +155,12 @@ class BatchedModular2D:
         for e, s in enumerate(specs):
             groups.setdefault(lanes_for(s.n_bodies), []).append(e)
         batches = []
+        desc = launch_policy.read_overrides().sort_desc   # (REM2D_SORT_DESC)
         for lanes in sorted(groups):
             # creatures of one wave run in lockstep: keep waves homogeneous in joint rounds / size
             # (the most complex first: their wavefronts are the long ones and should be dispatched first)
             idx = sorted(groups[lanes], key=lambda e: (specs[e].period, max(specs[e].rounds, default=-1), specs[e].n_bodies),
-                         reverse=os.environ.get("REM2D_SORT_DESC", "1") != "0")
+                         reverse=desc)
             batches.append((Morphology.from_specs([specs[e] for e in idx], lanes), idx))
         self._upload(batches, len(specs))
 
@@ -181,7 +177,6 @@ class BatchedModular2D:
         self._uploaded = [(m, np.asarray(idx, dtype=np.int64)) for m, idx in batches]   # (evaluate.run_episode's fallback)
         self._compacted = False
         self._inactive = set()   # worlds compact() found without a single open fitness
-        self._tile_shape_used = None
         self._group_args = None
         self.n_envs = n_envs
         self.streams = []
@@ -190,100 +185,25 @@ class BatchedModular2D:
         self._ctl_keep = None
         self._sense = None                                     # sense_terrain()'s persistent (frac, hit) buffers, made on first use
         self._sense_rays = {}                                  # ray tables on the device, by content
-        # Step groups: a step is a chain of four launches, each as long as its slowest wavefront; independent parts of the
-        # population on their own streams let one part's tail run under another part's kernels.  (Creatures are
-        # independent, so any split is legal.)  What counts is the number of 64-lane blocks and how long a step is: below
-        # ~3 000 blocks the chip is not full anyway (4 096 4-module chains: 23.0 M env-steps/s with one group, 20.3 M with
-        # two); mixed or wide-creature populations, whose steps take more than a millisecond, gain up to four groups
-        # (65 536 L-system creatures, 7 790 blocks: 26 / 36 / 39 / 40 M with 1 / 2 / 3 / 4; CPPN creatures on the
-        # hardcore terrain 38.7 / 43.2 / 44.3 M with 2 / 3 / 4); small uniform creatures, whose steps are short, three
-        # (65 536 8-module chains, 8 192 blocks: 121 / 160 / 171 / 135 M with 1 / 2 / 3 / 4).  Never more than four streams
-        # in all, the caller's included (see group_streams below).
-        groups = self.step_groups
-        blocks = sum(m.n_envs * m.lanes for m, _ in batches) / 64.0
-        if groups <= 0:
-            long_steps = len(batches) > 1 or max(m.lanes for m, _ in batches) >= 16
-            if long_steps:
-                groups = 4 if blocks >= 512 else 1   # (8 192 / 16 384 / 24 576 L-system creatures: +13 / +11 / +15 % over one)
-            else:
-                groups = 3 if blocks >= 6144 else (2 if blocks >= 3072 else 1)
-        # Tile shape of the velocity kernel: 64-lane tiles up to ~130 000 creatures, 128-lane tiles beyond (see __init__).
-        # Fixed-morphology populations (every creature the same tree: the north-star's "8-module creatures") are the
-        # exception: all creatures of a tile need the same slots per iteration, so a bigger tile costs no more per
-        # iteration and halves the wavefronts -- 128-lane tiles: 170 M instead of 136 M env-steps/s for 65 536 8-module
-        # chains -- once the 64-lane tiles of a step group would no longer fit the chip at once.
-        shape = self.tile_shape
-        if shape is None and _lib.env_tile_shape() is None:
-            shape = 1 if n_envs >= self.BIG_POPULATION else 3
-            if shape == 3 and blocks / groups > 2048 and all(_uniform(m) for m, _ in batches):
-                shape = 4   # (128-lane tiles with the static phase -> set map: nothing to rotate in a uniform population)
-        self._tile_shape_used = shape
-        # (experiment override, host layer only: a tile shape per lane bucket, "lanes:shape,..." -- e.g. the light buckets on 128-lane
-        # tiles beside the 16-lane bucket on 64-lane ones in ONE launch: the launch takes the kernel of the largest shape)
-        by_lanes = {}
-        for item in os.environ.get("REM2D_TILE_SHAPE_BY_LANES", "").split(","):
-            if ":" in item:
-                by_lanes[int(item.split(":")[0])] = int(item.split(":")[1])
-        self._tile_shape_by_lanes = by_lanes
-        # REM2D_FLAG_RETILE (the position kernel deals the creatures anew in every step, in arrival order) was round 3's policy
-        # for >= 98 304 creatures; the stable re-ordering every 50 steps does better there and also pays at 65 536
-        # (profiles/r04_lane_fill_experiments.txt), so the flag is an experiment override now (REM2D_RETILE=1)
-        retile = os.environ.get("REM2D_RETILE") == "1"
-        # The step train (the library's default launch form for 64-lane tiles, REM2D_OPT_FUSE_VELPOST = 2: all steps of a call in
-        # one launch, block-steps handed from workgroup to workgroup) is ONE in-order train: it wants the whole population in one
-        # group (config 3: 64.8 M env-steps/s with one group, 59 M with two, 39 M with four -- profiles/r05_step_train.txt).
-        # Round 6: the 128-lane tile shapes have a train of their own (rem2d_step_train128_kernel: an item = a tile's two blocks).  It
-        # wins while a step is bound by the chain of its launches and loses once the chip's instruction issue saturates: shape 1
-        # up to TRAIN128_MAX creatures (beyond: per-step launches on four step groups, as before); shape 4 (uniform populations) --
-        # see TRAIN128_UNIFORM.
-        opts = dict(_lib.env_options(), **self.options)
-        eff_shape = shape if shape is not None else _lib.env_tile_shape()
-        self._launch_options = {}
-        if "fuse_velpost" not in opts and ((eff_shape == 1 and n_envs > self.TRAIN128_MAX) or (eff_shape == 4 and not self.TRAIN128_UNIFORM)):
-            self._launch_options["fuse_velpost"] = 1   # (per-step launches; no result depends on it)
-            opts["fuse_velpost"] = 1
-        train = eff_shape in (3, 1, 4) and not retile and \
-            opts.get("fuse_velpost", 2) == 2 and opts.get("pipeline", 3) == 3 and opts.get("debug", 0) == 0
-        if train and self.step_groups <= 0:
-            groups = 1      # ... unless its lane buckets, cut into worlds of <= MAX_WORLD_LANES lanes, are more than one launch takes
-
-            def worlds_per_group(g):
-                return sum(-(-(-(-m.n_envs // g)) // max(1, self.MAX_WORLD_LANES // m.lanes)) for m, _ in batches)
-            while groups < _lib.MAX_STEP_GROUPS and worlds_per_group(groups) > _lib.MAX_WORLDS_PER_STEP:
-                groups += 1
-        self._world_flags = (self.flags | _lib.FLAG_RETILE) if retile else (self.flags & ~_lib.FLAG_RETILE)
-        every = self.rebalance_every
-        if every < 0:
-            every = self.REBALANCE_EVERY if (n_envs >= 4096 and not all(_uniform(m) for m, _ in batches)) else 0
-        self._rebalance_steps = 0 if retile else every
-        self.groups = [[] for _ in range(groups)]
-        for morph, idx in batches:
-            idx = np.asarray(idx, dtype=np.int64)
-            # which creatures go to which group: wavefront-sized runs of the (schedule-sorted) batch are dealt round-robin,
-            # so that every group gets the same mix of simple and complex creatures and the groups reach the join at the
-            # end of a step call together (contiguous parts, REM2D_GROUP_SPLIT=cut: 40.2 instead of 40.6 M on config 3)
-            if morph.n_envs < 4 * groups:
-                members = [np.arange(morph.n_envs)]
-            elif os.environ.get("REM2D_GROUP_SPLIT") != "cut":
-                run = max(1, 64 // morph.lanes)
-                which = (np.arange(morph.n_envs) // run) % groups
-                members = [np.nonzero(which == g)[0] for g in range(groups)]
-            else:
-                cuts = [morph.n_envs * g // groups for g in range(groups + 1)]
-                members = [np.arange(cuts[g], cuts[g + 1]) for g in range(groups)]
-            pieces = []
-            for g, mem in enumerate(members):   # one world addresses its lanes with 32-bit offsets: <= MAX_WORLD_LANES
-                per = max(1, self.MAX_WORLD_LANES // morph.lanes)
-                for lo in range(0, len(mem), per):
-                    pieces.append((g, mem[lo:lo + per]))
-            for g, mem in pieces:
-                part = morph if len(mem) == morph.n_envs else morph.take(mem)
-                w = BatchedWorld(part.n_envs, part.lanes, self._world_flags, self.device, wide=self.wide, options=self._world_options())
-                w.set_terrain(self._terrain())
-                w.reset(part, tile_shape=self._tile_shape_by_lanes.get(part.lanes, shape))
-                self.groups[g].append(len(self.worlds))
-                self.worlds.append((w, torch.as_tensor(idx[mem], dtype=torch.long, device=w.device)))
-                self._world_morph.append(part)
+        # how this population runs -- step groups, tile shape, train or per-step launches, rebalancing, which creatures share a
+        # world -- is launch_policy.plan's decision, from the buckets' shapes, this env's settings and the REM2D_* overrides
+        knobs = launch_policy.Knobs(self.step_groups, self.tile_shape, self.flags, self.options, self.rebalance_every,
+                                    self.BIG_POPULATION, self.TRAIN128_MAX, self.TRAIN128_UNIFORM, self.REBALANCE_EVERY,
+                                    self.MAX_WORLD_LANES, _lib.MAX_STEP_GROUPS, _lib.MAX_WORLDS_PER_STEP)
+        plan = self._plan = launch_policy.plan([launch_policy.bucket(m) for m, _ in batches], n_envs, knobs,
+                                               launch_policy.read_overrides())
+        # (the names bench.py, tests and tools read)
+        self._tile_shape_used, self._tile_shape_by_lanes, self._launch_options = plan.tile_shape, plan.tile_shape_by_lanes, plan.launch_options
+        self._world_flags, self._rebalance_steps = plan.world_flags, plan.rebalance_steps
+        self.groups = [[] for _ in range(plan.groups)]
+        for piece in plan.pieces:
+            morph, idx = self._uploaded[piece.bucket]
+            part = morph if len(piece.members) == morph.n_envs else morph.take(piece.members)
+            w = self._new_world(part.n_envs, part.lanes)
+            w.reset(part, tile_shape=plan.tile_shape_by_lanes.get(part.lanes, plan.tile_shape))
+            self.groups[piece.group].append(len(self.worlds))
+            self.worlds.append((w, torch.as_tensor(idx[piece.members], dtype=torch.long, device=w.device)))
+            self._world_morph.append(part)
         self.groups = [g for g in self.groups if g]
         dev = self.worlds[0][0].device
         # the first group runs on the caller's stream: four streams in all is what the device overlaps well (a fifth costs
@@ -307,10 +227,13 @@ class BatchedModular2D:
             w.set_outputs(self._reward, self._done, idx.to(torch.int32))
 
     def _world_options(self):
-        opts = dict(getattr(self, "_launch_options", {}), **self.options)
-        if self._rebalance_steps > 0:
-            opts.setdefault("rebalance", self._rebalance_steps)
-        return opts or None
+        return self._plan.world_options
+
+    def _new_world(self, n_envs, lanes):
+        """A world of this env: its device and build, the plan's flags and options, the terrain."""
+        w = BatchedWorld(n_envs, lanes, self._plan.world_flags, self.device, wide=self.wide, options=self._world_options())
+        w.set_terrain(self._terrain())
+        return w
 
     def handover_failures(self, clear=False):
         """Failed hand-overs of the step train over all worlds (host-side counters, no synchronisation: what the launches that have
@@ -358,7 +281,7 @@ class BatchedModular2D:
             # the caller's stream, the steps of the groups queued round-robin, join -- or the whole call replayed as a
             # hipGraph (REM2D_GRAPH=1)
             if self._group_args is None:
-                arrs = [(C.c_void_p * len(g))(*[self.worlds[i][0].h for i in g]) for g in self.groups]
+                arrs = [_lib.world_array(self.worlds[i][0] for i in g) for g in self.groups]
                 sg = (_lib.StepGroup * len(self.groups))()
                 for k, (g, st) in enumerate(zip(self.groups, self.group_streams)):
                     sg[k].worlds = C.cast(arrs[k], C.POINTER(C.c_void_p))
@@ -407,7 +330,7 @@ class BatchedModular2D:
         train, 1 = velocity tiles and position iterations in one launch per step, 0 = two launches); for tools that name
         kernels, results never depend on it."""
         idx = self.groups[0] if self.groups else list(range(len(self.worlds)))
-        arr = (C.c_void_p * len(idx))(*[self.worlds[i][0].h for i in idx])
+        arr = _lib.world_array(self.worlds[i][0] for i in idx)
         shape, fused = C.c_int32(), C.c_int32()
         _lib.check(_lib.lib(self.wide).rem2d_worlds_launch_info(arr, len(idx), C.byref(shape), C.byref(fused)), self.wide)
         return shape.value, int(fused.value)
@@ -458,14 +381,13 @@ class BatchedModular2D:
                 self._inactive.update(wis)
                 continue
             part = Morphology.concat([self._world_morph[wi].take(k.cpu().numpy()) for wi, k in zip(wis, keeps) if k.numel()])
-            nw = BatchedWorld(n_keep, lanes, self._world_flags, self.device, wide=self.wide, options=self._world_options())
-            nw.set_terrain(self._terrain())
+            nw = self._new_world(n_keep, lanes)
             for name in _lib.FIELDS:
                 dst = nw.view(name)
                 dim = 1 if dst.dim() == 3 else 0
                 dst.copy_(torch.cat([self.worlds[wi][0].view(name).index_select(dim, k) for wi, k in zip(wis, keeps)
                                      if k.numel()], dim=dim))
-            nw.adopt(part, tile_shape=self._tile_shape_used)
+            nw.adopt(part, tile_shape=self._plan.tile_shape)
             new_idx = torch.cat([self.worlds[wi][1][k] for wi, k in zip(wis, keeps) if k.numel()])
             nw.set_outputs(self._reward, self._done, new_idx.to(torch.int32))
             torch.cuda.synchronize(nw.device)   # the old arenas must outlive the copies

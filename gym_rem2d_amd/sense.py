@@ -6,7 +6,6 @@ A ray is a binary64 offset from a creature's root body; its result is the fracti
 ``i`` as ``n_polys + i``; ``-1``: none).  ``bipedal_rays()`` is BipedalWalker's lidar fan, whose 10 fractions are the part of the
 reference's advertised 24-float observation that the reference itself never fills (Modular2DEnv.py:32, :741-744).
 """
-import ctypes as C
 import math
 
 import numpy as np
@@ -50,7 +49,6 @@ def sense(worlds, rays, frac, hit=None):
     if hit is not None and (hit.dtype != torch.int32 or not hit.is_contiguous() or hit.device != w0.device
                             or tuple(hit.shape) != tuple(frac.shape)):
         raise ValueError("sense: hit must be a contiguous int32 tensor of frac's shape on %s" % w0.device)
-    arr = (C.c_void_p * len(worlds))(*[w.h for w in worlds])
-    _lib.check(w0.L.rem2d_worlds_sense(arr, len(worlds), rays.data_ptr(), R, frac.data_ptr(),
+    _lib.check(w0.L.rem2d_worlds_sense(_lib.world_array(worlds), len(worlds), rays.data_ptr(), R, frac.data_ptr(),
                                        None if hit is None else hit.data_ptr(), int(frac.shape[0]), w0._stream()), w0.wide)
     return frac if hit is None else (frac, hit)

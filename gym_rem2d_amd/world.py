@@ -112,13 +112,25 @@ class BatchedWorld:
             float(terrain.friction)))
         self.terrain = terrain
 
+    def _install_tiles(self, morph, tile_shape):
+        """What reset() and adopt() share, done first: `morph` must have this world's shape; then the work partition of the velocity
+        kernel for these creatures -- consecutive creatures packed into tiles of <= 256 lanes with <= 64 joints per schedule phase
+        (include/rem2d.h, rem2d_world_set_tiles) -- planned from the host arrays (it needs nothing of the state that follows)."""
+        if morph.n_envs != self.n_envs or morph.lanes != self.lanes:
+            raise ValueError("morphology shape (%d x %d) does not match world (%d x %d)" %
+                             (morph.n_envs, morph.lanes, self.n_envs, self.lanes))
+        if tile_shape is not None:
+            self._check(self.L.rem2d_world_set_tile_shape(self.h, int(tile_shape)))
+            self.tile_shape = int(tile_shape)
+        self.tiles = _lib.plan_tiles(morph.arrays["parent"], morph.arrays["jround"], self.n_envs, self.lanes,
+                                     self.n_envs_padded, tile_shape=self.tile_shape, wide=self.wide)
+        self._check(self.L.rem2d_world_set_tiles(self.h, self.tiles.ctypes.data, len(self.tiles) - 1))
+
     # ---- reset: upload the morphology and rebuild every world ----
     def reset(self, morph: Morphology, tile_shape=None):
         """tile_shape: launch shape of the velocity kernel for this world (0 .. 4, include/rem2d.h
         rem2d_world_set_tile_shape); None keeps the world's current one (3 unless REM2D_TILE_SHAPE overrode it)."""
-        if morph.n_envs != self.n_envs or morph.lanes != self.lanes:
-            raise ValueError("morphology shape (%d x %d) does not match world (%d x %d)" %
-                             (morph.n_envs, morph.lanes, self.n_envs, self.lanes))
+        self._install_tiles(morph, tile_shape)
         dev = {}
         for k in MORPH_I32 + MORPH_F32 + MORPH_F64:
             dev[k] = torch.from_numpy(morph.arrays[k]).to(self.device, non_blocking=False)
@@ -127,29 +139,13 @@ class BatchedWorld:
             setattr(m, k, dev[k].data_ptr())
         self._morph_dev = dev  # keep alive until the reset kernel has run
         self._check(self.L.rem2d_world_reset(self.h, C.byref(m), self._stream()))
-        # work partition of the velocity kernel: consecutive creatures packed into tiles of <= 256 lanes with <= 64
-        # joints per schedule phase (include/rem2d.h, rem2d_world_set_tiles)
-        if tile_shape is not None:
-            self._check(self.L.rem2d_world_set_tile_shape(self.h, int(tile_shape)))
-            self.tile_shape = int(tile_shape)
-        self.tiles = _lib.plan_tiles(morph.arrays["parent"], morph.arrays["jround"], self.n_envs, self.lanes,
-                                     self.n_envs_padded, tile_shape=self.tile_shape, wide=self.wide)
-        self._check(self.L.rem2d_world_set_tiles(self.h, self.tiles.ctypes.data, len(self.tiles) - 1))
 
     def adopt(self, morph: Morphology, tile_shape=None):
         """Instead of reset(): the caller has filled every state field of this world (``view(name)`` for all of
         ``_lib.FIELDS``) from another world between two steps (include/rem2d.h, rem2d_world_adopt).  ``morph``: the
         host-side layout of the creatures now in this world, for the tile plan of the velocity kernel."""
-        if morph.n_envs != self.n_envs or morph.lanes != self.lanes:
-            raise ValueError("morphology shape (%d x %d) does not match world (%d x %d)" %
-                             (morph.n_envs, morph.lanes, self.n_envs, self.lanes))
+        self._install_tiles(morph, tile_shape)
         self._check(self.L.rem2d_world_adopt(self.h))
-        if tile_shape is not None:
-            self._check(self.L.rem2d_world_set_tile_shape(self.h, int(tile_shape)))
-            self.tile_shape = int(tile_shape)
-        self.tiles = _lib.plan_tiles(morph.arrays["parent"], morph.arrays["jround"], self.n_envs, self.lanes,
-                                     self.n_envs_padded, tile_shape=self.tile_shape, wide=self.wide)
-        self._check(self.L.rem2d_world_set_tiles(self.h, self.tiles.ctypes.data, len(self.tiles) - 1))
 
     def set_outputs(self, reward, done, index):
         """Let the kernels also write reward / done of creature e to reward[index[e]] / done[index[e]] (population
