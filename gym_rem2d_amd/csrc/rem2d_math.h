@@ -36,6 +36,9 @@ DEV float fclamp(float a, float lo, float hi) { return __builtin_amdgcn_fmed3f(a
 // whatever a is -- the median of (a, -m, m) is not.  With |m| as the upper bound the median is b2Clamp's value in both
 // cases (m >= 0: the same three numbers; m < 0: two of the three are -m).  The |.| is a source modifier of v_med3_f32.
 DEV float fclamp_sym(float a, float m) { return __builtin_amdgcn_fmed3f(a, -m, __builtin_fabsf(m)); }
+// a value the instruction selector must take as it is: keeps a product from being fused into the sum that consumes it (the sense
+// kernel and the renderer, whose results are defined as separately rounded operations in every build; see rem2d_sense.h)
+DEV float sn_keep(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xE4 /* quad_perm 0 1 2 3 */, 0xf, 0xf, false)); }
 DEV V2 vmin2(V2 a, V2 b) { return mk(fmin32(a.x, b.x), fmin32(a.y, b.y)); }
 DEV V2 vmax2(V2 a, V2 b) { return mk(fmax32(a.x, b.x), fmax32(a.y, b.y)); }
 DEV float vnormalize(V2 &a) {

@@ -9,8 +9,11 @@
 //
 // Every pixel is defined exactly, so that a CPU model (tests/render_model.py) matches it with ==:
 //   * pixel (i, j) has its centre at X = cam_x + (i + 0.5) * INV_SCALE, Y = (cam_y + H * INV_SCALE) - (j + 0.5) * INV_SCALE;
-//   * coverage uses + - * and comparisons only, every operation a separately rounded binary32 one (__fadd_rn & co., so that no
-//     -ffp-contract setting changes a pixel): edge functions cross(b - a, p - a) for quads, the triangle and the ground,
+//   * coverage uses + - * and comparisons only, every operation a separately rounded binary32 one in every build.  The
+//     __fmul_rn / __fadd_rn spelling does not give that by itself (they are the plain operators here, and -ffp-contract=fast
+//     fuses a product into the sum that consumes it: librem2d_fma.so drew other pixels until every product that a sum
+//     takes went through sn_keep(), rem2d_math.h -- r_mul; r_sq is the lone product; tests/test_render_forge_gpu.py compares the three builds): edge functions
+//     cross(b - a, p - a) for quads, the triangle and the ground,
 //     d^2 <= r^2 for discs, (r - h)^2 < d^2 <= (r + h)^2 for rings, and for a line band of half width h along a -> b
 //     cross^2 <= h^2 * |b - a|^2 with 0 <= dot(b - a, p - a) <= |b - a|^2 (butt ends);
 //   * a body's rotation is the engine's own rot_set(angle).
@@ -61,21 +64,22 @@ struct RBody {
 
 DEV float r_add(float a, float b) { return __fadd_rn(a, b); }
 DEV float r_sub(float a, float b) { return __fsub_rn(a, b); }
-DEV float r_mul(float a, float b) { return __fmul_rn(a, b); }
+DEV float r_mul(float a, float b) { return sn_keep(__fmul_rn(a, b)); } // a product that a sum takes: kept, so that it cannot fuse into it
+DEV float r_sq(float a, float b) { return __fmul_rn(a, b); }           // a product that only a comparison (or a store) takes: nothing to fuse with
 // cross(d, p - a) and dot(d, p - a)
 DEV void r_edge(float ax, float ay, float dx, float dy, float X, float Y, float &cr, float &dt) {
     const float qx = r_sub(X, ax), qy = r_sub(Y, ay);
     cr = r_sub(r_mul(dx, qy), r_mul(dy, qx));
     dt = r_add(r_mul(dx, qx), r_mul(dy, qy));
 }
-DEV bool r_band(float cr, float dt, float len2, float hh) { return r_mul(cr, cr) <= hh && dt >= 0.0f && dt <= len2; }
+DEV bool r_band(float cr, float dt, float len2, float hh) { return r_sq(cr, cr) <= hh && dt >= 0.0f && dt <= len2; }
 // a segment a -> b as a band of half width 1 px
 DEV bool r_segment(float ax, float ay, float bx, float by, float X, float Y) {
     const float dx = r_sub(bx, ax), dy = r_sub(by, ay);
     const float len2 = r_add(r_mul(dx, dx), r_mul(dy, dy));
     float cr, dt;
     r_edge(ax, ay, dx, dy, X, Y, cr, dt);
-    return r_band(cr, dt, len2, r_mul(r_mul(R_INV_SCALE, R_INV_SCALE), len2));
+    return r_band(cr, dt, len2, r_sq(r_sq(R_INV_SCALE, R_INV_SCALE), len2));
 }
 // the colour of a convex quad / triangle (CCW vertices) over `c`: fill where every edge function is >= 0, then the outline
 DEV unsigned r_poly(const float *vx, const float *vy, int n, float X, float Y, unsigned fill, unsigned line, unsigned c) {
@@ -87,7 +91,7 @@ DEV unsigned r_poly(const float *vx, const float *vy, int n, float X, float Y, u
         float cr, dt;
         r_edge(vx[k], vy[k], dx, dy, X, Y, cr, dt);
         inside = inside && cr >= 0.0f;
-        edge = edge || r_band(cr, dt, len2, r_mul(r_mul(R_INV_SCALE, R_INV_SCALE), len2));
+        edge = edge || r_band(cr, dt, len2, r_sq(r_sq(R_INV_SCALE, R_INV_SCALE), len2));
     }
     return edge ? line : (inside ? fill : c);
 }
@@ -96,7 +100,7 @@ DEV unsigned r_shade(float X, float Y, const Terrain &T, const RBody *bodies, co
                      float wod) {
     unsigned c = RC_SKY;
     // terrain edges near X: the edge index from the (uniform) pitch, +-1 for the +-0.1 pitch the xs may deviate by
-    float fi = r_mul(r_sub(X, T.x0), T.invPitch);
+    float fi = r_sq(r_sub(X, T.x0), T.invPitch);
     fi = fi < -2.0f ? -2.0f : (fi > (float)T.nEdge + 1.0f ? (float)T.nEdge + 1.0f : fi);
     const int i0 = (int)floorf(fi);
     // ground: below edge i (cross(b - a, p - a) <= 0), x between its ends, y >= 0
@@ -145,7 +149,7 @@ DEV unsigned r_shade(float X, float Y, const Terrain &T, const RBody *bodies, co
     // wall of death: 1 px wide
     {
         const float d = r_sub(X, wod);
-        if (r_mul(d, d) <= r_mul(R_HALF_PX, R_HALF_PX) && Y >= R_WOD_Y0 && Y <= R_WOD_Y1) c = RC_WOD;
+        if (r_sq(d, d) <= r_sq(R_HALF_PX, R_HALF_PX) && Y >= R_WOD_Y0 && Y <= R_WOD_Y1) c = RC_WOD;
     }
     // flag: pole, then the triangle
     if (r_segment(R_FLAG_X, R_FLAG_Y1, R_FLAG_X, R_FLAG_Y2, X, Y)) c = RC_FLAG_LINE;
@@ -192,11 +196,11 @@ __global__ __launch_bounds__(R_THREADS) void rem2d_render_kernel(State S, Terrai
             b.line = lineRgb ? ((unsigned)lineRgb[ci] | ((unsigned)lineRgb[ci + 1] << 8) | ((unsigned)lineRgb[ci + 2] << 16))
                              : (shape == SHAPE_CIRCLE ? RC_CIRCLE_LINE : RC_BOX_LINE);
             const float px = LF(L_PX), py = LF(L_PY), hx = LF(L_HX), hy = LF(L_HY);
-            const float H2 = r_mul(R_INV_SCALE, R_INV_SCALE);
+            const float H2 = r_sq(R_INV_SCALE, R_INV_SCALE);
             if (shape == SHAPE_CIRCLE) {
                 const float ri = r_sub(hx, R_INV_SCALE), ro = r_add(hx, R_INV_SCALE);
                 b.ax[0] = px; b.ay[0] = py;
-                b.dx[0] = r_mul(hx, hx); b.dy[0] = r_mul(ri, ri); b.len2[0] = r_mul(ro, ro);
+                b.dx[0] = r_sq(hx, hx); b.dy[0] = r_sq(ri, ri); b.len2[0] = r_sq(ro, ro);
                 b.lx = r_sub(px, hx); b.ux = r_add(px, hx); b.ly = r_sub(py, hx); b.uy = r_add(py, hx);
             } else if (shape == SHAPE_BOX) {
                 const Rot q = rot_set(LF(L_ANG));
@@ -214,7 +218,7 @@ __global__ __launch_bounds__(R_THREADS) void rem2d_render_kernel(State S, Terrai
                     b.ax[k] = vx[k]; b.ay[k] = vy[k];
                     b.dx[k] = r_sub(vx[k1], vx[k]); b.dy[k] = r_sub(vy[k1], vy[k]);
                     b.len2[k] = r_add(r_mul(b.dx[k], b.dx[k]), r_mul(b.dy[k], b.dy[k]));
-                    b.hh[k] = r_mul(H2, b.len2[k]);
+                    b.hh[k] = r_sq(H2, b.len2[k]);
                     b.lx = fminf(b.lx, vx[k]); b.ux = fmaxf(b.ux, vx[k]); b.ly = fminf(b.ly, vy[k]); b.uy = fmaxf(b.uy, vy[k]);
                 }
             }
@@ -249,7 +253,7 @@ __global__ __launch_bounds__(R_THREADS) void rem2d_render_kernel(State S, Terrai
         px[p] = r_shade(X, Y, T, bodies, list, nList, obst, nObst, wod);
     }
     const size_t off = (((size_t)img * H + j) * W + i0) * 3;
-    if (i0 + R_PX_PER_LANE <= W && (off & 3) == 0) { // the 12 bytes as three dwords
+    if (i0 + R_PX_PER_LANE <= W && ((uintptr_t)(out + off) & 3) == 0) { // the 12 bytes as three dwords (by address: `out` may be odd)
         unsigned *o = (unsigned *)(out + off);
         o[0] = px[0] | (px[1] << 24);
         o[1] = (px[1] >> 8) | (px[2] << 16);

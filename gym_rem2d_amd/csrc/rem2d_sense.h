@@ -48,8 +48,7 @@ struct SenseTable {
     SenseTerrain t[CTL_TABLE]; // world i of the launch's CtlTable
 };
 
-// a value the instruction selector must take as it is: keeps a product from being fused into the sum that consumes it
-DEV float sn_keep(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xE4 /* quad_perm 0 1 2 3 */, 0xf, 0xf, false)); }
+// (sn_keep: rem2d_math.h -- the renderer needs the same move)
 DEV float sn_mul(float a, float b) { return sn_keep(__fmul_rn(a, b)); }
 DEV float sn_dot(float ax, float ay, float bx, float by) { return __fadd_rn(sn_mul(ax, bx), sn_mul(ay, by)); }
 

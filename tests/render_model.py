@@ -90,10 +90,14 @@ def box_vertices(px, py, ang, hx, hy, sincosf):
     return vx, vy
 
 
-def render(width, height, cam, terrain=None, bodies=(), fill=None, line=None, wod=None, flag=True, sincosf=None):
+def render(width, height, cam, terrain=None, bodies=(), fill=None, line=None, wod=None, flag=True, sincosf=None, brute=False):
     """uint8 [height, width, 3].  cam: (x, y) of the view's lower left corner; terrain: a :class:`Terrain` or None;
     bodies: (shape, px, py, angle, hx, hy) per slot (shape 0: none, 1: box, 2: circle); fill / line: rgb per slot or None
-    for the shape colours; wod: the wall of death's x (a float64 state value) or None (not drawn); sincosf: oracle.sincosf."""
+    for the shape colours; wod: the wall of death's x (a float64 state value) or None (not drawn); sincosf: oracle.sincosf.
+    brute: the terrain without the kernel's shortcut -- every pixel is tested against EVERY edge (ground under each, then
+    each edge line from the highest index down), with no edge index computed from the pixel's x; obstacles and bodies have no
+    shortcut in either mode.  (The +-1 window of the other mode cannot cover a pitch under 2 px: a line's half width is 1 px.
+    rem2d_world_set_terrain accepts such a pitch, no track has one, and nothing here draws one.)"""
     cx, cy = f32(cam[0]), f32(cam[1])
     i = np.arange(width, dtype=f32)
     j = np.arange(height, dtype=f32)
@@ -103,7 +107,15 @@ def render(width, height, cam, terrain=None, bodies=(), fill=None, line=None, wo
     X, Y = np.meshgrid(X1, Y1)
     img = np.empty((height, width, 3), np.uint8)
     img[:] = SKY
-    if terrain is not None:
+    if terrain is not None and brute:
+        for k in range(terrain.n_edge):
+            ax, ay, bx, by = terrain.xs[k], terrain.ys[k], terrain.xs[k + 1], terrain.ys[k + 1]
+            cr, _ = _edge(ax, ay, bx - ax, by - ay, X, Y)
+            img[(X >= ax) & (X <= bx) & (Y >= f32(0)) & (cr <= f32(0))] = GROUND
+        for k in range(terrain.n_edge - 1, -1, -1):
+            m = _segment(terrain.xs[k], terrain.ys[k], terrain.xs[k + 1], terrain.ys[k + 1], X, Y)
+            img[m] = EDGE_ODD if k & 1 else EDGE_EVEN
+    elif terrain is not None:
         fi = (X1 - terrain.x0) * terrain.inv_pitch
         fi = np.where(fi < f32(-2), f32(-2), np.where(fi > f32(terrain.n_edge) + f32(1), f32(terrain.n_edge) + f32(1), fi))
         i0 = np.floor(fi).astype(np.int64)
@@ -125,6 +137,7 @@ def render(width, height, cam, terrain=None, bodies=(), fill=None, line=None, wo
             odd = np.broadcast_to((k & 1) == 1, X.shape)
             img[m & odd] = EDGE_ODD
             img[m & ~odd] = EDGE_EVEN
+    if terrain is not None:
         for q in reversed(terrain.polys):
             fm, em = _poly(q[:, 0], q[:, 1], X, Y)
             img[fm] = OBST_FILL

@@ -1,0 +1,149 @@
+"""The renderer on forged scenes (pytest -m gpu): rem2d_world_render, called straight through the library, against the BRUTE pixel
+model (render_model.render(brute=True): every edge, every obstacle, every body for every pixel -- no window, no per-tile cull) with
+np.array_equal, for every scene of tests/render_forge.py, in the default, the wide and the -ffp-contract=fast build; nothing written
+outside the frame at any byte alignment of `out`; the state untouched.  tests/test_render_forge_host.py keeps the scenes honest."""
+import numpy as np
+import pytest
+
+import render_forge as RF
+
+pytestmark = pytest.mark.gpu
+
+CANARY = 0xA7
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import __graft_entry__ as g
+    g.build()
+    return torch
+
+
+@pytest.fixture(scope="module")
+def sincosf(gpu):
+    from oracle import oracle as O
+    O.build()
+    return O.sincosf
+
+
+_MODEL = {}
+
+
+def model(scene, state, sincosf):
+    """the brute model's frames of a scene, computed once: every build must hold the same state bits, hence the same frames"""
+    if scene.name not in _MODEL:
+        _MODEL[scene.name] = (state, RF.model_frames(scene, state, sincosf))
+    first, frames = _MODEL[scene.name]
+    assert RF.same_state(first, state), "%s: the state read back differs between worlds" % scene.name
+    return frames
+
+
+def compare(got, want, what):
+    assert got.shape == want.shape and got.dtype == np.uint8, what
+    if not np.array_equal(got, want):
+        bad = np.argwhere(np.any(got != want, axis=-1))
+        pytest.fail("%s: %d pixels differ, first (image, row, column) %s: kernel %s model %s" % (
+            what, len(bad), bad[0].tolist(), got[tuple(bad[0])].tolist(), want[tuple(bad[0])].tolist()))
+
+
+def run_scene(torch, scene, sincosf, wide=False):
+    w, fill, line = RF.install(scene, wide=wide)
+    try:
+        want = model(scene, RF.readback(w), sincosf)
+        before = w.arena.clone()
+        for (width, height, creatures, cams), frames in zip(scene.calls, want):
+            got = RF.render_call(w, creatures, cams, width, height, fill, line).cpu().numpy()
+            compare(got, frames, "%s %d x %d x %d (%s build)" % (scene.name, len(creatures), width, height, {False: "default", True: "wide"}.get(wide, wide)))
+        torch.cuda.synchronize()
+        assert torch.equal(w.arena, before), "%s: rendering changed the state" % scene.name
+    finally:
+        w.close()
+
+
+@pytest.mark.parametrize("name", RF.names())
+def test_kernel_equals_brute_model(gpu, sincosf, name):
+    run_scene(gpu, RF.scenes()[name], sincosf)
+
+
+@pytest.mark.parametrize("name", RF.names())
+@pytest.mark.parametrize("wide", [True, "fma"], ids=["wide", "fma"])
+def test_other_builds_draw_the_same_frames(gpu, sincosf, wide, name):
+    """Every scene in librem2d_wide.so and in librem2d_fma.so (-ffp-contract=fast): the same state bits, the model's frames, hence the
+    default build's.  (The model's frames of a scene are computed once per session and shared by the three builds.)"""
+    run_scene(gpu, RF.scenes()[name], sincosf, wide=wide)
+
+
+def test_no_images_is_ok_and_writes_nothing(gpu):
+    from gym_rem2d_amd import _lib
+    torch = gpu
+    scene = RF.scenes()["four_near"]
+    w, _, _ = RF.install(scene)
+    try:
+        out = torch.full((4 * 4 * 3,), CANARY, dtype=torch.uint8, device=w.device)
+        _lib.check(w.L.rem2d_world_render(w.h, None, 0, None, None, None, 4, 4, out.data_ptr(), w._stream()), w.wide)
+        _lib.check(w.L.rem2d_world_render(w.h, None, 0, None, None, None, 4, 4, None, w._stream()), w.wide)
+        torch.cuda.synchronize()
+        assert bool((out == CANARY).all())
+    finally:
+        w.close()
+
+
+@pytest.mark.parametrize("size", [(1, 1), (2, 1), (3, 2), (4, 1), (5, 17), (6, 3), (64, 16), (65, 17), (66, 33), (70, 16), (255, 2)], ids=lambda s: "%dx%d" % s)
+def test_nothing_outside_the_frame_at_any_alignment(gpu, sincosf, size):
+    """The frames land in a view of a larger buffer full of a canary byte, starting 0, 1, 2 and 3 bytes past a 4-byte boundary (the
+    dword store path is chosen by the ADDRESS): the frame equals the model's, every byte before and after is still the canary."""
+    torch = gpu
+    scene = RF.scenes()["shape_%dx%d" % size]
+    w, fill, line = RF.install(scene)
+    try:
+        want = model(scene, RF.readback(w), sincosf)
+        pad = 64
+        for (width, height, creatures, cams), frames in zip(scene.calls, want):
+            nbytes = frames.size
+            for shift in (0, 1, 2, 3):
+                buf = torch.full((pad + shift + nbytes + pad,), CANARY, dtype=torch.uint8, device=w.device)
+                assert buf.data_ptr() % 4 == 0
+                out = buf[pad + shift:pad + shift + nbytes]
+                assert out.data_ptr() % 4 == shift
+                RF.render_call(w, creatures, cams, width, height, fill, line, out=out)
+                host = buf.cpu().numpy()
+                what = "%s, %d images, %d bytes past a dword" % (scene.name, len(creatures), shift)
+                compare(host[pad + shift:pad + shift + nbytes].reshape(frames.shape), frames, what)
+                assert (host[:pad + shift] == CANARY).all() and (host[pad + shift + nbytes:] == CANARY).all(), what + ": bytes outside the frame written"
+    finally:
+        w.close()
+
+
+def test_record_frames_at_an_odd_size(gpu):
+    """record_frames at 5 x 171 (a column from below the ground line into the sky), one creature, chunks of 3 (a frame is an odd number
+    of bytes, so every second chunk slot starts on an odd address) against frames rendered one by one into fresh tensors by a
+    twin env under the same camera."""
+    from gym_rem2d_amd import render as R, synthetic
+    from gym_rem2d_amd.env import BatchedModular2D
+    envs = []
+    for _ in range(2):
+        env = BatchedModular2D()
+        env.reset_morphology(synthetic.chain_population(4, 8, "left"))
+        envs.append(env)
+    env, twin = envs
+    try:
+        cam = R.ReferenceCamera(1, "cuda")
+        got = list(R.record_frames(env, 16, [2], every=2, width=5, height=171, chunk=3, stop_when_frozen=False))
+        assert [s for s, _ in got] == [0, 2, 4, 6, 8, 10, 12, 14, 16]
+        t, seen = 0, set()
+        for s, frames in got:
+            while t < s:
+                twin.step(1)
+                p = R.root_poses(twin, [2])
+                cam.update(p[:, 0], p[:, 1])
+                t += 1
+            want = twin.render([2], width=5, height=171, camera=cam).cpu().numpy()
+            assert frames.shape == (1, 171, 5, 3) and np.array_equal(frames, want), s
+            seen |= set(map(tuple, frames.reshape(-1, 3)))
+        assert len(seen) >= 3                                                            # more than sky
+    finally:
+        env.close()
+        twin.close()
