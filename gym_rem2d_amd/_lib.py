@@ -91,6 +91,10 @@ RENDER_MAX_SIZE = 8192      # REM2D_RENDER_MAX_SIZE
 CONTROL_ABI_VERSION = 1     # include/rem2d_control.h
 SENSE_ABI_VERSION = 1       # include/rem2d_sense.h
 SENSE_MAX_RAYS = 64         # REM2D_SENSE_MAX_RAYS
+SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
+SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
+SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
+SELFTEST_OPS = ("collide", "distance", "toi", "far_apart")   # REM2D_SELFTEST_COLLIDE .. _FAR_APART
 
 
 class WorldCfg(C.Structure):
@@ -339,6 +343,12 @@ def lib(wide=False):
                                      C.c_void_p]
     if L.rem2d_sense_abi_version() != SENSE_ABI_VERSION:
         raise Rem2dError("%s: sense ABI version mismatch" % os.path.basename(path))
+    # self-test of the collision geometry (include/rem2d_selftest.h)
+    L.rem2d_selftest_abi_version.restype = C.c_int
+    L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]
+    L.rem2d_selftest_geometry.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    if L.rem2d_selftest_abi_version() != SELFTEST_ABI_VERSION:
+        raise Rem2dError("%s: selftest ABI version mismatch" % os.path.basename(path))
     if L.rem2d_abi_version() != 11:
         raise Rem2dError("%s: ABI version mismatch" % os.path.basename(path))
     L.rem2d_build_id.restype = C.c_char_p

@@ -1552,3 +1552,6 @@ extern "C" int rem2d_world_step_time_ms(rem2d_world *w, double *total_ms, int64_
     w->evStep.report(total_ms, steps);
     return REM2D_OK;
 }
+
+// ---- self-test of the collision geometry on a table of cases (include/rem2d_selftest.h); LAST: its kernel follows every other ----
+#include "rem2d_selftest.h"

@@ -113,6 +113,8 @@ def _load(path):
         L.rem2d_oracle_kat_toi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         L.rem2d_oracle_kat_contact_solve.argtypes = [C.c_void_p, C.c_void_p]
         L.rem2d_oracle_kat_scalar.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.rem2d_oracle_kat_polygon_separations.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.rem2d_oracle_kat_geometry_batch.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rem2d_oracle_batch_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint] + [C.c_void_p] * 5
         L.rem2d_oracle_batch_run_caps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint] + [C.c_void_p] * 5
         L.rem2d_oracle_batch_window.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p,
@@ -343,6 +345,29 @@ def contact_solve(normal, points, cB, inv_mass, inv_I, friction, vB, wB, n_imp=(
     out = np.zeros(8, dtype=np.float32)
     assert lib().rem2d_oracle_kat_contact_solve(_ptr(vin), _ptr(out)) == 0
     return out[0:2].copy(), float(out[2]), out[3:5].copy(), out[5:7].copy(), int(out[7])
+
+
+GEOMETRY_OPS = {"collide": 0, "distance": 1, "toi": 2}
+
+
+def geometry_batch(op, cases):
+    """collide / distance / time of impact on a table of cases, float32 [n, >= 18] (rem2d_oracle_kat_geometry_batch; the layout
+    is tests/geometry_forge.py's) -> (fout float32 [n, 8], iout int32 [n, 8], extra int32 [n]: b2Distance's iterations)."""
+    cases = np.ascontiguousarray(cases, dtype=np.float32)
+    assert cases.ndim == 2
+    n = len(cases)
+    fout, iout, extra = np.zeros((n, 8), np.float32), np.zeros((n, 8), np.int32), np.zeros(n, np.int32)
+    rc = lib().rem2d_oracle_kat_geometry_batch(GEOMETRY_OPS[op], n, _ptr(cases), cases.shape[1], _ptr(fout), _ptr(iout), _ptr(extra))
+    assert rc == 0, "case %d: the oracle refuses its shapes" % (-1 - rc)
+    return fout, iout, extra
+
+
+def polygon_separations(cases):
+    """(separationA, separationB) of b2CollidePolygons for the box-on-hardcore-box cases of a geometry table: float32 [n, 2]."""
+    cases = np.ascontiguousarray(cases, dtype=np.float32)
+    out = np.zeros((len(cases), 2), np.float32)
+    assert lib().rem2d_oracle_kat_polygon_separations(len(cases), _ptr(cases), cases.shape[1], _ptr(out)) == 0
+    return out
 
 
 def batch_toi_stats(reset=True):

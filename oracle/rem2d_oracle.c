@@ -3186,6 +3186,88 @@ int rem2d_oracle_kat_collide(const float *specA, const float *xfA, const float *
     fout[6] = (float)m.points[1].localPoint.x; fout[7] = (float)m.points[1].localPoint.y;
     return 0;
 }
+/* The three entry points above on a table of n cases per call (tests/geometry_forge.py makes the table; 10^5 cases do not cost
+ * 10^5 ctypes calls), with the simplex cache b2distance leaves behind exposed.  Entry point only: every value comes from the
+ * functions above, unchanged.  A case is 18 binary32 words (case_words >= 18):
+ *   0 kind of A (0 edge, 1 static box)   1-8 A: x1 y1 x2 y2 of the edge, or the box's four corners as the terrain lists them
+ *   9 shape of B (1 box, 2 circle)  10-11 hx hy (circle: radius)  12-14 c0.xy a0 (pose / sweep start)  15-17 c.xy a (sweep end)
+ * op 0 collide, 1 distance, 2 time of impact; fout / iout are [n][8], laid out as include/rem2d_selftest.h lays out the
+ * device's answers (unused words 0).  extra [n] (may be NULL): b2Distance's iteration count for op 1.  Returns 0, -1 - i for
+ * the first case i whose shapes are refused, 1 for bad arguments. */
+int rem2d_oracle_kat_geometry_batch(int32_t op, int32_t n, const float *cases, int32_t case_words, float *fout, int32_t *iout,
+                                    int32_t *extra) {
+    if (op < 0 || op > 2 || n < 0 || case_words < 18 || (n > 0 && (!cases || !fout || !iout))) return 1;
+    int32_t bad = n;
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int32_t i = 0; i < n; ++i) {
+        const float *c = cases + (size_t)i * (size_t)case_words;
+        float *fo = fout + (size_t)i * 8;
+        int32_t *io = iout + (size_t)i * 8;
+        for (int k = 0; k < 8; ++k) { fo[k] = 0.0f; io[k] = 0; }
+        if (extra) extra[i] = 0;
+        float specA[10], specB[3];
+        if ((int)c[0] == 0) { specA[0] = 0.0f; for (int k = 0; k < 4; ++k) specA[1 + k] = c[1 + k]; }
+        else { specA[0] = 3.0f; specA[1] = 4.0f; for (int k = 0; k < 8; ++k) specA[2 + k] = c[1 + k]; }
+        specB[0] = c[9]; specB[1] = c[10]; specB[2] = c[11];
+        const float xfA[3] = {0.0f, 0.0f, 0.0f};
+        int rc;
+        if (op == 0) {
+            rc = rem2d_oracle_kat_collide(specA, xfA, specB, c + 12, io, fo);
+        } else if (op == 1) {
+            shape_t a, b;
+            rc = (kat_shape(&a, specA) || kat_shape(&b, specB)) ? -1 : 0;
+            if (rc == 0) {
+                proxy_t pa, pb;
+                proxy_set(&pa, &a);
+                proxy_set(&pb, &b);
+                simplex_cache_t cache;
+                memset(&cache, 0, sizeof(cache));
+                dist_out_t d;
+                b2distance(&d, &cache, &pa, kat_xf(xfA), &pb, kat_xf(c + 12));
+                fo[0] = (float)d.distance;
+                fo[1] = (float)cache.metric;
+                io[0] = (int32_t)cache.count;
+                for (int k = 0; k < 3; ++k) {
+                    io[1 + k] = k < (int)cache.count ? (int32_t)cache.indexA[k] : -1;
+                    io[4 + k] = k < (int)cache.count ? (int32_t)cache.indexB[k] : -1;
+                }
+                if (extra) extra[i] = d.iterations;
+            }
+        } else {
+            const float sweepA[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            float out[2];
+            rc = rem2d_oracle_kat_toi(specA, sweepA, specB, c + 12, 1.0f, out);
+            if (rc == 0) { io[0] = (int32_t)out[0]; fo[0] = out[1]; }
+        }
+        if (rc != 0) {
+#pragma omp critical
+            { if (i < bad) bad = i; }
+        }
+    }
+    return bad < n ? -1 - bad : 0;
+}
+/* The two b2FindMaxSeparation values b2CollidePolygons' flip rule compares, for the box-on-hardcore-box cases of the same table
+ * (kind of A = 1, shape of B = 1): out [n][2] = separationA, separationB as collide_polygons computes them; other cases get 0 0.
+ * Entry point only.  Lets a test find and keep the inputs where separationB == separationA + 0.1 b2_linearSlop to the bit. */
+int rem2d_oracle_kat_polygon_separations(int32_t n, const float *cases, int32_t case_words, float *out) {
+    if (n < 0 || case_words < 18 || (n > 0 && (!cases || !out))) return 1;
+#pragma omp parallel for schedule(dynamic, 1024)
+    for (int32_t i = 0; i < n; ++i) {
+        const float *c = cases + (size_t)i * (size_t)case_words;
+        out[2 * (size_t)i] = out[2 * (size_t)i + 1] = 0.0f;
+        if ((int)c[0] != 1 || (int)c[9] != 1) continue;
+        float specA[10], specB[3] = {1.0f, c[10], c[11]};
+        specA[0] = 3.0f; specA[1] = 4.0f;
+        for (int k = 0; k < 8; ++k) specA[2 + k] = c[1 + k];
+        shape_t a, b;
+        if (kat_shape(&a, specA) || kat_shape(&b, specB)) continue;
+        const float xfA[3] = {0.0f, 0.0f, 0.0f};
+        int edgeA = 0, edgeB = 0;
+        out[2 * (size_t)i] = (float)find_max_separation(&edgeA, &a, kat_xf(xfA), &b, kat_xf(c + 12));
+        out[2 * (size_t)i + 1] = (float)find_max_separation(&edgeB, &b, kat_xf(c + 12), &a, kat_xf(xfA));
+    }
+    return 0;
+}
 /* One b2ContactSolver::SolveVelocityConstraints sweep over ONE contact between the static body (A) and a body B at
  * cB: in = normal.xy, nPoints, p0.xy, p1.xy (world manifold points), cB.xy, invMassB, invIB, friction, vB.xy, wB,
  * accumulated normalImpulse0/1, tangentImpulse0/1.  out = vB.xy wB normalImpulse0/1 tangentImpulse0/1 pointCount

@@ -107,6 +107,10 @@ int rem2d_oracle_toi_dynamic_advances(const o_world *);
 /* standalone pieces for known-answer tests */
 void rem2d_oracle_sincosf(float a, float *s, float *c);
 int rem2d_oracle_kat_scalar(const float *a, const float *b, const float *c, int32_t n, float *out);
+/* collide / distance / time of impact on a table of cases (tests/geometry_forge.py); see rem2d_oracle.c */
+int rem2d_oracle_kat_geometry_batch(int32_t op, int32_t n, const float *cases, int32_t case_words, float *fout, int32_t *iout,
+                                    int32_t *extra);
+int rem2d_oracle_kat_polygon_separations(int32_t n, const float *cases, int32_t case_words, float *out);
 double rem2d_oracle_sin(double x);
 void rem2d_oracle_box_mass(float hx, float hy, float *mass, float *I);
 void rem2d_oracle_circle_mass(float r, float *mass, float *I);

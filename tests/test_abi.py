@@ -21,6 +21,10 @@ def test_exports_every_declared_symbol(lib):
     hdr = open(os.path.join(ROOT, "include", "rem2d.h")).read()
     names = sorted(set(re.findall(r"\b(rem2d_[a-z_0-9]+)\s*\(", hdr)))
     assert len(names) >= 12
+    # ... and the geometry self-test's header (include/rem2d_selftest.h)
+    selftest = set(re.findall(r"^\s*int\s+(rem2d_[a-z_0-9]+)\s*\(", open(os.path.join(ROOT, "include", "rem2d_selftest.h")).read(), flags=re.M))
+    assert selftest == {"rem2d_selftest_abi_version", "rem2d_selftest_static_box", "rem2d_selftest_geometry"}
+    names = names + sorted(selftest)
     for path in (lib.LIB_PATH, lib.WIDE_LIB_PATH):
         L = C.CDLL(path)
         for n in names:
