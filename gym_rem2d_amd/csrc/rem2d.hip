@@ -1086,6 +1086,11 @@ static bool iters_ok(int vel_iters, int pos_iters) {
 }
 #define ITERS_TRY(v, p) \
     do { if (!iters_ok((v), (p))) return fail(REM2D_E_INVALID, "velocity / position iterations must be in 0..8192"); } while (0)
+// b2World::Step skips Solve and SolveTOI at dt == 0 and keeps the old inv_dt0; the kernels have no such path (only invDt0 and the
+// TOI scan look at h > 0), and a negative or non-finite dt is a caller's error in Box2D too: refuse all of them here, before a launch.
+static bool dt_ok(float dt) { return dt > 0.0f && dt <= 3.402823466e+38f; } // (false for NaN: both comparisons are)
+#define DT_TRY(dt) \
+    do { if (!dt_ok(dt)) return fail(REM2D_E_INVALID, "dt must be finite and > 0"); } while (0)
 
 extern "C" int rem2d_world_step_ex(rem2d_world *w, int32_t n_steps, float dt, int32_t vel_iters, int32_t pos_iters,
                                    void *stream) {
@@ -1094,6 +1099,7 @@ extern "C" int rem2d_world_step_ex(rem2d_world *w, int32_t n_steps, float dt, in
 extern "C" int rem2d_worlds_step_ex(rem2d_world *const *ws, int32_t n_worlds, int32_t n_steps, float dt, int32_t vel_iters,
                                     int32_t pos_iters, void *stream) {
     ITERS_TRY(vel_iters, pos_iters); // (first: what a caller passes for the worlds is not looked at behind bad counts)
+    DT_TRY(dt);
     { int rc = worlds_ok(ws, n_worlds, nullptr, true); if (rc != REM2D_OK) return rc; }
     if (n_steps <= 0) return REM2D_OK;
     HIP_TRY(hipSetDevice(ws[0]->cfg.device));
@@ -1203,6 +1209,7 @@ extern "C" int rem2d_groups_step_ex(const rem2d_step_group *groups, int32_t n_gr
     if (!groups || n_groups <= 0) return fail(REM2D_E_INVALID, "no step groups");
     if (n_groups > REM2D_MAX_STEP_GROUPS) return fail(REM2D_E_INVALID, "too many step groups");
     ITERS_TRY(vel_iters, pos_iters);
+    DT_TRY(dt);
     bool timing = false;
     for (int g = 0; g < n_groups; ++g) {
         int rc = worlds_ok(groups[g].worlds, groups[g].n_worlds, g > 0 ? groups[0].worlds[0] : nullptr, true);

@@ -268,7 +268,9 @@ int rem2d_world_get_option(const rem2d_world *w, int32_t key, int32_t *value);
  * (REM2D_main.py:362-377).  Asynchronous on `stream` (hipStream_t). */
 int rem2d_world_step(rem2d_world *w, int32_t n_steps, void *stream);
 /* same with explicit b2World::Step arguments (dt, velocityIterations, positionIterations); iteration counts outside
- * 0..8192 are refused with REM2D_E_INVALID (the solver loops count ticks = iterations x schedule period in 16 bits) */
+ * 0..8192 are refused with REM2D_E_INVALID (the solver loops count ticks = iterations x schedule period in 16 bits), and so is
+ * a dt that is not finite or not > 0 (0, negative, NaN, infinity), in all three *_step_ex calls and before the worlds are looked
+ * at: b2World::Step's dt == 0 (collide only, inv_dt0 kept) has no counterpart in the kernels */
 int rem2d_world_step_ex(rem2d_world *w, int32_t n_steps, float dt, int32_t vel_iters, int32_t pos_iters,
                         void *stream);
 

@@ -325,8 +325,11 @@ static void c_bookkeeping(rem2d_cpu_world *w, const size_t *foff, int e, double 
     FPTR(int32_t, REM2D_F_STEPS)[e] = stepIdx + 1;
 }
 
+/* like the HIP library: a dt that is not finite or not > 0 is refused before anything is looked at (false for NaN) */
+static int c_dt_ok(float dt) { return dt > 0.0f && dt <= 3.402823466e+38f; }
 int rem2d_cpu_world_step_ex(rem2d_cpu_world *w, int32_t n_steps, float dt, int32_t vel_iters, int32_t pos_iters, void *stream) {
     (void)stream;
+    if (!c_dt_ok(dt)) return c_fail(REM2D_E_INVALID, "dt must be finite and > 0");
     if (!w) return c_fail(REM2D_E_INVALID, "world is NULL");
     if (!w->terrain || !w->haveReset) return c_fail(REM2D_E_STATE, "set_terrain and reset must precede step");
     if (n_steps < 0 || vel_iters < 0 || pos_iters < 0) return c_fail(REM2D_E_INVALID, "negative step or iteration count");
@@ -365,6 +368,7 @@ int rem2d_cpu_worlds_step_ex(rem2d_cpu_world *const *worlds, int32_t n_worlds, i
                              int32_t pos_iters, void *stream) {
     if (!worlds || n_worlds <= 0) return c_fail(REM2D_E_INVALID, "no worlds");
     if (vel_iters < 0 || pos_iters < 0 || vel_iters > 8192 || pos_iters > 8192) return c_fail(REM2D_E_INVALID, "velocity / position iterations must be in 0..8192");
+    if (!c_dt_ok(dt)) return c_fail(REM2D_E_INVALID, "dt must be finite and > 0");
     for (int i = 0; i < n_worlds; ++i) {
         const int rc = rem2d_cpu_world_step_ex(worlds[i], n_steps, dt, vel_iters, pos_iters, stream);
         if (rc != REM2D_OK) return rc;
@@ -381,6 +385,7 @@ int rem2d_cpu_groups_step_ex(const rem2d_step_group *groups, int32_t n_groups, i
     (void)flags;
     if (!groups || n_groups <= 0) return c_fail(REM2D_E_INVALID, "no step groups");
     if (n_groups > REM2D_MAX_STEP_GROUPS) return c_fail(REM2D_E_INVALID, "too many step groups");
+    if (!c_dt_ok(dt)) return c_fail(REM2D_E_INVALID, "dt must be finite and > 0");
     for (int g = 0; g < n_groups; ++g) {
         int rc = rem2d_cpu_worlds_step_ex((rem2d_cpu_world *const *)groups[g].worlds, groups[g].n_worlds, n_steps, dt, vel_iters,
                                           pos_iters, stream);

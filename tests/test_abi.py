@@ -74,6 +74,35 @@ def test_host_only_entry_points(lib):
     assert L.rem2d_world_step_ex(fake, 1, 0.02, 180, -1, None) == -1
 
 
+def test_step_ex_refuses_a_dt_that_is_not_finite_and_positive(lib):
+    """b2World::Step at dt == 0 collides and skips Solve / SolveTOI; the kernels have no such path, and a negative or non-finite dt
+    is no step at all: all three *_step_ex calls answer REM2D_E_INVALID naming dt, before they look at a world -- in the default
+    and the wide build, and in the host twin of the ABI (oracle/rem2d_cpu.c) alike."""
+    from oracle import cpu_twin as T
+    T.build()
+    fake = C.c_void_p(8)   # (never dereferenced: the argument check comes first)
+    worlds = (C.c_void_p * 1)(fake)
+
+    class Group(C.Structure):
+        _fields_ = [("worlds", C.c_void_p), ("n_worlds", C.c_int32), ("stream", C.c_void_p)]
+    group = Group(C.cast(worlds, C.c_void_p), 1, None)
+    lib.lib(), lib.lib(wide=True), T.lib()      # (loaded the usual way first; the handles below carry no argtypes of their own)
+    libs = [(C.CDLL(lib.LIB_PATH), "rem2d_"), (C.CDLL(lib.WIDE_LIB_PATH), "rem2d_"), (C.CDLL(T._SO), "rem2d_cpu_")]
+    for L, prefix in libs:
+        one, many, groups = (getattr(L, prefix + n) for n in ("world_step_ex", "worlds_step_ex", "groups_step_ex"))
+        err = getattr(L, prefix + "last_error")
+        err.restype = C.c_char_p
+        for dt in (0.0, -0.0, -0.02, float("nan"), float("inf"), float("-inf"), 1e39):     # (1e39 rounds to binary32 infinity)
+            for call in (lambda: one(fake, C.c_int32(1), C.c_float(dt), 180, 60, None),
+                         lambda: many(worlds, 1, C.c_int32(1), C.c_float(dt), 180, 60, None),
+                         lambda: groups(C.byref(group), 1, C.c_int32(1), C.c_float(dt), 180, 60, None, 0)):
+                assert call() == -1 and b"dt" in err(), (prefix, dt)
+        # a bad iteration count is refused as before, and a good dt gets past both checks to the world (NULL here)
+        assert many(worlds, 1, 1, C.c_float(0.02), 70000, 60, None) == -1 and b"0..8192" in err()
+        assert one(None, 1, C.c_float(0.02), 180, 60, None) == -1 and b"dt" not in err()
+        assert one(None, 1, C.c_float(1e-30), 180, 60, None) == -1 and b"dt" not in err()
+
+
 def test_library_reads_no_environment_variable():
     """The library's launch options are rem2d_world_set_option arguments (include/rem2d.h REM2D_OPT_*): the HIP sources
     must not call getenv, and the REM2D_* experiment overrides live in gym_rem2d_amd/_lib.py alone."""
