@@ -86,13 +86,12 @@ def show_best_episode(individual, tree_depth=None, interval=5, frames_dir=None, 
     (:162-167).  The frames (render.record_frames: the reference's scrolling camera) go to ``frames_dir`` as
     ``frame<step>.png`` when it is given.  Returns (fitness, number of frames); the fitness is evaluate()'s rule on the same
     episode cap as the batched evaluation."""
-    from . import _lib
     from .env import BatchedModular2D
-    from .evaluate import EPISODE_CAP
+    from .evaluate import EPISODE_CAP, EVAL_FLAGS
     from .render import record_frames, write_png
     if tree_depth is None:
         tree_depth = individual.tree_depth
-    env = BatchedModular2D(flags=_lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN, device=device)
+    env = BatchedModular2D(flags=EVAL_FLAGS, device=device)
     try:
         env.reset([individual.genome.create(tree_depth)], [individual.genome.moduleList])
         n = 0
@@ -135,16 +134,15 @@ def run_ea(config=None, population=None, evaluate_batch=None, seed=None, save_di
     if n_generations is None:
         n_generations = 1 + int(int(config["ea"]["n_evaluations"]) / pop_size)
     if evaluate_batch is None:
-        from .evaluate import evaluate_population
+        from .evaluate import EVAL_FLAGS, evaluate_population
         from .env import BatchedModular2D
-        from . import _lib
-        env = BatchedModular2D(flags=_lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN)
+        env = BatchedModular2D(flags=EVAL_FLAGS)
 
         def evaluate_batch(inds):
             # one out-of-domain creature (contacts beyond even the wide build) must not abort a generation: it gets
             # evaluate.UNRESOLVED_FITNESS, a warning names it, run_ea.last_unresolved keeps the indices per generation
             fits = evaluate_population(inds, tree_depth=tree_depth, env=env, on_error="penalty")
-            run_ea.last_unresolved.append(list(getattr(env, "last_unresolved", [])))
+            run_ea.last_unresolved.append(list(env.last_episode.unresolved))
             return fits
 
     run_ea.last_unresolved = []

@@ -372,3 +372,22 @@ def encode_network_native(individuals, tree_depth=None, n_threads=0):
     arrays = network_genome_arrays(genomes)
     lanes = 32   # the emitter stops at MAX_MODULES = 20 (+ the root): at most 22 nodes
     return batches_from_compiled(compile_network_arrays(arrays, depth, maxm, lanes, n_threads))
+
+
+def encode_native(individuals, tree_depth=None, n_threads=0):
+    """The native encoder a population's genomes allow; the same batches as encode_population either way."""
+    from .encodings.lsystem import LSystem
+    from .encodings.network import FeedForwardCPPN, NNEncoding
+    if individuals and all(type(ind.genome) is LSystem for ind in individuals) and \
+            len({(ind.genome.treeDepth, ind.genome.maxModules) for ind in individuals}) == 1:
+        # L-system genomes: native compiler (no fork, ~30 us per individual incl. reading the objects)
+        return encode_lsystem_native(individuals, n_threads=n_threads)
+    if individuals and all(type(ind.genome) is NNEncoding and type(ind.genome.nn_g) is FeedForwardCPPN for ind in individuals) and \
+            len({ind.genome.maxModules for ind in individuals}) == 1:
+        # network genomes (feed-forward CPPN): the NN queries that grow the tree run natively as well -- unless the individuals
+        # have their own tree depths: the node-by-node compiler below expresses each with its own
+        depths = {tree_depth} if tree_depth is not None else {ind.tree_depth for ind in individuals}
+        if len(depths) == 1:
+            return encode_network_native(individuals, depths.pop(), n_threads=n_threads)
+    # every other encoding: python hands out the phenotype trees, the native compiler builds the creatures
+    return encode_trees_native(individuals, tree_depth, n_threads=n_threads)

@@ -98,6 +98,7 @@ class BatchedModular2D:
         self.trees = None
         self.robots = None
         self._reward = self._done = None
+        self.last_episode = None      # evaluate.EpisodeReport of the population in place (None: no episode since its upload)
         over = launch_policy.read_overrides()   # (REM2D_MERGED_LAUNCH, REM2D_STEP_GROUPS, REM2D_GRAPH, REM2D_REBALANCE: read here, once)
         self.merged_launch = over.merged_launch   # False: step every lane bucket on its own stream instead of one merged grid
         self.step_groups = over.step_groups       # 0 = automatic
@@ -166,8 +167,13 @@ class BatchedModular2D:
 
     def reset_morphology(self, morph):
         """Fast path: a precompiled SoA batch (one lane count)."""
+        self.reset_batches([(morph, list(range(morph.n_envs)))])
+
+    def reset_batches(self, batches, n_envs=None):
+        """Precompiled lane-bucket batches [(Morphology, population indices)] (encode.batches_from_compiled, population.compile);
+        n_envs: the population's size (None: the batches' total)."""
         self.trees = self.robots = None
-        self._upload([(morph, list(range(morph.n_envs)))], morph.n_envs)
+        self._upload(batches, sum(m.n_envs for m, _ in batches) if n_envs is None else n_envs)
 
     def _upload(self, batches, n_envs):
         for w, _ in self.worlds:
@@ -176,6 +182,7 @@ class BatchedModular2D:
         self._world_morph = []   # host-side layout of every world's creatures (compact() re-plans tiles from it)
         self._uploaded = [(m, np.asarray(idx, dtype=np.int64)) for m, idx in batches]   # (evaluate.run_episode's fallback)
         self._compacted = False
+        self.last_episode = None
         self._inactive = set()   # worlds compact() found without a single open fitness
         self._group_args = None
         self.n_envs = n_envs

@@ -8,6 +8,7 @@ torch.distributed job (one process per GPU, contiguous blocks) and gathers the f
 single all-gather -- RCCL over xGMI on the MI355X node, gloo in the CPU tests.  There is no
 per-step collective: creatures are independent.
 """
+import collections
 import math
 
 import numpy as np
@@ -16,6 +17,14 @@ import torch
 from . import _lib
 
 EPISODE_CAP = 2500  # wall of death advances 0.04/step and the goal is x > 100
+# the flags of an evaluation env: fitness is all that leaves it, and creatures whose fitness is final need no more steps
+EVAL_FLAGS = _lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN
+
+# What an episode found (run_episode_masked builds it once, at its end; ``BatchedModular2D.last_episode`` keeps it until the next
+# upload).  codes: int32 [N], the creatures' final REM2D_ERR_* bits (of the wide run where there was one: what SolverOverflow
+# reports for the creatures still unresolved); handover: sorted population indices re-run on per-step launches; overflow: indices
+# that needed the wide build; unresolved: indices without a valid fitness after every fallback.
+EpisodeReport = collections.namedtuple("EpisodeReport", "codes handover overflow unresolved")
 
 
 def _env_singleton():
@@ -140,7 +149,7 @@ def reevaluate(env, mask, fit, wide=None, options=None, max_steps=EPISODE_CAP, c
         sel = np.nonzero(np.isin(idx, idx_bad))[0]
         if sel.size:
             batches.append((morph.take(sel), np.searchsorted(idx_bad, idx[sel]).tolist()))
-    again._upload(batches, int(idx_bad.size))
+    again.reset_batches(batches, int(idx_bad.size))
     _episode(again, max_steps, chunk, compact=False)
     where = torch.as_tensor(idx_bad, dtype=torch.long, device=fit.device)
     fit.index_copy_(0, where, again.fitness.to(fit.device))
@@ -149,24 +158,23 @@ def reevaluate(env, mask, fit, wide=None, options=None, max_steps=EPISODE_CAP, c
     return codes
 
 
-def reevaluate_wide(env, bad, fit, max_steps=EPISODE_CAP, chunk=100):
+def reevaluate_wide(env, bad, fit, handover, max_steps=EPISODE_CAP, chunk=100):
     """The overflow fallback (see ``reevaluate``): the creatures of ``bad`` again, from reset, in the wide build.  Writes their
-    fitness into ``fit`` and returns the mask of creatures that overflowed even there."""
-    codes = _resolve_handover(env, reevaluate(env, bad, fit, wide=True, max_steps=max_steps, chunk=chunk), fit, True, max_steps, chunk)
-    env.last_error_codes = codes   # (REM2D_ERR_* of the wide run, [N]: what SolverOverflow reports for the creatures still unresolved)
-    return codes != 0
+    fitness into ``fit`` and returns the REM2D_ERR_* codes [N] of the wide run (0 elsewhere): non-zero = overflowed even there."""
+    return _resolve_handover(env, reevaluate(env, bad, fit, wide=True, max_steps=max_steps, chunk=chunk), fit, True, handover,
+                             max_steps, chunk)
 
 
-def _resolve_handover(env, err, fit, wide, max_steps, chunk):
+def _resolve_handover(env, err, fit, wide, handover, max_steps, chunk):
     """``err``: REM2D_ERR_* codes [N] of a run in the env's own (wide=None) or the wide build.  The creatures that carry
     REM2D_ERR_HANDOVER are evaluated again on per-step launches of that build; returns the codes with theirs replaced by the second
-    run's, and logs the event on the env (``env.last_handover``: population indices).  A hand-over bit that survives per-step
-    launches cannot exist (they have no hand-over); if it does, HandoverError."""
+    run's, and adds their population indices to the set ``handover``.  A hand-over bit that survives per-step launches cannot
+    exist (they have no hand-over); if it does, HandoverError."""
     hand = (err & _lib.ERR_HANDOVER) != 0
     if not bool(hand.any()):
         return err
     idx = torch.nonzero(hand).flatten().cpu().tolist()
-    env.last_handover = sorted(set(getattr(env, "last_handover", [])) | set(idx))
+    handover.update(idx)
     import warnings
     warnings.warn("%d creature(s) were flagged REM2D_ERR_HANDOVER by a step train launch (first: %s): evaluating them again on "
                   "per-step launches" % (len(idx), idx[:8]))
@@ -182,7 +190,8 @@ def run_episode_masked(env, max_steps=EPISODE_CAP, chunk=100, compact=True, fall
     (with ``fallback``) the wide build's as well.  Never raises on overflow -- what a sharded job calls before its
     collective (a rank that raised here would leave the others waiting in the all-gather).
     Creatures a step train flagged REM2D_ERR_HANDOVER are ALWAYS resolved here (whatever ``fallback`` says): evaluated again on
-    per-step launches of the same build, never sent to the wide build for it, never penalised; ``env.last_handover`` lists them."""
+    per-step launches of the same build, never sent to the wide build for it, never penalised.  What the episode found is left
+    in ``env.last_episode`` (EpisodeReport)."""
     policy, env.on_handover = env.on_handover, "flag"   # (the episode goes on for everybody else; the flagged ones are dealt with below)
     try:
         _episode(env, max_steps, chunk, compact)
@@ -190,14 +199,17 @@ def run_episode_masked(env, max_steps=EPISODE_CAP, chunk=100, compact=True, fall
         err = env.errors().to(torch.int32)
     finally:
         env.on_handover = policy
-    env.last_handover = []
+    handover = set()
+    # (the counter is read and cleared without a synchronisation before it, and a count above 0 with no flagged creature is
+    # dropped here: kept exactly as it was -- ADVICE.md's finding on this line is a change of behaviour and not made here)
     if env.handover_failures(clear=True) or bool(((err & _lib.ERR_HANDOVER) != 0).any()):
-        err = _resolve_handover(env, err, fit, None, max_steps, chunk)
+        err = _resolve_handover(env, err, fit, None, handover, max_steps, chunk)
     bad = (err & _lib.ERR_CAPACITY) != 0
-    env.last_error_codes = err
-    env.last_overflow = torch.nonzero(bad).flatten().cpu().tolist()   # population indices that needed the fallback
+    overflow = torch.nonzero(bad).flatten().cpu().tolist()   # population indices that needed the fallback
     if fallback and bool(bad.any()):
-        bad = reevaluate_wide(env, bad, fit, max_steps, chunk)
+        err = reevaluate_wide(env, bad, fit, handover, max_steps, chunk)
+        bad = err != 0
+    env.last_episode = EpisodeReport(err, sorted(handover), overflow, torch.nonzero(bad).flatten().cpu().tolist())
     return fit, bad
 
 
@@ -220,22 +232,21 @@ def run_episode(env, max_steps=EPISODE_CAP, chunk=100, on_error="fallback", comp
     by default, not fatal: on_error="fallback" re-evaluates the flagged creatures in the wide build (reevaluate_wide) so
     that every individual gets the fitness Box2D would give, and raises only for creatures that overflow even that;
     on_error="penalty" (what the EA loops use) does the same but never raises: a creature beyond the wide build gets
-    UNRESOLVED_FITNESS, a warning names it and ``env.last_unresolved`` lists it;
-    "raise" / "warn" / "ignore" judge the default build's flags without a second attempt.  compact: in worlds created
+    UNRESOLVED_FITNESS, a warning names it and ``env.last_episode.unresolved`` lists it;
+    "raise" / "warn" / "ignore" judge the default build's flags without a second attempt (and leave no report:
+    ``env.last_episode`` is None after them).  compact: in worlds created
     with REM2D_FLAG_SKIP_FROZEN (the bodies of finished creatures are nobody's business any more) the survivors are
     moved into smaller worlds between chunks once most of a world has finished (BatchedModular2D.compact) -- same
     fitness, a shorter episode."""
-    if on_error == "penalty":
+    if on_error in ("penalty", "fallback"):
         fit, bad = run_episode_masked(env, max_steps, chunk, compact, fallback=True)
-        env.last_unresolved = apply_penalty(fit, bad)
+        if on_error == "penalty":
+            apply_penalty(fit, bad)
+        elif bool(bad.any()):
+            report = env.last_episode
+            raise SolverOverflow(report.unresolved, report.codes[bad].cpu().tolist())   # (the creatures' real REM2D_ERR_* bits of the wide run)
         return fit
-    if on_error == "fallback":
-        fit, bad = run_episode_masked(env, max_steps, chunk, compact, fallback=True)
-        env.last_unresolved = torch.nonzero(bad).flatten().cpu().tolist()
-        if bool(bad.any()):
-            idx = torch.nonzero(bad).flatten().cpu().tolist()
-            raise SolverOverflow(idx, env.last_error_codes[bad].cpu().tolist())   # (the creatures' real REM2D_ERR_* bits of the wide run)
-        return fit
+    env.last_episode = None
     _episode(env, max_steps, chunk, compact)
     check_errors(env, on_error)   # (REM2D_ERR_HANDOVER raises HandoverError in "raise" and "warn"; so does env.fitness below)
     return env.fitness.clone()
@@ -244,48 +255,21 @@ def run_episode(env, max_steps=EPISODE_CAP, chunk=100, on_error="fallback", comp
 def evaluate_population(individuals, tree_depth=None, env=None, max_steps=EPISODE_CAP, workers=None, on_error="fallback",
                         **env_kw):
     """Batched stand-in for ``toolbox.map(toolbox.evaluate, population)``: list of floats.
-    The genotype -> phenotype step runs on ``workers`` host processes (encode.encode_population).
+    The genotype -> phenotype step runs natively on ``workers`` host threads (encode.encode_native).
     on_error: what to do when a creature overflowed the engine's contact capacity ("fallback": re-evaluate it in the
     wide build and raise only if even that overflows, the default | "penalty": the same without ever raising, see
     run_episode | "raise" | "warn" | "ignore")."""
-    from .encode import encode_population
+    from .encode import encode_native
     from .env import BatchedModular2D
     own = env is None
     if own:
-        # fitness is all that leaves this function: creatures whose fitness is final need no more steps
-        env_kw.setdefault("flags", _lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN)
+        env_kw.setdefault("flags", EVAL_FLAGS)
         env = BatchedModular2D(**env_kw)
-    env.trees = env.robots = None
-    from .encodings.lsystem import LSystem
-    if individuals and all(type(ind.genome) is LSystem for ind in individuals) and \
-            len({(ind.genome.treeDepth, ind.genome.maxModules) for ind in individuals}) == 1:
-        # L-system genomes: native compiler (no fork, ~30 us per individual incl. reading the objects)
-        from .encode import encode_lsystem_native
-        batches = encode_lsystem_native(individuals, n_threads=workers or 0)
-    elif individuals and all(_is_ff_network(ind.genome) for ind in individuals) and \
-            len({ind.genome.maxModules for ind in individuals}) == 1:
-        # network genomes (feed-forward CPPN): the NN queries that grow the tree run natively as well
-        from .encode import encode_network_native
-        depths = {tree_depth} if tree_depth is not None else {ind.tree_depth for ind in individuals}
-        if len(depths) == 1:
-            batches = encode_network_native(individuals, depths.pop(), n_threads=workers or 0)
-        else:   # individuals with their own tree depths: the node-by-node compiler expresses each with its own
-            from .encode import encode_trees_native
-            batches = encode_trees_native(individuals, tree_depth, n_threads=workers or 0)
-    else:
-        # every other encoding: python hands out the phenotype trees, the native compiler builds the creatures
-        from .encode import encode_trees_native
-        batches = encode_trees_native(individuals, tree_depth, n_threads=workers or 0)
-    env._upload(batches, len(individuals))
+    env.reset_batches(encode_native(individuals, tree_depth, n_threads=workers or 0), len(individuals))
     fit = run_episode(env, max_steps, on_error=on_error).cpu().tolist()
     if own:
         env.close()
     return fit
-
-
-def _is_ff_network(genome):
-    from .encodings.network import FeedForwardCPPN, NNEncoding
-    return type(genome) is NNEncoding and type(genome.nn_g) is FeedForwardCPPN
 
 
 def shard_range(n, rank, world_size):
@@ -357,38 +341,119 @@ def all_gather_fitness(local, n_total, group=None, flags=None, index=None):
     return fit, bad
 
 
+def _evaluate_sharded(n_total, run_local, cost, group, device, on_error):
+    """The protocol of a sharded evaluation, once: deal (``cost``: a static key per individual, shard_balanced) or cut (None:
+    contiguous blocks, shard_range) the shards, evaluate this rank's with ``run_local(population indices, int64 array) -> fitness``
+    (or ``-> (fitness, unresolved mask)``: run_episode_masked), one all-gather, the verdict after it.
+    Returns (fitness [n_total] float64 tensor in population order, unresolved indices, predicted cost per rank | None).
+    The mask rides in the fitness all-gather: a rank with a creature that has no valid fitness does not raise before the
+    collective (the others would wait in it for ever).  After it every rank holds the same mask: every rank raises SolverOverflow
+    in step, or (on_error="penalty") the creatures get UNRESOLVED_FITNESS on every rank alike and every rank warns."""
+    import torch.distributed as dist
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    index = shard_cost = None
+    if cost is not None:
+        index = shard_balanced(cost, world)
+        shard_cost = shard_costs(cost, index)
+        mine = index[rank][index[rank] >= 0]
+    else:
+        mine = np.arange(*shard_range(n_total, rank, world))
+    local, mask = run_local(mine), None
+    if isinstance(local, tuple):
+        local, mask = local
+    local = torch.as_tensor(local, dtype=torch.float64, device=device)
+    if mask is None:
+        mask = torch.zeros(local.numel(), dtype=torch.bool)
+    fit, bad = all_gather_fitness(local, n_total, group, flags=mask, index=index)
+    unresolved = []
+    if bool(bad.any()):
+        if on_error != "penalty":
+            idx = torch.nonzero(bad).flatten().cpu().tolist()
+            raise SolverOverflow(idx, [_lib.ERR_SOLVER_OVERFLOW] * len(idx))
+        unresolved = apply_penalty(fit, bad, warn=True)
+    return fit, unresolved, shard_cost
+
+
 def evaluate_population_sharded(n_total, local_eval, group=None, device=None, on_error="raise", cost=None):
     """Shard [0, n_total) over the job's ranks, evaluate the local block with
     ``local_eval(lo, hi) -> tensor[hi-lo]`` (or ``-> (tensor, unresolved mask)``, run_episode_masked) and all-gather.
     cost (optional, [n_total], the same on every rank): a static cost key per individual -- the shards are then dealt by
     shard_balanced instead of cut contiguously, ``local_eval(indices)`` gets the rank's population indices (int64 array) and
-    ``evaluate_population_sharded.last_shard_cost`` holds the predicted cost per rank; the result is in population order.
+    ``evaluate_population_sharded.last_shard_cost`` holds the predicted cost per rank (None after a call without ``cost``); the
+    result is in population order.
     Returns fitness[n_total] (float64).  The mask rides in the same collective, so every rank learns about every rank's
     unresolved creatures AFTER it: with on_error="raise" (the library default -- the reference has no contact cap and would
     have produced a fitness) every rank raises SolverOverflow in step; with "penalty" (an EA loop's opt-in) they get
     UNRESOLVED_FITNESS on every rank alike, every rank warns, ``evaluate_population_sharded.last_unresolved`` lists them and
     the job goes on."""
-    import torch.distributed as dist
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    index = None
-    if cost is not None:
-        index = shard_balanced(cost, world)
-        evaluate_population_sharded.last_shard_cost = shard_costs(cost, index)
-        local = local_eval(index[rank][index[rank] >= 0])
-    else:
-        lo, hi = shard_range(n_total, rank, world)
-        local = local_eval(lo, hi)
-    mask = None
-    if isinstance(local, tuple):
-        local, mask = local
-    local = torch.as_tensor(local, dtype=torch.float64, device=device if device is not None else None)
-    if mask is None:
-        mask = torch.zeros(local.numel(), dtype=torch.bool, device=local.device)
-    fit, bad = all_gather_fitness(local, n_total, group, flags=torch.as_tensor(mask, device=local.device), index=index)
-    evaluate_population_sharded.last_unresolved = []
-    if bool(bad.any()):
-        if on_error != "penalty":
-            idx = torch.nonzero(bad).flatten().cpu().tolist()
-            raise SolverOverflow(idx, [_lib.ERR_SOLVER_OVERFLOW] * len(idx))
-        evaluate_population_sharded.last_unresolved = apply_penalty(fit, bad, warn=True)
+    run_local = local_eval
+    if cost is None:   # (a contiguous block as its two ends; an empty one lies at the population's end: shard_range)
+        def run_local(idx):
+            return local_eval(int(idx[0]), int(idx[-1]) + 1) if len(idx) else local_eval(n_total, n_total)
+    fit, evaluate_population_sharded.last_unresolved, evaluate_population_sharded.last_shard_cost = _evaluate_sharded(
+        n_total, run_local, cost, group, device, on_error)
     return fit
+
+
+class sharded_evaluator:
+    """evaluate(population) for a torch.distributed job (one process per GPU): every rank holds the whole
+    population as arrays (selection and mutation are replicated from a shared seed, so no genome ever crosses a
+    rank boundary), expresses and evaluates only its share with ``local_eval(population of that share) -> fitness``
+    (or ``-> (fitness, unresolved mask)``: gpu_evaluator(masked=True)) and the ranks exchange one all-gather of float64
+    fitness (REM2D_main.py:256-267 pool.map).  Returns the fitness in population order as float64 numpy.
+
+    balance (default): the reference's pool balances dynamically (pool.map hands out chunks as workers finish); a static
+    contiguous cut does not, and a generation ends with its slowest rank.  Every rank therefore computes the same deal from the
+    arrays it holds anyway -- the individuals in descending order of body count (a native expression pass, population.body_counts)
+    dealt snake-wise over the ranks, shard_balanced -- and the fitness comes back in population order through the same
+    single all-gather.  ``last_shard_cost`` = the predicted cost (bodies) per rank.  balance=False: contiguous blocks.
+
+    on_error: what to do about creatures without a valid fitness (beyond even the wide build's contact slots -- Box2D has
+    no such cap, so the reference would have produced a number).  "raise" (the library default): every rank raises
+    SolverOverflow AFTER the collective, in step.  "penalty" (what an EA loop opts into so that one out-of-domain creature
+    does not abort a run): UNRESOLVED_FITNESS on every rank alike, a warning on EVERY rank, the indices in ``last_unresolved``
+    and kept per call in ``unresolved_log`` (a list that grows by one entry per call: a long run cannot lose them)."""
+
+    def __init__(self, local_eval, group=None, device=None, on_error="raise", balance=True, n_threads=0):
+        self.local_eval, self.group, self.device, self.on_error = local_eval, group, device, on_error
+        self.balance, self.n_threads = balance, n_threads
+        self.last_unresolved, self.unresolved_log, self.last_shard_cost = [], [], None
+
+    def __call__(self, pop):
+        def run_local(idx):
+            return self.local_eval(pop.select(idx)) if len(idx) else np.zeros(0, dtype=np.float64)
+        fit, self.last_unresolved, self.last_shard_cost = _evaluate_sharded(
+            len(pop), run_local, pop.body_counts(self.n_threads) if self.balance else None, self.group, self.device, self.on_error)
+        self.unresolved_log.append(list(self.last_unresolved))
+        return fit.cpu().numpy().astype(np.float64)
+
+
+class gpu_evaluator:
+    """local_eval for sharded_evaluator / evaluate for run_generations on one GPU: native expression, upload,
+    whole episodes (evaluate()'s rule), fitness as float64 numpy.  Creatures that overflow the default build's contact
+    slots are re-evaluated in the wide build (reevaluate_wide); one that overflows even that
+    raises SolverOverflow (on_error="fallback", the library default: Box2D has no contact cap, so there is no fitness the
+    reference would have given) or, if the caller opts in with on_error="penalty" (the EA loops do: one out-of-domain
+    creature does not abort a generation), gets UNRESOLVED_FITNESS, a warning, and an entry in
+    ``last_unresolved`` / ``unresolved_log`` (one list per call) -- or, with masked=True
+    (what a sharded job wants), comes back in a second array ``(fitness, unresolved)`` so that the verdict is taken after
+    the job's collective."""
+
+    def __init__(self, env=None, max_steps=None, n_threads=0, masked=False, on_error="fallback"):
+        self.env, self.n_threads, self.masked, self.on_error = env, n_threads, masked, on_error
+        self.max_steps = max_steps if max_steps is not None else EPISODE_CAP
+        self.last_unresolved, self.unresolved_log = [], []
+
+    def __call__(self, pop):
+        if self.env is None:
+            from .env import BatchedModular2D
+            self.env = BatchedModular2D(flags=EVAL_FLAGS)
+        self.env.reset_batches(pop.compile(self.n_threads), len(pop))
+        if self.masked:
+            fit, bad = run_episode_masked(self.env, self.max_steps)
+            return fit.cpu().numpy(), bad.cpu().numpy()
+        fit = run_episode(self.env, self.max_steps, on_error=self.on_error).cpu().numpy()
+        report = self.env.last_episode   # (None after the modes that judge without a second attempt)
+        self.last_unresolved = list(report.unresolved) if report is not None else []
+        self.unresolved_log.append(list(self.last_unresolved))
+        return fit

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import encode
 from .controller import Controller
+from .evaluate import gpu_evaluator, sharded_evaluator  # noqa: F401  (their home now; still importable from here)
 from .modules import Circular2D, Standard2D
 
 BOX, CIRCLE = 1, 2
@@ -96,19 +97,9 @@ class LSystemPopulation:
         """``Individual.random`` for n individuals: default module sizes (simple_module.py:41-43,
         circular_module.py:44-46), uniform controllers (m_controller.py:9-15), random rules (LSystem.py:30-45)."""
         T = n_box + n_circle
-        a = dict(mod_shape=np.empty((n, T), np.int32))
-        a["mod_shape"][:, :n_box], a["mod_shape"][:, n_box:] = BOX, CIRCLE
-        box = a["mod_shape"] == BOX
-        a["mod_width"] = np.where(box, 0.2, 0.0)
-        a["mod_height"] = np.where(box, 0.8, 0.0)
-        a["mod_radius"] = np.where(box, 0.0, 0.25)
-        a["mod_angle"] = np.full((n, T), math.pi / 2)
-        a["mod_torque"] = np.full((n, T), 50.0)
-        a["ctl_amp"] = rng.uniform(0, Controller.MAX_AMP, (n, T))
-        a["ctl_phase"] = rng.uniform(-Controller.MAX_PHASE, Controller.MAX_PHASE, (n, T))
-        a["ctl_freq"] = rng.uniform(-Controller.MAX_FREQ, Controller.MAX_FREQ, (n, T))
-        a["ctl_offset"] = rng.uniform(-Controller.MAX_OFFSET, Controller.MAX_OFFSET, (n, T))
-        max_children = np.where(box, 3, 0)
+        a = default_module_arrays(n, n_box, n_circle)
+        a.update(random_controller_arrays((n, T), rng))
+        max_children = np.where(a["mod_shape"] == BOX, 3, 0)
         a["rule_n"] = (rng.integers(0, 4, (n, T)) * (max_children > 0)).astype(np.int32)   # randint(0, max_children)
         # sites without replacement: a random permutation of (left, right, top) per rule
         a["rule_site"] = np.argsort(rng.random((n, T, 3)), axis=2).astype(np.int32)
@@ -159,9 +150,13 @@ class LSystemPopulation:
         return out
 
     # ------------------------------------------------------------------ variation
+    def _like(self, arrays):
+        """A population of this one's type and parameters around `arrays`."""
+        return LSystemPopulation(arrays, self.tree_depth, self.max_modules)
+
     def select(self, idx):
         """Clone the individuals `idx` (tools.selTournament + toolbox.clone, REM2D_main.py:283-285)."""
-        return LSystemPopulation(_take(self.a, np.asarray(idx, dtype=np.int64)), self.tree_depth, self.max_modules)
+        return self._like(_take(self.a, np.asarray(idx, dtype=np.int64)))
 
     def _mutate_modules(self, morph_rate, rate, sigma, rng):
         mutate_module_arrays(self.a, morph_rate, rate, sigma, rng)
@@ -169,10 +164,7 @@ class LSystemPopulation:
     def mutate(self, morph_rate, rate, sigma, rng):
         """LSystem.mutate (LSystem.py:174-179): every module, then every rule (whose mutate starts with its
         module once more, LSystem.py:71), rule growth / shrinkage with probability morph_rate each."""
-        if len(self) >= _MUTATE_PARALLEL_FROM:
-            return _mutate_in_blocks(self, lambda a: LSystemPopulation(a, self.tree_depth, self.max_modules), rng,
-                                     morph_rate, rate, sigma)
-        self._mutate_serial(morph_rate, rate, sigma, rng)
+        _mutate_rows(self, rng, morph_rate, rate, sigma)
 
     def _mutate_serial(self, morph_rate, rate, sigma, rng):
         a = self.a
@@ -245,100 +237,6 @@ def run_generations(pop, n_generations, evaluate, rng, morph_rate=0.01, rate=0.0
     return pop, fit, history
 
 
-def sharded_evaluator(local_eval, group=None, device=None, on_error="raise", balance=True, n_threads=0):
-    """evaluate(population) for a torch.distributed job (one process per GPU): every rank holds the whole
-    population as arrays (selection and mutation are replicated from a shared seed, so no genome ever crosses a
-    rank boundary), expresses and evaluates only its contiguous block ``[lo, hi)`` with
-    ``local_eval(LSystemPopulation block) -> fitness[hi-lo]`` and the ranks exchange one all-gather of float64
-    fitness (REM2D_main.py:256-267 pool.map).
-
-    balance (default): the reference's pool balances dynamically (pool.map hands out chunks as workers finish); a static
-    contiguous cut does not, and a generation ends with its slowest rank.  Every rank therefore computes the same deal from the
-    arrays it holds anyway -- the individuals in descending order of body count (a native expression pass, population.body_counts)
-    dealt snake-wise over the ranks, evaluate.shard_balanced -- and the fitness comes back in population order through the same
-    single all-gather.  ``evaluate.last_shard_cost`` = the predicted cost (bodies) per rank.  balance=False: contiguous blocks.
-
-    on_error: what to do about creatures without a valid fitness (beyond even the wide build's contact slots -- Box2D has
-    no such cap, so the reference would have produced a number).  "raise" (the library default): every rank raises
-    SolverOverflow AFTER the collective, in step.  "penalty" (what an EA loop opts into so that one out-of-domain creature
-    does not abort a run): evaluate.UNRESOLVED_FITNESS on every rank alike, a warning on EVERY rank, and the indices kept per
-    call in ``evaluate.unresolved_log`` (a list that grows by one entry per call: a long run cannot lose them)."""
-    import torch
-    import torch.distributed as dist
-    from .evaluate import all_gather_fitness, shard_balanced, shard_costs, shard_range
-
-    def evaluate(pop):
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-        index = None
-        if balance:
-            cost = pop.body_counts(n_threads)
-            index = shard_balanced(cost, world)
-            mine = index[rank][index[rank] >= 0]
-            evaluate.last_shard_cost = shard_costs(cost, index)
-        else:
-            lo, hi = shard_range(len(pop), rank, world)
-            mine = np.arange(lo, hi)
-        local = local_eval(pop.select(mine)) if len(mine) else np.zeros(0, dtype=np.float64)
-        mask = None
-        if isinstance(local, tuple):     # (fitness, unresolved mask): gpu_evaluator(masked=True)
-            local, mask = local
-        local = torch.as_tensor(np.asarray(local, dtype=np.float64), device=device)
-        mask = torch.zeros(local.numel(), dtype=torch.bool) if mask is None else torch.as_tensor(np.asarray(mask))
-        # the mask rides in the fitness all-gather: a rank with a creature that has no valid fitness does not raise
-        # before the collective (the others would wait in it for ever).  After it every rank holds the same mask: the
-        # creatures get the defined penalty on every rank alike (on_error="penalty": the generation goes on, the indices
-        # are kept in evaluate.last_unresolved) or every rank raises in step (on_error="raise")
-        fit, bad = all_gather_fitness(local, len(pop), group, flags=mask.to(local.device), index=index)
-        evaluate.last_unresolved = []
-        if bool(bad.any()):
-            from .evaluate import SolverOverflow, apply_penalty
-            from . import _lib
-            if on_error != "penalty":
-                idx = torch.nonzero(bad).flatten().cpu().tolist()
-                raise SolverOverflow(idx, [_lib.ERR_SOLVER_OVERFLOW] * len(idx))
-            evaluate.last_unresolved = apply_penalty(fit, bad, warn=True)
-        evaluate.unresolved_log.append(list(evaluate.last_unresolved))
-        return fit.cpu().numpy().astype(np.float64)
-    evaluate.last_unresolved = []
-    evaluate.unresolved_log = []
-    evaluate.last_shard_cost = None
-    return evaluate
-
-
-def gpu_evaluator(env=None, max_steps=None, n_threads=0, masked=False, on_error="fallback"):
-    """local_eval for sharded_evaluator / evaluate for run_generations on one GPU: native expression, upload,
-    whole episodes (evaluate()'s rule), fitness as float64 numpy.  Creatures that overflow the default build's contact
-    slots are re-evaluated in the wide build (evaluate.reevaluate_wide); one that overflows even that gets
-    raises SolverOverflow (on_error="fallback", the library default: Box2D has no contact cap, so there is no fitness the
-    reference would have given) or, if the caller opts in with on_error="penalty" (the EA loops do: one out-of-domain
-    creature does not abort a generation), gets evaluate.UNRESOLVED_FITNESS, a warning, and an entry in
-    ``evaluate.last_unresolved`` / ``evaluate.unresolved_log`` (one list per call) -- or, with masked=True
-    (what a sharded job wants), comes back in a second array ``(fitness, unresolved)`` so that the verdict is taken after
-    the job's collective."""
-    from .env import BatchedModular2D
-    from .evaluate import EPISODE_CAP, run_episode, run_episode_masked
-    holder = {"env": env}
-
-    def evaluate(pop):
-        if holder["env"] is None:
-            from . import _lib
-            holder["env"] = BatchedModular2D(flags=_lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN)
-        e = holder["env"]
-        e.trees = e.robots = None
-        e._upload(pop.compile(n_threads), len(pop))
-        cap = max_steps if max_steps is not None else EPISODE_CAP
-        if masked:
-            fit, bad = run_episode_masked(e, cap)
-            return fit.cpu().numpy(), bad.cpu().numpy()
-        fit = run_episode(e, cap, on_error=on_error).cpu().numpy()
-        evaluate.last_unresolved = list(getattr(e, "last_unresolved", []))
-        evaluate.unresolved_log.append(list(evaluate.last_unresolved))
-        return fit
-    evaluate.last_unresolved = []
-    evaluate.unresolved_log = []
-    return evaluate
-
-
 # ------------------------------------------------------------------------------------------------------------------------
 # Array populations of the other two encodings (round 5).  Same contract as LSystemPopulation: the reference's operators
 # element-wise with a numpy generator -- the same distributions, not the reference's random stream (the object genomes in
@@ -349,18 +247,20 @@ _MUTATE_BLOCKS = 16          # row blocks of a big population's mutation (a cons
 _MUTATE_PARALLEL_FROM = 32768
 
 
-def _mutate_in_blocks(pop, make, rng, *args):
-    """pop.mutate(*args, rng) for a big population: _MUTATE_BLOCKS contiguous row blocks, each with a generator spawned from `rng`
-    (numpy.random.Generator.spawn: independent streams, reproducible from the seed), mutated side by side on a thread pool --
-    numpy releases the GIL inside its loops and generators -- and written back.  make(arrays) -> a population of pop's type."""
-    from concurrent.futures import ThreadPoolExecutor
+def _mutate_rows(pop, rng, *args):
+    """pop._mutate_serial(*args, rng); for a big population in _MUTATE_BLOCKS contiguous row blocks, each with a generator spawned
+    from `rng` (numpy.random.Generator.spawn: independent streams, reproducible from the seed), mutated side by side on a thread
+    pool -- numpy releases the GIL inside its loops and generators -- and written back."""
     n = len(pop)
+    if n < _MUTATE_PARALLEL_FROM:
+        return pop._mutate_serial(*args, rng)
+    from concurrent.futures import ThreadPoolExecutor
     edges = np.linspace(0, n, _MUTATE_BLOCKS + 1).astype(np.int64)
     gens = rng.spawn(_MUTATE_BLOCKS)
 
     def work(b):
         lo, hi = int(edges[b]), int(edges[b + 1])
-        sub = make({k: v[lo:hi].copy() for k, v in pop.a.items()})
+        sub = pop._like({k: v[lo:hi].copy() for k, v in pop.a.items()})
         sub._mutate_serial(*args, gens[b])
         for k, v in sub.a.items():
             pop.a[k][lo:hi] = v
@@ -408,16 +308,16 @@ class NetworkPopulation:
     def from_genomes(cls, genomes, tree_depth=7):
         return cls(encode.network_genome_arrays(genomes), tree_depth, genomes[0].maxModules)
 
+    def _like(self, arrays):
+        return NetworkPopulation(arrays, self.tree_depth, self.max_modules)
+
     def select(self, idx):
-        return NetworkPopulation(_take(self.a, np.asarray(idx, dtype=np.int64)), self.tree_depth, self.max_modules)
+        return self._like(_take(self.a, np.asarray(idx, dtype=np.int64)))
 
     def mutate(self, morph_rate, rate, sigma, rng, weight_rate=0.2, weight_sigma=0.3):
         """NNEncoding.mutate (Network_Encoding.py:142-152): the network's own mutation (FeedForwardCPPN.mutate: every weight
         with probability 0.2 += gauss(0, 0.3)), then every module prototype."""
-        if len(self) >= _MUTATE_PARALLEL_FROM:
-            return _mutate_in_blocks(self, lambda a: NetworkPopulation(a, self.tree_depth, self.max_modules), rng,
-                                     morph_rate, rate, sigma, weight_rate, weight_sigma)
-        self._mutate_serial(morph_rate, rate, sigma, weight_rate, weight_sigma, rng)
+        _mutate_rows(self, rng, morph_rate, rate, sigma, weight_rate, weight_sigma)
 
     def _mutate_serial(self, morph_rate, rate, sigma, weight_rate, weight_sigma, rng):
         for k in ("w1", "w2"):
@@ -501,9 +401,11 @@ class DirectPopulation:
         a["parent"][pad] = -1
         return cls(a, g0.maxModules, g0.maxDepth)
 
+    def _like(self, arrays):
+        return DirectPopulation(arrays, self.max_modules, self.max_depth, self.n_box, self.n_circle)
+
     def select(self, idx):
-        return DirectPopulation(_take(self.a, np.asarray(idx, dtype=np.int64)), self.max_modules, self.max_depth,
-                                self.n_box, self.n_circle)
+        return self._like(_take(self.a, np.asarray(idx, dtype=np.int64)))
 
     # ---------------------------------------------------------------- structure helpers (vectorised over individuals)
     def depths(self):

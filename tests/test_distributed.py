@@ -131,6 +131,13 @@ def _ea_worker(rank, world, port, out_dir):
     np.save(os.path.join(out_dir, "ea_cost%d.npy" % rank), ev.last_shard_cost)
     np.save(os.path.join(out_dir, "ea_fit%d.npy" % rank), fit)
     np.save(os.path.join(out_dir, "ea_angle%d.npy" % rank), pop.a["mod_angle"])
+    # the two adapters over the one sharded protocol: the same population and the same local_eval through
+    # evaluate_population_sharded, dealt by the same key -- the same fitness and the same predicted costs, on every rank
+    from gym_rem2d_amd.evaluate import evaluate_population_sharded
+    one = ev(pop)
+    two = evaluate_population_sharded(len(pop), lambda idx: local_eval(pop.select(idx)), cost=pop.body_counts(1))
+    assert one.dtype == np.float64 and one.shape == (301,) and (one == two.numpy()).all()
+    assert (ev.last_shard_cost == evaluate_population_sharded.last_shard_cost).all()
     dist.barrier()
     dist.destroy_process_group()
 

@@ -388,7 +388,7 @@ def test_creature_beyond_the_wide_build_gets_the_defined_penalty(need_gpu, oracl
     """Box2D has no contact cap (Modular2DEnv.py:634); the engine has two tiers (24 / 6, then 32 / 12 pair / solver slots per
     body).  A hand-built 7.6 m plank -- seven times the largest box the reference's classes can produce -- rests on more
     than 12 terrain edges: beyond both.  With on_error="penalty" (what the EA loops use) the episode completes, the plank
-    gets evaluate.UNRESOLVED_FITNESS and is named in ``env.last_unresolved``; every other creature gets the oracle's
+    gets evaluate.UNRESOLVED_FITNESS and is named in ``env.last_episode.unresolved``; every other creature gets the oracle's
     fitness bit for bit, and the oracle -- asked how many touching manifolds its bodies held while the fitness was open --
     agrees on WHO is beyond the tiers, i.e. on every fitness under the same rule.  on_error="fallback" still raises."""
     import pytest
@@ -407,7 +407,7 @@ def test_creature_beyond_the_wide_build_gets_the_defined_penalty(need_gpu, oracl
     env.reset_morphology(m)
     with pytest.warns(UserWarning, match="UNRESOLVED_FITNESS"):
         fit = run_episode(env, max_steps=150, on_error="penalty")
-    assert env.last_unresolved == [2] and env.last_overflow == [2]
+    assert env.last_episode.unresolved == [2] and env.last_episode.overflow == [2]
     assert np.array_equal(fit.cpu().numpy(), want) and ref["fitness"][2] != UNRESOLVED_FITNESS
     env.reset_morphology(m)
     with pytest.raises(SolverOverflow):
@@ -440,7 +440,7 @@ def test_solver_overflow_falls_back_to_the_wide_build(need_gpu, oracle, flat_ter
     env = BatchedModular2D(flat=True)
     env.reset_morphology(m)
     fit = run_episode(env, max_steps=150)                                   # default: on_error="fallback"
-    assert env.last_overflow == [2]
+    assert env.last_episode.overflow == [2]
     assert np.array_equal(fit.cpu().numpy(), ref["fitness"])
     env.reset_morphology(m)
     with pytest.raises(SolverOverflow) as ei:
@@ -660,6 +660,6 @@ def test_five_joints_on_one_body_fall_back_to_the_wide_build(need_gpu, oracle, f
     assert err.tolist() == [_lib.ERR_SOLVER_OVERFLOW] * 8 + [0] * 4
     env.reset_morphology(m)
     fit = run_episode(env, max_steps=300)
-    assert env.last_overflow == list(range(8)) and env.last_unresolved == []
+    assert env.last_episode.overflow == list(range(8)) and env.last_episode.unresolved == []
     assert np.array_equal(fit.cpu().numpy(), ref["fitness"])
     env.close()

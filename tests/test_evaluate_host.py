@@ -69,7 +69,8 @@ def test_handover_goes_to_per_step_launches_capacity_to_the_wide_build(monkeypat
     # build; creature 3's capacity bit came from a state that was not to be trusted and is gone with the re-run
     assert calls == [((False, True), [1, 3]), ((True, False), [2])]
     assert fit.tolist() == [0.0, 101.0, 110.0, 101.0, 4.0]
-    assert env.last_handover == [1, 3] and env.last_overflow == [2] and env.last_unresolved == []
+    report = env.last_episode
+    assert report.handover == [1, 3] and report.overflow == [2] and report.unresolved == []
     assert env.on_handover == "raise" and env.handover_failures() == 0          # policy restored, counter consumed
 
 
@@ -90,7 +91,7 @@ def test_penalty_mode_never_scores_a_handover(monkeypatch):
     _patch_reevaluate(monkeypatch, {(False, True): 0})
     with pytest.warns(UserWarning, match="per-step launches"):
         fit = evaluate.run_episode(env, max_steps=10, chunk=10, on_error="penalty")
-    assert fit.tolist() == [101.0, 101.0, 2.0] and env.last_unresolved == []
+    assert fit.tolist() == [101.0, 101.0, 2.0] and env.last_episode.unresolved == []
     assert evaluate.UNRESOLVED_FITNESS not in fit.tolist()[:2]
 
 
@@ -101,6 +102,36 @@ def test_handover_that_survives_per_step_launches_raises(monkeypatch):
     with pytest.warns(UserWarning):
         with pytest.raises(_lib.HandoverError, match="even on per-step launches"):
             evaluate.run_episode(env, max_steps=10, chunk=10)
+
+
+def test_strict_modes_leave_no_report():
+    """ "raise" / "warn" / "ignore" judge the default build's flags without a second attempt: an earlier episode's report is gone."""
+    env = FakeEnv([0, 0])
+    evaluate.run_episode(env, max_steps=10, chunk=10, on_error="penalty")
+    assert env.last_episode.codes.tolist() == [0, 0] and env.last_episode[1:] == ([], [], [])
+    for mode in ("raise", "warn", "ignore"):
+        env.last_episode = "an earlier report"
+        assert evaluate.run_episode(env, max_steps=10, chunk=10, on_error=mode).tolist() == [0.0, 1.0]
+        assert env.last_episode is None
+
+
+def test_an_upload_clears_the_report(monkeypatch):
+    """BatchedModular2D declares the report and _upload resets it (the stand-in world of tests/test_launch_policy.py: no device)."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import record_launch_plans as R
+    from gym_rem2d_amd import env as envmod
+    assert envmod.BatchedModular2D().last_episode is None
+    seen, upload = [], envmod.BatchedModular2D._upload
+
+    def spy(self, batches, n_envs):
+        before = self.last_episode
+        upload(self, batches, n_envs)
+        seen.append((before, self.last_episode))
+    monkeypatch.setattr(envmod.BatchedModular2D, "_upload", spy)
+    R.run_case(envmod, R.case("report", "outputs", [(12, 8, True)], attrs={"last_episode": "the previous population's"}))
+    assert seen == [("the previous population's", None)]
 
 
 def test_strict_modes_name_the_handover():

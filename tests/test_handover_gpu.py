@@ -77,7 +77,8 @@ def test_forced_handover_failure_is_flagged_named_and_recovered(need_gpu, oracle
     with pytest.warns(UserWarning, match="REM2D_ERR_HANDOVER"):
         fit = run_episode(env, max_steps=2500)
     assert np.array_equal(fit.cpu().numpy(), ref)
-    assert len(env.last_handover) > 0 and env.last_overflow == [] and env.last_unresolved == []
+    report = env.last_episode
+    assert len(report.handover) > 0 and report.overflow == [] and report.unresolved == []
     # (4) strict modes name it; penalty mode resolves it instead of penalising it
     env.reset_specs(specs)
     with pytest.raises(HandoverError):
@@ -86,7 +87,7 @@ def test_forced_handover_failure_is_flagged_named_and_recovered(need_gpu, oracle
     env.handover_failures(clear=True)
     with pytest.warns(UserWarning, match="REM2D_ERR_HANDOVER"):
         fit = run_episode(env, max_steps=2500, on_error="penalty")
-    assert np.array_equal(fit.cpu().numpy(), ref) and env.last_unresolved == []
+    assert np.array_equal(fit.cpu().numpy(), ref) and env.last_episode.unresolved == []
     env.close()
 
     # and without the fault: no warning, no flag, the same fitness
@@ -95,7 +96,7 @@ def test_forced_handover_failure_is_flagged_named_and_recovered(need_gpu, oracle
     with warnings.catch_warnings():
         warnings.simplefilter("error")
         fit = run_episode(env, max_steps=2500)
-    assert np.array_equal(fit.cpu().numpy(), ref) and env.last_handover == [] and env.handover_failures() == 0
+    assert np.array_equal(fit.cpu().numpy(), ref) and env.last_episode.handover == [] and env.handover_failures() == 0
     env.close()
 
 

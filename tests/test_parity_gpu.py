@@ -668,13 +668,13 @@ def test_full_size_config5_generation_share(gpu, oracle, rough_terrain):
     env = BatchedModular2D(flags=_lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN)
     env._upload(pop.compile(0), N)
     fit = run_episode(env, max_steps=cap).cpu().numpy()      # overflowing creatures are re-evaluated in the wide build
-    n_fallback = len(env.last_overflow)
+    n_fallback = len(env.last_episode.overflow)
     env.close()
     assert fit.shape == (N,) and np.isfinite(fit).all() and (fit > 0).mean() > 0.5
     sample = rng.choice(N, N // 100, replace=False)
     ot = oracle_terrain(oracle, rough_terrain)
     ref = np.zeros(N)
-    fell_back = np.asarray(sorted(set(env.last_overflow) - set(sample.tolist())), dtype=np.int64)
+    fell_back = np.asarray(sorted(set(env.last_episode.overflow) - set(sample.tolist())), dtype=np.int64)
     sample = np.concatenate([sample, fell_back])
     for m, idx in pop.select(sample).compile(0):
         r = oracle.batch_run(ot, m.as_dict(), cap, n_threads=8, flags=oracle.FLAG_CONTINUOUS)

@@ -244,3 +244,62 @@ def test_sharded_generations_of_the_direct_and_network_populations_gloo(tmp_path
             assert np.array_equal(np.load(os.path.join(str(tmp_path), "%s_fit%d.npy" % (name, r))), fit), name
             cost = np.load(os.path.join(str(tmp_path), "%s_cost%d.npy" % (name, r)))
             assert cost.sum() == pop.body_counts(1).sum() and abs(cost[0] - cost[1]) <= 0.05 * cost.mean(), (name, cost)
+
+
+def _config5_worker(rank, world, port, out_dir):
+    import json
+    import os
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    import __graft_entry__ as g
+    g.build()
+    from gym_rem2d_amd.population import LSystemPopulation, gpu_evaluator, sharded_evaluator
+    pop = LSystemPopulation.random(96, np.random.default_rng(21), max_modules=15)
+    for name, balance in (("balanced", True), ("contiguous", False)):
+        ev = sharded_evaluator(gpu_evaluator(masked=True, max_steps=400), balance=balance, n_threads=1)
+        np.save(os.path.join(out_dir, name + "_fit.npy"), ev(pop))
+        cost = ev.last_shard_cost
+        with open(os.path.join(out_dir, name + ".json"), "w") as f:
+            json.dump({"last_unresolved": ev.last_unresolved, "unresolved_log": ev.unresolved_log,
+                       "last_shard_cost": None if cost is None else np.asarray(cost).tolist()}, f)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_sharded_gpu_evaluation_equals_the_unsharded_one(tmp_path, built):
+    """Config 5's composition, sharded_evaluator(gpu_evaluator(masked=True)), at world size 1 over gloo (a fresh child process, as a
+    rank of a job is): dealt and contiguous shards give the fitness of the unsharded gpu_evaluator, value for value, report nothing
+    unresolved, log one entry per call, and the predicted cost of the one rank is the population's bodies.  96 creatures of up to 15
+    modules: several lane buckets and, in worlds with REM2D_FLAG_SKIP_FROZEN, the compaction path."""
+    import json
+    import os
+    import socket
+    import torch
+    import torch.multiprocessing as mp
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from gym_rem2d_amd.population import gpu_evaluator
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    mp.spawn(_config5_worker, args=(1, port, str(tmp_path)), nprocs=1, join=True)
+    pop = LSystemPopulation.random(96, np.random.default_rng(21), max_modules=15)
+    assert len(pop.compile(1)) > 1
+    ev = gpu_evaluator(max_steps=400, on_error="penalty")
+    want = ev(pop)
+    assert ev.last_unresolved == [] and ev.unresolved_log == [[]] and len(set(want.tolist())) > 10
+    for name in ("balanced", "contiguous"):
+        got = np.load(os.path.join(str(tmp_path), name + "_fit.npy"))
+        print(name, "sharded != unsharded for", int((got != want).sum()), "of", len(want))
+        assert got.dtype == np.float64 and got.shape == want.shape and (got == want).all(), name
+        with open(os.path.join(str(tmp_path), name + ".json")) as f:
+            rec = json.load(f)
+        assert rec["last_unresolved"] == [] and rec["unresolved_log"] == [[]], name
+        if name == "balanced":
+            assert sum(rec["last_shard_cost"]) == pop.body_counts(1).sum()
+        else:
+            assert rec["last_shard_cost"] is None

@@ -53,8 +53,7 @@ def main():
         batches = encode_population(off, 8, args.workers)
         t_enc = time.time() - t0
         t0 = time.time()
-        env.trees = env.robots = None
-        env._upload(batches, len(off))
+        env.reset_batches(batches, len(off))
         fit = run_episode(env).cpu().tolist()
         torch.cuda.synchronize()
         t_gpu = time.time() - t0
@@ -107,8 +106,7 @@ def main_arrays(args):
                 fit[np.asarray(idx)] = m.n_bodies
             t_gpu, steps = 0.0, 0
         else:
-            env.trees = env.robots = None
-            env._upload(batches, len(pop))
+            env.reset_batches(batches, len(pop))
             fit = run_episode(env, on_error="penalty").cpu().numpy()
             torch.cuda.synchronize()
             t_gpu, steps = time.time() - t0, int(env.steps.max())

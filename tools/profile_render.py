@@ -122,7 +122,7 @@ def generation_seconds(n=65536):
     from gym_rem2d_amd.evaluate import run_episode
     env = BatchedModular2D(flat=True, flags=_lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN)
     batches = synthetic.lsystem_batches_native(range(n))
-    env._upload(batches, n)
+    env.reset_batches(batches, n)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     run_episode(env, on_error="penalty")

@@ -28,7 +28,7 @@ def make_env(n, hardcore):
     from gym_rem2d_amd import _lib, synthetic
     from gym_rem2d_amd.env import BatchedModular2D
     env = BatchedModular2D(hardcore=hardcore, flags=_lib.FLAG_CONTINUOUS)
-    env._upload(synthetic.lsystem_batches_native(range(n)), n)
+    env.reset_batches(synthetic.lsystem_batches_native(range(n)), n)
     env.step(20)
     torch.cuda.synchronize()
     return env

@@ -57,12 +57,12 @@ def main():
                 pop.mutate(0.2, 0.2, 0.2, rng)
         batches = pop.compile(0)
     env = BatchedModular2D(hardcore=hard, flags=_lib.FLAG_CONTINUOUS | _lib.FLAG_SKIP_FROZEN)
-    env._upload(batches, args.n)
+    env.reset_batches(batches, args.n)
     shapes = sorted({int(w.tile_shape) for w, _ in env.worlds})
     t0 = time.time()
     fit = run_episode(env, max_steps=args.cap).cpu().numpy()
     t_gpu = time.time() - t0
-    overflow = sorted(env.last_overflow)
+    overflow = sorted(env.last_episode.overflow)
     env.close()
     sample = np.arange(args.n) if args.check >= 1.0 else \
         np.union1d(rng.choice(args.n, int(args.n * args.check), replace=False), np.asarray(overflow, dtype=np.int64))

@@ -57,7 +57,7 @@ def main():
             e.step_groups = 1   # (the same worlds on both sides: per-step launches would otherwise be dealt to four step groups)
             if args.tile_shape >= 0:
                 e.tile_shape = args.tile_shape
-            e._upload(batches, args.creatures)
+            e.reset_batches(batches, args.creatures)
             envs.append(e)
         # (launch_info: (tile shape, 2 = step train / 1 = velocity + position in one launch per step / 0 = two launches per step))
         assert envs[0].launch_info()[1] == 2 and envs[1].launch_info()[1] in (0, 1), (envs[0].launch_info(), envs[1].launch_info())
