@@ -91,6 +91,9 @@ RENDER_MAX_SIZE = 8192      # REM2D_RENDER_MAX_SIZE
 CONTROL_ABI_VERSION = 1     # include/rem2d_control.h
 SENSE_ABI_VERSION = 1       # include/rem2d_sense.h
 SENSE_MAX_RAYS = 64         # REM2D_SENSE_MAX_RAYS
+POLICY_ABI_VERSION = 1      # include/rem2d_policy.h
+POLICY_MAX_HIDDEN = 128     # REM2D_POLICY_MAX_HIDDEN
+POLICY_ACTIVATIONS = ("softsign", "relu")   # REM2D_POLICY_SOFTSIGN, REM2D_POLICY_RELU
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -146,6 +149,14 @@ class TreePopulation(C.Structure):
 class StepGroup(C.Structure):
     """rem2d_step_group (include/rem2d.h)."""
     _fields_ = [("worlds", C.POINTER(C.c_void_p)), ("n_worlds", C.c_int32), ("stream", C.c_void_p)]
+
+
+class Policy(C.Structure):
+    """rem2d_policy (include/rem2d_policy.h): device pointers the caller owns."""
+    _fields_ = ([(k, C.c_int32) for k in ("d", "max_bodies", "n_rays", "hidden", "activation")] + [("scale", C.c_float)]
+                + [(k, C.c_int32) for k in ("n_sets", "reserved")]
+                + [(k, C.c_void_p) for k in ("w1", "b1", "w2", "b2", "index", "row_mask", "obs", "frac", "targets", "valid")]
+                + [("n_rows", C.c_int64)])
 
 
 class Rem2dError(RuntimeError):
@@ -343,6 +354,12 @@ def lib(wide=False):
                                      C.c_void_p]
     if L.rem2d_sense_abi_version() != SENSE_ABI_VERSION:
         raise Rem2dError("%s: sense ABI version mismatch" % os.path.basename(path))
+    # device policies (include/rem2d_policy.h)
+    L.rem2d_policy_abi_version.restype = C.c_int
+    L.rem2d_policy_forward.argtypes = [C.POINTER(Policy), C.c_void_p]
+    L.rem2d_worlds_act.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Policy), C.c_void_p, C.c_void_p]
+    if L.rem2d_policy_abi_version() != POLICY_ABI_VERSION:
+        raise Rem2dError("%s: policy ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

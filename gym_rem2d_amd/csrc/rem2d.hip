@@ -42,6 +42,7 @@
 #include "rem2d_render.h"
 #include <rem2d_control.h> // the public header (include/); the quoted name below is the kernels' file beside this one
 #include <rem2d_sense.h>   // (likewise)
+#include <rem2d_policy.h>  // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -98,6 +99,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_raster.h"
 #include "rem2d_control.h"
 #include "rem2d_sense.h"
+#include "rem2d_policy.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -1511,6 +1513,94 @@ extern "C" int rem2d_worlds_sense(rem2d_world *const *worlds, int32_t n_worlds, 
         HIP_TRY(hipGetLastError());
     }
     return REM2D_OK;
+}
+
+// ---- device policies (include/rem2d_policy.h, csrc/rem2d_policy.h) ----
+extern "C" int rem2d_policy_abi_version(void) { return REM2D_POLICY_ABI_VERSION; }
+// Checks a policy descriptor; `what` prefixes the message.  Nothing it points to is read.
+static int policy_ok(const char *what, const rem2d_policy *p) {
+    const std::string s = std::string(what) + ": ";
+    if (!p) return fail(REM2D_E_INVALID, s + "NULL policy");
+    if (p->max_bodies < 1 || p->max_bodies > REM2D_CONTROL_MAX_BODIES)
+        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(p->max_bodies));
+    if (p->n_rays < 0 || p->n_rays > REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, s + "n_rays must be 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + ", not " + std::to_string(p->n_rays));
+    if (p->hidden < 1 || p->hidden > REM2D_POLICY_MAX_HIDDEN)
+        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(p->hidden));
+    if (p->d != REM2D_OBS_HEAD + REM2D_OBS_BODY * p->max_bodies + p->n_rays)
+        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + n_rays = " +
+                                         std::to_string(REM2D_OBS_HEAD + REM2D_OBS_BODY * p->max_bodies + p->n_rays) + ", not " + std::to_string(p->d));
+    if (p->activation != REM2D_POLICY_SOFTSIGN && p->activation != REM2D_POLICY_RELU)
+        return fail(REM2D_E_INVALID, s + "unknown activation " + std::to_string(p->activation));
+    if (p->n_sets < 1) return fail(REM2D_E_INVALID, s + "n_sets must be at least 1");
+    if (p->n_rows < 0) return fail(REM2D_E_INVALID, s + "negative row count");
+    if (!p->w1 || !p->b1 || !p->w2 || !p->b2 || !p->obs || !p->targets || !p->valid || (p->n_rays > 0 && !p->frac))
+        return fail(REM2D_E_INVALID, s + "NULL device pointer");
+    if (!p->index && (int64_t)p->n_sets != p->n_rows)
+        return fail(REM2D_E_INVALID, s + "without an index n_sets must be n_rows (" + std::to_string(p->n_sets) + " sets, " +
+                                         std::to_string(p->n_rows) + " rows)");
+    return REM2D_OK;
+}
+static unsigned pow2_at_least(unsigned v) {
+    unsigned p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+// The forward pass of a checked descriptor on `st`.
+static int policy_launch(const rem2d_policy *p, hipStream_t st) {
+    if (p->n_rows == 0) return REM2D_OK;
+    PolicyArgs A;
+    memset(&A, 0, sizeof(A));
+    A.w1 = p->w1; A.b1 = p->b1; A.w2 = p->w2; A.b2 = p->b2;
+    A.index = p->index; A.rowMask = p->row_mask;
+    A.obs = p->obs; A.frac = p->frac; A.targets = p->targets; A.valid = p->valid;
+    A.nRows = p->n_rows;
+    A.D = p->d; A.MB = p->max_bodies; A.R = p->n_rays; A.H = p->hidden; A.G = p->n_sets; A.act = p->activation;
+    A.scale = p->scale;
+    // 16-byte loads where a weight row is whole float4s and its base is aligned (the sets' strides D H and H MB then are too)
+    const bool v1 = p->hidden % 4 == 0 && (uintptr_t)p->w1 % 16 == 0;
+    const bool v2 = p->max_bodies % 4 == 0 && (uintptr_t)p->w2 % 16 == 0;
+    const unsigned need = std::max((unsigned)(p->hidden + (v1 ? 3 : 0)) / (v1 ? 4u : 1u), (unsigned)(p->max_bodies + (v2 ? 3 : 0)) / (v2 ? 4u : 1u));
+    const unsigned lpr = std::min((unsigned)WAVE, std::max((unsigned)POL_MIN_LPR, pow2_at_least(need)));
+    A.lpr = (int)lpr;
+    const unsigned rpw = WAVE / lpr;
+    const long long blocks = (p->n_rows + rpw - 1) / rpw;
+    if (blocks > 0x7fffffffLL) return fail(REM2D_E_INVALID, "policy: too many rows for one launch");
+    const size_t lds = (size_t)rpw * (size_t)(p->d + p->hidden) * sizeof(float);
+    void (*kernel)(PolicyArgs) = v1 ? (v2 ? rem2d_policy_forward_kernel<4, 4> : rem2d_policy_forward_kernel<4, 1>)
+                                    : (v2 ? rem2d_policy_forward_kernel<1, 4> : rem2d_policy_forward_kernel<1, 1>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, A);
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
+}
+extern "C" int rem2d_policy_forward(const rem2d_policy *p, void *stream) {
+    const int rc = policy_ok("policy", p);
+    if (rc != REM2D_OK) return rc;
+    return policy_launch(p, (hipStream_t)stream);
+}
+extern "C" int rem2d_worlds_act(rem2d_world *const *worlds, int32_t n_worlds, const rem2d_policy *p, const double *ray_offsets_dev,
+                                void *stream) {
+    // (arguments first, worlds after, everything before the first launch)
+    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "act: no worlds");
+    int rc = policy_ok("act", p);
+    if (rc != REM2D_OK) return rc;
+    if (p->n_rays > 0 && !ray_offsets_dev) return fail(REM2D_E_INVALID, "act: NULL device pointer (ray offsets)");
+    for (int32_t i = 0; i < n_worlds; ++i)
+        if (!worlds[i]) return fail(REM2D_E_INVALID, "act: world " + std::to_string(i) + " is NULL");
+    rc = control_worlds_ok("act", worlds, n_worlds, p->max_bodies, p->n_rows, p->obs);
+    if (rc != REM2D_OK) return rc;
+    if (p->n_rays > 0)
+        for (int32_t i = 0; i < n_worlds; ++i)
+            if (!worlds[i]->haveTerrain) return fail(REM2D_E_STATE, "act: rem2d_world_set_terrain must be called first");
+    rc = rem2d_worlds_observe(worlds, n_worlds, p->max_bodies, const_cast<float *>(p->obs), p->n_rows, stream);
+    if (rc != REM2D_OK) return rc;
+    if (p->n_rays > 0) {
+        rc = rem2d_worlds_sense(worlds, n_worlds, ray_offsets_dev, p->n_rays, const_cast<float *>(p->frac), nullptr, p->n_rows, stream);
+        if (rc != REM2D_OK) return rc;
+    }
+    rc = policy_launch(p, (hipStream_t)stream);
+    if (rc != REM2D_OK) return rc;
+    return rem2d_worlds_control(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, stream);
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

@@ -98,6 +98,7 @@ class BatchedModular2D:
         self.trees = None
         self.robots = None
         self._reward = self._done = None
+        self._policy = self._act_args = None   # set_policy()
         self.last_episode = None      # evaluate.EpisodeReport of the population in place (None: no episode since its upload)
         over = launch_policy.read_overrides()   # (REM2D_MERGED_LAUNCH, REM2D_STEP_GROUPS, REM2D_GRAPH, REM2D_REBALANCE: read here, once)
         self.merged_launch = over.merged_launch   # False: step every lane bucket on its own stream instead of one merged grid
@@ -192,6 +193,8 @@ class BatchedModular2D:
         self._ctl_keep = None
         self._sense = None                                     # sense_terrain()'s persistent (frac, hit) buffers, made on first use
         self._sense_rays = {}                                  # ray tables on the device, by content
+        self._policy = None                                    # set_policy(): the device policy and its persistent buffers
+        self._act_args = None
         # how this population runs -- step groups, tile shape, train or per-step launches, rebalancing, which creatures share a
         # world -- is launch_policy.plan's decision, from the buckets' shapes, this env's settings and the REM2D_* overrides
         knobs = launch_policy.Knobs(self.step_groups, self.tile_shape, self.flags, self.options, self.rebalance_every,
@@ -414,6 +417,7 @@ class BatchedModular2D:
             self.groups = groups
             self.group_streams = self.group_streams[:max(1, len(groups))]   # (the first is the caller's stream: None)
             self._group_args = None
+            self._act_args = None   # (act() masks the rows no live world holds any more)
         return alive_total
 
     @property
@@ -528,6 +532,72 @@ class BatchedModular2D:
             sense.sense(worlds, dev_rays, frac, hit)
         return (frac, hit) if hits else frac
 
+    # ---- device policies: the controllers live on the device as data (include/rem2d_policy.h) ----
+    def set_policy(self, policy):
+        """Attach a ``policy.MLPPolicy`` to the population in place (after reset; a new upload drops it), or None to detach it.  The
+        policy needs one weight set per creature, or an ``index`` with one entry per creature, and at most 64 bodies' worth of
+        columns; it is moved to the env's device.  The buffers act() works in -- observation rows, ray fractions, targets, validity
+        bytes -- are allocated here, once.  step(), observe(), sense_terrain() and set_joint_targets() are not affected."""
+        self._act_args = None
+        if policy is None:
+            self._policy = None
+            return
+        if not self.worlds:
+            raise ValueError("set_policy: no population in place (reset first)")
+        have = policy.n_sets if policy.index is None else int(policy.index.shape[0])
+        if have != self.n_envs:
+            raise ValueError("set_policy: the policy has %d %s for %d creatures"
+                             % (have, "weight sets" if policy.index is None else "index entries", self.n_envs))
+        dev = self.worlds[0][0].device
+        policy = policy.to(dev)
+        N, M, R = self.n_envs, policy.max_bodies, policy.n_rays
+        self._policy = dict(
+            policy=policy, rays=self._ray_table(policy.rays) if R else None,
+            obs=torch.zeros((N, control.width(M)), dtype=torch.float32, device=dev),
+            frac=torch.ones((N, R), dtype=torch.float32, device=dev) if R else None,
+            targets=torch.zeros((N, M), dtype=torch.float64, device=dev),
+            valid=torch.zeros((N, M), dtype=torch.uint8, device=dev))
+
+    @property
+    def policy(self):
+        return None if self._policy is None else self._policy["policy"]
+
+    def act(self):
+        """One control step by the attached policy: every creature is observed (and its rays cast), the policy's forward pass turns
+        the rows into joint targets, and the finite ones are written to the joints as set_joint_targets would -- one library call
+        (rem2d_worlds_act), four launches queued on the current stream, nothing synchronises.  Returns the persistent ``(targets
+        float64 [N, max_bodies], valid uint8 [N, max_bodies])`` buffers the call writes (clone what must last); ``valid`` 0 = the
+        target is not finite and that joint was left as it is.  After compact(), rows no live world holds are masked out of the
+        forward pass and keep their last values."""
+        P = self._policy
+        if P is None:
+            raise ValueError("act: no policy attached (set_policy first)")
+        if self._act_args is None:
+            worlds = self._control_worlds()
+            mask = None
+            if self._compacted:
+                mask = torch.zeros(self.n_envs, dtype=torch.uint8, device=P["obs"].device)
+                for wi, (w, idx) in enumerate(self.worlds):
+                    if wi not in self._inactive and getattr(w, "h", None):
+                        mask[idx] = 1
+            desc = P["policy"].descriptor(P["obs"], P["frac"], P["targets"], P["valid"], mask)
+            self._act_args = (worlds, _lib.world_array(worlds) if worlds else None, desc, mask)
+        worlds, arr, desc, _ = self._act_args
+        if worlds:
+            w0 = worlds[0]
+            _lib.check(w0.L.rem2d_worlds_act(arr, len(worlds), C.byref(desc), None if P["rays"] is None else P["rays"].data_ptr(),
+                                             w0._stream()), w0.wide)
+        return P["targets"], P["valid"]
+
+    def step_policy(self, n_steps=1):
+        """n_steps x (act(), step(1)), queued without any synchronisation: the closed loop with the controller on the device.
+        Returns what step() returns."""
+        out = self._reward, self._done
+        for _ in range(int(n_steps)):
+            self.act()
+            out = self.step(1)
+        return out
+
     def render(self, creatures=None, mode='rgb_array', **kw):
         """Frames of the creatures as they stand now: uint8 [n, H, W, 3] on the device (gym's rgb_array layout, one image per
         creature), drawn by the library's renderer (render.render_frames, which takes the keyword arguments: width, height,
@@ -550,7 +620,8 @@ class Modular2D(gymshim.Env):
 
     DEFAULT_MAX_BODIES = 32
 
-    def __init__(self, random_seed=None, device=None, closed_loop=False, max_bodies=DEFAULT_MAX_BODIES, wide=False, lidar=False):
+    def __init__(self, random_seed=None, device=None, closed_loop=False, max_bodies=DEFAULT_MAX_BODIES, wide=False, lidar=False,
+                 policy=None):
         """closed_loop=False: the reference's surface -- step(action) ignores the action and returns observation 0.
         closed_loop=True: ``observation_space`` is the ``8 + 6 * max_bodies`` floats of BatchedModular2D.observe (columns:
         control.layout(max_bodies)), ``action_space`` ``max_bodies`` joint target angles within +-pi/2 (column b: the joint between
@@ -560,8 +631,16 @@ class Modular2D(gymshim.Env):
         ``env._batch.errors()``, or construct the env with wide=True.
         lidar=True (closed loop only): BipedalWalker's 10 lidar fractions (BatchedModular2D.sense_terrain with sense.bipedal_rays())
         follow the ``8 + 6 * max_bodies`` words; ``observation_space`` is that much wider.  The reference advertises them
-        (24 = 14 + 10 floats) and never fills them."""
+        (24 = 14 + 10 floats) and never fills them.
+        policy (closed loop only): a ``policy.MLPPolicy`` with one weight set and ``max_bodies`` columns; step(None) then acts by it
+        (BatchedModular2D.act) instead of leaving the joints as they are.  An explicit action still wins."""
         self._device = device
+        self._policy = policy
+        if policy is not None:
+            if not closed_loop:
+                raise ValueError("policy= needs closed_loop=True")
+            if policy.max_bodies != int(max_bodies) or (policy.n_sets if policy.index is None else int(policy.index.shape[0])) != 1:
+                raise ValueError("policy= must have one weight set (or a one-entry index) and max_bodies = %d columns" % int(max_bodies))
         self.closed_loop, self.max_bodies, self._wide = bool(closed_loop), int(max_bodies), wide
         self.lidar = bool(lidar)
         if self.lidar and not self.closed_loop:
@@ -616,6 +695,8 @@ class Modular2D(gymshim.Env):
         self._pin_done = torch.zeros(1, dtype=torch.bool).pin_memory()
         self._pin_index = torch.zeros(1, dtype=torch.int32, device=self.world.device)
         self.world.set_outputs(self._pin_reward, self._pin_done, self._pin_index)
+        if self._policy is not None:
+            self._batch.set_policy(self._policy)
         if self.closed_loop:
             self._obs_dev = torch.zeros((1, control.width(self.max_bodies)), dtype=torch.float32, device=self.world.device)
             self._pin_obs = torch.zeros(control.width(self.max_bodies) + self._n_lidar, dtype=torch.float32).pin_memory()
@@ -643,6 +724,8 @@ class Modular2D(gymshim.Env):
             if a.shape[1] != self.max_bodies:
                 raise ValueError("action must have %d entries (max_bodies), got %d" % (self.max_bodies, a.shape[1]))
             self._batch.set_joint_targets(torch.from_numpy(a))
+        elif self._policy is not None:
+            self._batch.act()
         self.world.step(1)                      # one creature: straight to the C ABI, no bucket / group bookkeeping
         obs = self._observe() if self.closed_loop else 0   # (waits for the stream like the line below)
         torch.cuda.current_stream(self.world.device).synchronize()

@@ -108,12 +108,13 @@ def check_errors(env, on_error="raise"):
     return bad
 
 
-def _episode(env, max_steps, chunk, compact):
+def _episode(env, max_steps, chunk, compact, step=None):
+    step = env.step if step is None else step
     done_steps = 0
     compact = compact and bool(env.flags & _lib.FLAG_SKIP_FROZEN)
     while done_steps < max_steps:
         n = min(chunk, max_steps - done_steps)
-        env.step(n)
+        step(n)
         done_steps += n
         if compact:
             if env.compact() == 0:
@@ -249,6 +250,23 @@ def run_episode(env, max_steps=EPISODE_CAP, chunk=100, on_error="fallback", comp
     env.last_episode = None
     _episode(env, max_steps, chunk, compact)
     check_errors(env, on_error)   # (REM2D_ERR_HANDOVER raises HandoverError in "raise" and "warn"; so does env.fitness below)
+    return env.fitness.clone()
+
+
+def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_error="raise"):
+    """run_episode for a BatchedModular2D with a device policy attached (``env.set_policy``): the same episode loop, every step
+    preceded by the policy's control step (``env.step_policy``), chunks of ``chunk`` steps queued without a synchronisation in
+    between.  Returns fitness[N] (float64 tensor on the env's device).  on_error: "raise" | "warn" | "ignore", judged by
+    ``check_errors`` on the default build's flags.  There is no second attempt here: replaying the flagged creatures from reset in
+    the wide build, as run_episode's fallback does for open-loop creatures, is not built for policies yet -- construct the env
+    with wide=True where creatures may outgrow the default build's contact slots.  ``env.last_episode`` is None afterwards."""
+    if on_error not in ("raise", "warn", "ignore"):
+        raise ValueError("on_error must be 'raise', 'warn' or 'ignore', not %r" % (on_error,))
+    if env.policy is None:
+        raise ValueError("run_policy_episode: the env has no policy (set_policy first)")
+    env.last_episode = None
+    _episode(env, max_steps, chunk, compact, step=env.step_policy)
+    check_errors(env, on_error)
     return env.fitness.clone()
 
 

@@ -1,0 +1,182 @@
+"""Device policies: per-creature MLP controllers evaluated by the library between what the creatures sense and what their joints
+are told (include/rem2d_policy.h).
+
+``MLPPolicy`` holds the weights of G controllers -- one per creature, or fewer that creatures share through an ``index`` -- as
+float32 tensors.  Its input row is ``BatchedModular2D.observe(max_bodies)`` followed by ``sense_terrain(rays)``, its output one joint
+target per body column, ``scale * softsign(.)``, and a validity byte per target (false: not finite, the joint is left alone).
+``BatchedModular2D.set_policy`` / ``act`` / ``step_policy`` run it for a population; ``MLPPolicy.forward`` is the kernel alone.
+
+The arithmetic is binary32, one separately rounded operation after the other in a fixed order (the header states it), the same in
+every build of the library: what a policy computes is as reproducible as a step.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, control, sense
+
+ABI_VERSION = _lib.POLICY_ABI_VERSION
+MAX_HIDDEN = _lib.POLICY_MAX_HIDDEN
+ACTIVATIONS = _lib.POLICY_ACTIVATIONS     # index = REM2D_POLICY_SOFTSIGN / REM2D_POLICY_RELU
+DEFAULT_SCALE = float(np.float32(math.pi / 2))   # the reference's joint limit, as binary32
+
+
+def input_width(max_bodies, n_rays):
+    """D: words of a policy's input row."""
+    return control.width(max_bodies) + int(n_rays)
+
+
+def _f32(t, what, dims):
+    t = torch.as_tensor(t)
+    if t.dtype != torch.float32:
+        if t.dtype not in (torch.float64, torch.float16, torch.bfloat16):
+            raise ValueError("%s must be a float tensor" % what)
+        t = t.to(torch.float32)
+    if t.dim() == dims - 1:
+        t = t.unsqueeze(0)      # one weight set given without its leading axis
+    if t.dim() != dims:
+        raise ValueError("%s must have %d axes ([G, ...]), not shape %r" % (what, dims, tuple(t.shape)))
+    return t.contiguous()
+
+
+class MLPPolicy:
+    """G feed-forward controllers ``x [D] -> softsign / relu -> [H] -> scale * softsign -> [max_bodies]``.
+
+    w1 ``[G, D, H]``, b1 ``[G, H]``, w2 ``[G, H, max_bodies]``, b2 ``[G, max_bodies]`` (a single set may come without the G axis);
+    ``max_bodies``, ``H``, ``G`` and the number of rays ``R = D - 8 - 6 * max_bodies`` follow from the shapes.  ``index``: int
+    ``[N]``, the weight set of population row r (a value outside ``[0, G)`` leaves that creature to its oscillators); without it
+    row r uses set r.  ``rays``: float64 ``[R, 2]`` offsets of the rays whose fractions follow the observation words; default
+    ``sense.bipedal_rays()`` when R is 10, none when R is 0."""
+
+    def __init__(self, w1, b1, w2, b2, activation="softsign", scale=None, index=None, rays=None):
+        w1, b1, w2, b2 = _f32(w1, "w1", 3), _f32(b1, "b1", 2), _f32(w2, "w2", 3), _f32(b2, "b2", 2)
+        G, D, H = (int(v) for v in w1.shape)
+        MB = int(w2.shape[2])
+        if tuple(b1.shape) != (G, H) or tuple(w2.shape) != (G, H, MB) or tuple(b2.shape) != (G, MB):
+            raise ValueError("shapes do not fit: w1 %r b1 %r w2 %r b2 %r (want [G, D, H], [G, H], [G, H, M], [G, M])"
+                             % (tuple(w1.shape), tuple(b1.shape), tuple(w2.shape), tuple(b2.shape)))
+        if G < 1:
+            raise ValueError("a policy needs at least one weight set")
+        if not 1 <= MB <= control.MAX_BODIES:
+            raise ValueError("max_bodies (w2's last axis) must be 1..%d, not %d" % (control.MAX_BODIES, MB))
+        if not 1 <= H <= MAX_HIDDEN:
+            raise ValueError("the hidden width must be 1..%d, not %d" % (MAX_HIDDEN, H))
+        R = D - control.width(MB)
+        if not 0 <= R <= sense.MAX_RAYS:
+            raise ValueError("w1 has %d input rows: with max_bodies = %d that must be %d + R, R in 0..%d"
+                             % (D, MB, control.width(MB), sense.MAX_RAYS))
+        if activation not in ACTIVATIONS:
+            raise ValueError("activation must be one of %r, not %r" % (ACTIVATIONS, activation))
+        if len({t.device for t in (w1, b1, w2, b2)}) != 1:
+            raise ValueError("the four weight tensors must share a device")
+        if rays is None:
+            if R == len(sense.bipedal_rays()):
+                rays = sense.bipedal_rays()
+            elif R != 0:
+                raise ValueError("w1 asks for %d rays: pass their offsets as rays=[%d, 2]" % (R, R))
+        elif R == 0:
+            raise ValueError("rays given, but w1 has no input rows for ray fractions")
+        if rays is not None:
+            rays = sense.check_rays(rays.detach().cpu().numpy() if isinstance(rays, torch.Tensor) else rays)
+            if rays.shape[0] != R:
+                raise ValueError("w1 asks for %d rays, rays has %d" % (R, rays.shape[0]))
+        if index is not None:
+            index = torch.as_tensor(index)
+            if index.dim() != 1 or index.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+                raise ValueError("index must be a 1-d integer tensor")
+            index = index.to(device=w1.device, dtype=torch.int32).contiguous()
+        self.w1, self.b1, self.w2, self.b2 = w1, b1, w2, b2
+        self.activation = activation
+        self.scale = DEFAULT_SCALE if scale is None else float(np.float32(scale))
+        self.index, self.rays = index, rays
+        self.n_sets, self.d, self.hidden, self.max_bodies, self.n_rays = G, D, H, MB, R
+
+    # ---- construction ----
+    @classmethod
+    def random(cls, n_sets, max_bodies, hidden, n_rays=10, seed=0, std=(0.3, 0.3, 0.5, 0.3), **kw):
+        """n_sets controllers with normal weights: w1, b1, w2, b2 drawn in that order from ``numpy.random.default_rng(seed)``, scaled
+        by ``std`` (one number, or one per array).  Keyword arguments go to the constructor."""
+        std = (float(std),) * 4 if np.isscalar(std) else tuple(float(s) for s in std)
+        rng = np.random.default_rng(seed)
+        D = input_width(max_bodies, n_rays)
+        shapes = ((n_sets, D, hidden), (n_sets, hidden), (n_sets, hidden, max_bodies), (n_sets, max_bodies))
+        arrays = [torch.from_numpy((rng.standard_normal(s) * sd).astype(np.float32)) for s, sd in zip(shapes, std)]
+        if n_rays not in (0, 10) and "rays" not in kw:
+            kw["rays"] = sense.bipedal_rays(n_rays)
+        return cls(*arrays, **kw)
+
+    def _like(self, w1, b1, w2, b2, index):
+        return MLPPolicy(w1, b1, w2, b2, self.activation, self.scale, index, self.rays)
+
+    def take(self, indices):
+        """The policy of a selection: weight sets ``indices`` (repeats allowed), in that order, one per creature -- what an EA's
+        selection step needs.  With an ``index`` the creatures' sets are resolved through it first."""
+        sel = torch.as_tensor(indices, dtype=torch.long, device=self.device)
+        if self.index is not None:
+            sel = self.index.to(torch.long)[sel]
+            if bool(((sel < 0) | (sel >= self.n_sets)).any()):
+                raise ValueError("take: a selected creature's index names no weight set")
+        return self._like(self.w1[sel], self.b1[sel], self.w2[sel], self.b2[sel], None)
+
+    @property
+    def device(self):
+        return self.w1.device
+
+    def to(self, device):
+        device = torch.device(device)
+        if device == self.device:
+            return self
+        return self._like(self.w1.to(device), self.b1.to(device), self.w2.to(device), self.b2.to(device),
+                          None if self.index is None else self.index.to(device))
+
+    def weight_bytes(self):
+        """Bytes of one weight set."""
+        return 4 * (self.d * self.hidden + self.hidden + self.hidden * self.max_bodies + self.max_bodies)
+
+    # ---- the library's descriptor ----
+    def descriptor(self, obs, frac, targets, valid, row_mask=None):
+        """rem2d_policy over these buffers (checked: contiguous, right dtype and shape, this policy's device)."""
+        dev, N = self.device, int(obs.shape[0])
+
+        def ok(t, dtype, shape, what):
+            if t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape:
+                raise ValueError("policy: %s must be a contiguous %s %r tensor on %s" % (what, dtype, shape, dev))
+        if dev.type != "cuda":
+            raise ValueError("policy: the weights are on %s; move the policy to the GPU with .to(device)" % dev)
+        ok(obs, torch.float32, (N, control.width(self.max_bodies)), "obs")
+        if self.n_rays:
+            ok(frac, torch.float32, (N, self.n_rays), "frac")
+        ok(targets, torch.float64, (N, self.max_bodies), "targets")
+        ok(valid, torch.uint8, (N, self.max_bodies), "valid")
+        if row_mask is not None:
+            ok(row_mask, torch.uint8, (N,), "row_mask")
+        if self.index is not None and int(self.index.shape[0]) != N:
+            raise ValueError("policy: index has %d entries for %d rows" % (self.index.shape[0], N))
+        if self.index is None and self.n_sets != N:
+            raise ValueError("policy: %d weight sets for %d rows (share sets through index=)" % (self.n_sets, N))
+        p = _lib.Policy()
+        p.d, p.max_bodies, p.n_rays, p.hidden = self.d, self.max_bodies, self.n_rays, self.hidden
+        p.activation, p.scale, p.n_sets, p.reserved = ACTIVATIONS.index(self.activation), self.scale, self.n_sets, 0
+        p.w1, p.b1, p.w2, p.b2 = (t.data_ptr() for t in (self.w1, self.b1, self.w2, self.b2))
+        p.index = None if self.index is None else self.index.data_ptr()
+        p.row_mask = None if row_mask is None else row_mask.data_ptr()
+        p.obs, p.frac = obs.data_ptr(), (frac.data_ptr() if self.n_rays else None)
+        p.targets, p.valid, p.n_rows = targets.data_ptr(), valid.data_ptr(), N
+        return p
+
+    def forward(self, obs, frac=None, out=None, row_mask=None, wide=False):
+        """The forward pass alone (rem2d_policy_forward) on the current stream: ``obs`` float32 ``[N, 8 + 6 * max_bodies]``, ``frac``
+        float32 ``[N, R]`` (None when R is 0) -> ``(targets float64 [N, max_bodies], valid uint8 [N, max_bodies])``.  ``out``: that
+        pair to write into (rows a ``row_mask`` uint8 ``[N]`` clears, or whose index names no weight set, keep what they hold);
+        without it new zeroed tensors.  ``wide``: the build whose kernel runs (all three write the same bits)."""
+        N = int(obs.shape[0])
+        if out is None:
+            out = (torch.zeros((N, self.max_bodies), dtype=torch.float64, device=self.device),
+                   torch.zeros((N, self.max_bodies), dtype=torch.uint8, device=self.device))
+        p = self.descriptor(obs, frac, out[0], out[1], row_mask)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib(wide).rem2d_policy_forward(C.byref(p), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                       wide)
+        return out
