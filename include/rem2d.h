@@ -156,7 +156,11 @@ size_t rem2d_state_bytes(const rem2d_world_cfg *cfg);
 int32_t rem2d_padded_envs(const rem2d_world_cfg *cfg);
 
 /* Box2D.b2World() for n_envs worlds (Modular2DEnv.py:144,572): gravity (0,-10), sleeping,
- * warm starting and continuous physics as pybox2d defaults (flags select variants). */
+ * warm starting and continuous physics as pybox2d defaults (flags select variants).
+ * The arena (state_dev: rem2d_state_bytes bytes, 256-byte aligned, caller-owned) may hold ANYTHING at create: this call neither
+ * reads nor writes it, and no call reads a field of it before rem2d_world_reset (or the caller itself, rem2d_world_adopt) has
+ * written every field.  The bytes between the field groups (alignment gaps) and outside the rem2d_state_bytes window are never
+ * written by any call. */
 int rem2d_world_create(const rem2d_world_cfg *cfg, void *state_dev, size_t state_bytes, rem2d_world **out);
 /* world teardown (Modular2DEnv.py:175-186 _destroy + garbage-collected b2World) */
 int rem2d_world_destroy(rem2d_world *w);
@@ -168,7 +172,16 @@ int rem2d_world_set_terrain(rem2d_world *w, const float *xs, const float *ys, in
                             int32_t npolys, float friction);
 
 /* Modular2D.reset (Modular2DEnv.py:565-598): destroy + re-create every world and build the
- * robots (create_robot :517-563) from the uploaded layout; wall of death back to 0. */
+ * robots (create_robot :517-563) from the uploaded layout; wall of death back to 0.
+ * May be called any number of times on one world, between any two step calls (queued on `stream` like them).
+ * Re-initialised: EVERY field of the arena -- all lanes, pair slots and per-creature words (reward, done, fitness, step count,
+ * error bits, ...), padding creatures and empty lanes included --, whatever the arena held before: a world that was stepped, or
+ * memory that was never written.  Kept: the terrain, the launch options, the tile shape and the tile table (one planned for
+ * other creatures must be replaced, rem2d_world_set_tiles, before the next step), the outputs of rem2d_world_set_outputs, the
+ * creature order (rem2d_world_set_order, REM2D_OPT_REBALANCE, REM2D_FLAG_RETILE: a launch shape, valid for any population),
+ * the timing state and the hand-over failure counter (cumulative until read with `clear`); a graph captured by rem2d_groups_step
+ * stays valid.  The handle's scratch memory is not cleared and need not be: every step writes what it reads ("What
+ * survives a reset, what survives a step"). */
 int rem2d_world_reset(rem2d_world *w, const rem2d_morph *morph_dev, void *stream);
 
 /* Instead of rem2d_world_reset: the caller has filled EVERY field of the state arena itself, creature by creature, from the

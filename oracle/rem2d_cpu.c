@@ -11,7 +11,9 @@
  *
  * Fields the twin maintains: every per-lane pose / velocity / sleep / joint-impulse / limit-state / controller field,
  * the static per-lane fields written by reset, the pair lists (edge, point count | type << 8, feature keys, warm-start
- * impulses, in list order) and every per-creature field except REM2D_F_NEWFIX.  Scheduling entry points of the GPU
+ * impulses, in list order) and every per-creature field except REM2D_F_NEWFIX and REM2D_F_ERR, which only reset writes (1 and
+ * 0, like the GPU's reset: the arena right after rem2d_cpu_world_reset is the image of rem2d_reset_kernel's, byte for byte over
+ * all padded rows -- tests/test_lifecycle_gpu.py compares them before anything steps).  Scheduling entry points of the GPU
  * library (set_tiles, timing) are accepted and ignored; the host-only entry points of librem2d.so (rem2d_plan_tiles,
  * rem2d_compile_*) need no twin.
  */
@@ -263,6 +265,17 @@ int rem2d_cpu_world_reset(rem2d_cpu_world *w, const rem2d_morph *m, void *stream
     const int K = w->cfg.lanes, N = w->cfg.n_envs;
     c_free_worlds(w);
     memset(w->arena, 0, w->L.total);
+    /* what rem2d_reset_kernel (gym_rem2d_amd/csrc/rem2d_kernels.h) writes that is not a zero, on EVERY lane, pair slot and
+     * creature word, padding creatures and empty lanes included -- the image of the arena right after a reset is the same in
+     * both libraries, byte for byte (tests/test_lifecycle_gpu.py): no parent, the fat AABB of a circle of radius 0 at the
+     * origin, every pair slot without an edge, "fixtures are new" for the first step's FindNewContacts */
+    for (int i = 0; i < w->L.Lp; ++i) {
+        FPTR(int32_t, REM2D_F_PARENT)[i] = -1;
+        FPTR(float, REM2D_F_FATLX)[i] = 0.0f - 0.1f; FPTR(float, REM2D_F_FATLY)[i] = 0.0f - 0.1f; /* b2_aabbExtension */
+        FPTR(float, REM2D_F_FATUX)[i] = 0.0f + 0.1f; FPTR(float, REM2D_F_FATUY)[i] = 0.0f + 0.1f;
+    }
+    for (size_t q = 0; q < (size_t)REM2D_CONTACT_SLOTS * w->L.Lp; ++q) FPTR(int32_t, REM2D_F_CEDGE)[q] = -1;
+    for (int e = 0; e < w->L.Np; ++e) FPTR(int32_t, REM2D_F_NEWFIX)[e] = 1;
     o_morph om;
     om.n_envs = N; om.lanes = K;
     om.shape = m->shape; om.hx = m->hx; om.hy = m->hy; om.x = m->x; om.y = m->y; om.angle = m->angle;
