@@ -182,6 +182,12 @@ DEV void contact_warm_start(const ContactC &c, float mB, float iB, float &vx, fl
         vx += mB * P.x; vy += mB * P.y;
     }
 }
+// The 2-point block solve's cases 2 .. 4 are three short predicated regions the compiler gives no skip branch: a wavefront
+// issued them (~34 instructions) in every sub-slot that holds a 2-point manifold, though case 1 settles most of them.  One ballot
+// over the lanes that EXECUTE the 2-point branch (an inactive lane's bit of a ballot is 0: lanes outside the gated sub-slot or in
+// the count == 1 branch cannot ask for the cases) gives a scalar to branch on around the three as a whole; inside, every lane
+// takes the cases it took before, in the same order on the same operands: the same bits.
+DEV bool block_fallback_needed(bool solved) { return __ballot(solved ? 0 : 1) != 0ull; }
 // SolveVelocityConstraints for one contact (friction first, then normal / 2-point block LCP)
 DEV void contact_solve(ContactC &c, float mB, float iB, float friction, float &vx, float &vy, float &w) {
     V2 normal = c.normal, tangent = vcross_vs(normal, 1.0f);
@@ -232,22 +238,24 @@ DEV void contact_solve(ContactC &c, float mB, float iB, float friction, float &v
         bool solved = false;
         x = vneg(mk(c.i11 * b.x + c.i12 * b.y, c.i12 * b.x + c.i22 * b.y)); // case 1
         solved = x.x >= 0.0f && x.y >= 0.0f;
-        if (!solved) { // case 2
-            x.x = -c.nm0 * b.x;
-            x.y = 0.0f;
-            vn2 = c.k12 * x.x + b.y;
-            solved = x.x >= 0.0f && vn2 >= 0.0f;
-        }
-        if (!solved) { // case 3
-            x.x = 0.0f;
-            x.y = -c.nm1 * b.y;
-            vn1 = c.k12 * x.y + b.x;
-            solved = x.y >= 0.0f && vn1 >= 0.0f;
-        }
-        if (!solved) { // case 4
-            x.x = 0.0f;
-            x.y = 0.0f;
-            solved = b.x >= 0.0f && b.y >= 0.0f;
+        if (block_fallback_needed(solved)) {
+            if (!solved) { // case 2
+                x.x = -c.nm0 * b.x;
+                x.y = 0.0f;
+                vn2 = c.k12 * x.x + b.y;
+                solved = x.x >= 0.0f && vn2 >= 0.0f;
+            }
+            if (!solved) { // case 3
+                x.x = 0.0f;
+                x.y = -c.nm1 * b.y;
+                vn1 = c.k12 * x.y + b.x;
+                solved = x.y >= 0.0f && vn1 >= 0.0f;
+            }
+            if (!solved) { // case 4
+                x.x = 0.0f;
+                x.y = 0.0f;
+                solved = b.x >= 0.0f && b.y >= 0.0f;
+            }
         }
         if (solved) {
             V2 d = vsub(x, a);
@@ -339,22 +347,24 @@ DEV void contact_solve_quad(ContactC &c, const QuadRole &r, float mB, float iB, 
         bool solved = false;
         x = vneg(mk(c.i11 * b.x + c.i12 * b.y, c.i12 * b.x + c.i22 * b.y)); // case 1
         solved = x.x >= 0.0f && x.y >= 0.0f;
-        if (!solved) { // case 2
-            x.x = -c.nm0 * b.x;
-            x.y = 0.0f;
-            vn2 = c.k12 * x.x + b.y;
-            solved = x.x >= 0.0f && vn2 >= 0.0f;
-        }
-        if (!solved) { // case 3
-            x.x = 0.0f;
-            x.y = -c.nm1 * b.y;
-            vn1 = c.k12 * x.y + b.x;
-            solved = x.y >= 0.0f && vn1 >= 0.0f;
-        }
-        if (!solved) { // case 4
-            x.x = 0.0f;
-            x.y = 0.0f;
-            solved = b.x >= 0.0f && b.y >= 0.0f;
+        if (block_fallback_needed(solved)) { // (the four lanes of a quad hold the same constraint and take the same case: nothing more to agree on)
+            if (!solved) { // case 2
+                x.x = -c.nm0 * b.x;
+                x.y = 0.0f;
+                vn2 = c.k12 * x.x + b.y;
+                solved = x.x >= 0.0f && vn2 >= 0.0f;
+            }
+            if (!solved) { // case 3
+                x.x = 0.0f;
+                x.y = -c.nm1 * b.y;
+                vn1 = c.k12 * x.y + b.x;
+                solved = x.y >= 0.0f && vn1 >= 0.0f;
+            }
+            if (!solved) { // case 4
+                x.x = 0.0f;
+                x.y = 0.0f;
+                solved = b.x >= 0.0f && b.y >= 0.0f;
+            }
         }
         if (solved) {
             V2 d = vsub(x, a);
@@ -421,22 +431,24 @@ DEV void contact_solve_pair(ContactC &c, const QuadRole &r, float mB, float iB, 
         bool solved = false;
         x = vneg(mk(c.i11 * b.x + c.i12 * b.y, c.i12 * b.x + c.i22 * b.y)); // case 1
         solved = x.x >= 0.0f && x.y >= 0.0f;
-        if (!solved) { // case 2
-            x.x = -c.nm0 * b.x;
-            x.y = 0.0f;
-            vn2 = c.k12 * x.x + b.y;
-            solved = x.x >= 0.0f && vn2 >= 0.0f;
-        }
-        if (!solved) { // case 3
-            x.x = 0.0f;
-            x.y = -c.nm1 * b.y;
-            vn1 = c.k12 * x.y + b.x;
-            solved = x.y >= 0.0f && vn1 >= 0.0f;
-        }
-        if (!solved) { // case 4
-            x.x = 0.0f;
-            x.y = 0.0f;
-            solved = b.x >= 0.0f && b.y >= 0.0f;
+        if (block_fallback_needed(solved)) { // (both lanes of a pair hold the same constraint and take the same case: nothing more to agree on)
+            if (!solved) { // case 2
+                x.x = -c.nm0 * b.x;
+                x.y = 0.0f;
+                vn2 = c.k12 * x.x + b.y;
+                solved = x.x >= 0.0f && vn2 >= 0.0f;
+            }
+            if (!solved) { // case 3
+                x.x = 0.0f;
+                x.y = -c.nm1 * b.y;
+                vn1 = c.k12 * x.y + b.x;
+                solved = x.y >= 0.0f && vn1 >= 0.0f;
+            }
+            if (!solved) { // case 4
+                x.x = 0.0f;
+                x.y = 0.0f;
+                solved = b.x >= 0.0f && b.y >= 0.0f;
+            }
         }
         if (solved) {
             V2 d = vsub(x, a);
