@@ -17,7 +17,8 @@ import pytest
 
 import control_model as M
 import state_forge as F
-from test_injected_state_gpu import mismatches, read_state
+from env_harness import check_final, make_env, population_rows
+from replay import need_gpu, read_state
 
 pytestmark = pytest.mark.gpu
 
@@ -33,59 +34,7 @@ def _pid(c):
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
-    return torch
-
-
-def make_env(pop, wide=False, options=None, flags=CONT):
-    """BatchedModular2D holding the lane buckets of loop population `pop`, one world per bucket, in an interleaved population
-    order: creature e of bucket k is population row rows[k][e].  -> (env, rows, morphs)"""
-    from gym_rem2d_amd.env import BatchedModular2D
-    terrain, morphs = M.loop_population(pop)
-    n = sum(m.n_envs for m in morphs)
-    order = np.random.default_rng(5).permutation(n)
-    rows, at = [], 0
-    for m in morphs:
-        rows.append(order[at:at + m.n_envs])
-        at += m.n_envs
-    env = BatchedModular2D(hardcore=(pop == "cppn"), seed=4, flags=flags, wide=wide, options=options)
-    assert np.array_equal(env._terrain().f32()[1], terrain.f32()[1])      # the population's own terrain
-    env._upload([(m, r) for m, r in zip(morphs, rows)], n)
-    assert len(env.worlds) == len(morphs) and all(w.n_envs == m.n_envs for (w, _), m in zip(env.worlds, morphs))
-    return env, rows, morphs
-
-
-def population_rows(runs, rows, key, t, max_bodies):
-    """The runs' per-bucket arrays of step t as one population-order array of `max_bodies` columns of bodies (zero beyond a bucket's)."""
-    n = sum(len(r) for r in rows)
-    per = M.OBS_BODY if key == "obs" else 1
-    head = M.OBS_HEAD if key == "obs" else 0
-    out = np.zeros((n, head + per * max_bodies), runs[0][key][t].dtype)
-    for run, r in zip(runs, rows):
-        v = run[key][t]
-        out[r, :v.shape[1]] = v
-    return out
-
-
-def check_final(env, runs, firsts, what):
-    from gym_rem2d_amd import _lib
-    pair_slots = _lib.capacity(env.wide)[0]
-    bad = []
-    for (w, _), run, (first, bits) in zip(env.worlds, runs, firsts):
-        keep = first >= len(run["obs"])
-        st = read_state(w)
-        bad += mismatches(run["ctx"], st, run["final"], keep, pair_slots, "%s K=%d final" % (what, run["ctx"].K))
-        err = st["err"]
-        if (err[keep] != 0).any():
-            bad.append("K=%d: error bits on creatures the oracle does not justify: %s" % (run["ctx"].K, err[keep][err[keep] != 0]))
-        if ((err[~keep] & bits[~keep]) != bits[~keep]).any():
-            bad.append("K=%d: left-out creatures without their capacity bit" % run["ctx"].K)
-        assert w.handover_failures() == 0
-    assert not bad, "\n".join(bad)
+    return need_gpu()
 
 
 @pytest.mark.parametrize("case", PARITY, ids=_pid)

@@ -23,13 +23,8 @@ HOST_ONLY = {
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
-    from gym_rem2d_amd.world import BatchedWorld
-    return BatchedWorld
+    import replay
+    return replay.need_gpu(world=True)
 
 
 def _twin():

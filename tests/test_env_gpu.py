@@ -14,11 +14,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def need_gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
+    import replay
+    replay.need_gpu()
 
 
 class _Individual:

@@ -30,12 +30,8 @@ OPS = {"collide": 0, "distance": 1, "toi": 2, "far_apart": 3}
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
-    return torch
+    import replay
+    return replay.need_gpu()
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,11 +22,8 @@ CONT = F.FLAG_CONTINUOUS
 
 @pytest.fixture(scope="module")
 def need_gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
+    import replay
+    replay.need_gpu()
 
 
 @pytest.fixture(scope="module")

@@ -21,12 +21,8 @@ T_SENTINEL, V_SENTINEL = -12345.678, 0xA5
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
-    return torch
+    import replay
+    return replay.need_gpu()
 
 
 # ------------------------------------------------------------------------------------------------------------------ the forge
@@ -185,7 +181,7 @@ def test_closed_loop_parity(gpu, oracle, case):
     torch = gpu
     pop, wide, options = case
     from gym_rem2d_amd import _lib, policy
-    from test_control_gpu import check_final, make_env, population_rows
+    from env_harness import check_final, make_env, population_rows
     runs = PM.policy_loop_run(oracle, pop, CONT)
     env, rows, morphs = make_env(pop, wide, options)
     try:
@@ -220,7 +216,7 @@ def test_closed_loop_parity(gpu, oracle, case):
 def _world_bytes(env):
     """every state field of every active world, as host arrays (one copy per world)"""
     from gym_rem2d_amd import _lib
-    from test_injected_state_gpu import read_state
+    from replay import read_state
     out = []
     for wi, (w, idx) in enumerate(env.worlds):
         if wi in env._inactive:

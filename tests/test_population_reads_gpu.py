@@ -14,11 +14,8 @@ _TORCH_INDEXING = ("index_copy_", "index_copy", "index_put_", "index_put", "inde
 
 @pytest.fixture(scope="module")
 def need_gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
+    import replay
+    replay.need_gpu()
 
 
 def test_population_reads_use_the_library_gather(need_gpu, monkeypatch):

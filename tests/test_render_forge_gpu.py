@@ -14,12 +14,8 @@ CANARY = 0xA7
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
-    return torch
+    import replay
+    return replay.need_gpu()
 
 
 @pytest.fixture(scope="module")

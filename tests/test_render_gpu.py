@@ -5,18 +5,15 @@ import random
 import numpy as np
 import pytest
 
-import render_model as M
+from env_harness import _compare
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def need_gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
+    import replay
+    replay.need_gpu()
 
 
 @pytest.fixture(scope="module")
@@ -51,44 +48,6 @@ def _env(kind, terrain="default", n=None, **kw):
     elif kind == "chain8":
         env.reset_morphology(synthetic.chain_population(n or 128, 8, "left"))
     return env
-
-
-def _scene(env, c):
-    """(bodies, wod) of population creature c, read from its world's state."""
-    from gym_rem2d_amd.render import _locate
-    _, wis, loc = _locate(env, [c])
-    w, e = env.worlds[int(wis[0])][0], int(loc[0])
-    cols = [w.view(k)[e].cpu().numpy() for k in ("shape", "px", "py", "ang", "hx", "hy")]
-    bodies = list(zip(*cols))
-    return bodies, float(w.view("wod")[e].item()), (int(wis[0]), e)
-
-
-def _model(env, c, cam, width, height, sincosf, fill=None, line=None):
-    bodies, wod, (wi, e) = _scene(env, c)
-    if fill is None:
-        from gym_rem2d_amd.render import _world_colors
-        f, l_ = _world_colors(env, wi)
-        if f is not None:
-            fill, line = f[e].cpu().numpy(), l_[e].cpu().numpy()
-    return M.render(width, height, cam, terrain=M.Terrain.of(env._terrain()), bodies=bodies, fill=fill, line=line, wod=wod,
-                    sincosf=sincosf)
-
-
-def _compare(env, creatures, width, height, sincosf, cam=None, **kw):
-    import torch
-    from gym_rem2d_amd import render as R
-    got = R.render_frames(env, creatures, width, height, camera=cam, **kw).cpu().numpy()
-    camxy = (R.follow_camera(env, creatures) if cam is None else torch.as_tensor(cam, dtype=torch.float32)).cpu().numpy()
-    fill, line = kw.get("fill"), kw.get("line")
-    for k, c in enumerate(creatures):
-        _, _, (wi, e) = _scene(env, c)
-        f = None if fill is None else np.asarray(fill.cpu() if hasattr(fill, "cpu") else fill)[e]
-        l_ = None if line is None else np.asarray(line.cpu() if hasattr(line, "cpu") else line)[e]
-        want = _model(env, c, camxy[k], width, height, sincosf, fill=f, line=l_)
-        if not np.array_equal(got[k], want):
-            bad = np.argwhere(np.any(got[k] != want, axis=-1))
-            pytest.fail("creature %d (%d x %d): %d pixels differ, first %s: kernel %s model %s" % (
-                c, width, height, len(bad), bad[0].tolist(), got[k][tuple(bad[0])].tolist(), want[tuple(bad[0])].tolist()))
 
 
 @pytest.mark.parametrize("kind,terrain", [("lsystem", "default"), ("direct", "hardcore"), ("chain8", "flat"),

@@ -19,12 +19,8 @@ f32 = np.float32
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
-    return torch
+    import replay
+    return replay.need_gpu()
 
 
 def same(got, want, what, keep=None):
@@ -351,7 +347,7 @@ def test_closed_loop_with_lidar_on_the_hardcore_track(gpu, oracle):
     made the same targets) and the final state the oracle's, as in test_control_gpu.py."""
     torch = gpu
     from gym_rem2d_amd import _lib
-    from test_control_gpu import check_final, make_env, population_rows
+    from env_harness import check_final, make_env, population_rows
     terrain, morphs = M.loop_population("cppn")
     T = R.Terrain.of(terrain)
     rays = R.bipedal_rays()

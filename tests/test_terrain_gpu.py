@@ -1,12 +1,10 @@
 """The step kernels on the ground the parity suite never stood on (tests/terrain_forge.py), on a real MI355X (pytest -m gpu).
 
-The protocol of tests/test_injected_state_gpu.py without the injection, with its comparator (read_state / mismatches over
-state_forge.masks / state_forge.snapshot): reset on the PLACED morphology, show the reset state equal to the oracle's, then
-compare with `==` after each of 60 single-step launches -- the 8 body columns, joint impulses, motor speed and limit state,
-every body's pair list in list order (static index, point count, manifold type, feature keys, normal and tangent impulses),
-position-iteration count, TOI events, reward, done, everdone, fitness, wall of death -- and in a second world after multi-step
-launches of 1, 9 and 50 steps.  Nobody is left out: the host half holds every input within the build's slots, any error bit on
-any creature fails the test, and handover_failures() == 0.
+The protocol of tests/test_injected_state_gpu.py without the injection, with its comparator (tests/replay.py: read_state / mismatches
+over state_forge.masks / state_forge.snapshot): reset on the PLACED morphology, show the reset state equal to the oracle's, then
+compare with `==` after each of 60 single-step launches and in a second world after multi-step launches of 1, 9 and 50 steps.
+Nobody is left out: the host half holds every input within the build's slots, any error bit on any creature fails the test, and
+handover_failures() == 0.
 
 The `rough` parametrisation of the older parity tests stays on the start pad (21 collinear points at y == 5.0); THIS module is
 where sloped ground, box obstacles of every kind, other pitches and origins and both ends of the polyline are compared.
@@ -22,19 +20,17 @@ Measured on an MI355X: 55 ids in 29 s, all passing; nothing differed, so no kern
 single-step worlds (ids): rough4 49 320 (7), hardcore4 43 680 (6), hardcore0 22 620 (3), saw 49 320 (7), stairs, vvalley, saw_fine,
 saw_coarse, saw_neg, shifted 15 000 (3) each, ends 52 800 (9): 11 terrains, 50 ids, 307 740 creature-steps.
 """
-import sys
-
 import numpy as np
 import pytest
 
+import replay as R
 import terrain_forge as G
-from test_injected_state_gpu import make_world, mismatches, read_state
 
 pytestmark = pytest.mark.gpu
 
 CONT = 1
 MULTI = (1, 9, 50)          # the second world's launches: compared after steps 1, 10 and 60
-ALL_FORMS = ("velpost", "two_launches", "fused_step_kernel")
+ALL_FORMS = ("velpost", "two_launches", "fused_step_kernel")      # this module's ids are replay.LAUNCH_FORMS' own names
 
 
 def _cases():
@@ -59,61 +55,23 @@ def _id(c):
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
-    from gym_rem2d_amd.world import BatchedWorld
-    return BatchedWorld
+    return R.need_gpu(world=True)
 
 
 @pytest.fixture(scope="module")
 def tally():
-    t = {}
-    yield t
-    out = sys.__stdout__
-    out.write("\nterrain parity: terrain | tests | creature-steps compared (single-step worlds)\n")
-    for name in G.TERRAINS:
-        if name in t:
-            out.write("  %-10s | %3d | %7d\n" % (name, t[name][0], t[name][1]))
-    out.write("  %d terrains, %d ids, %d creature-steps\n" % (len(t), sum(v[0] for v in t.values()), sum(v[1] for v in t.values())))
-    out.flush()
+    yield from R.tally("terrain parity (single-step worlds): terrain", G.TERRAINS)
 
 
 def run_bucket(gpu, run, flags, form, wide):
-    """-> creature-steps compared; raises AssertionError with every difference of the first step that has one."""
+    """-> creature-steps compared on the single-step world, through replay.replay: both worlds from reset, nobody left out, the
+    second one in launches of MULTI steps."""
     from gym_rem2d_amd import _lib
-    ctx, morph, prof = run["ctx"], run["ctx"].morph, run["profile"]
-    pair_slots = _lib.capacity(wide)[0]
-    everyone = np.ones(ctx.N, bool)
-    a = make_world(gpu, morph, prof, flags, form, wide)     # single-step launches
-    b = make_world(gpu, morph, prof, flags, form, wide)     # launches of MULTI steps
-    try:
-        assert a.contact_slots == pair_slots
-        for name, w in (("single", a), ("multi", b)):
-            st = read_state(w)
-            bad = mismatches(ctx, st, run["reset"], everyone, pair_slots, "%s reset" % name)
-            assert not bad and int(st["err"].max()) == 0, bad
-        marks = list(np.cumsum(MULTI))
-        assert marks[-1] == G.N_STEPS
-        for t in range(G.N_STEPS):
-            a.step(1)
-            worlds = [("single step %d" % (t + 1), a)]
-            if t + 1 in marks:
-                b.step(MULTI[marks.index(t + 1)])
-                worlds.append(("multi step %d" % (t + 1), b))
-            for where, w in worlds:
-                st = read_state(w)
-                bad = mismatches(ctx, st, run["steps"][t], everyone, pair_slots, where)
-                if (st["err"] != 0).any():
-                    bad.append("%s: error bits %s" % (where, st["err"][st["err"] != 0]))
-                assert not bad, "\n".join(bad)
-        assert a.handover_failures() == 0 and b.handover_failures() == 0
-        return G.N_STEPS * ctx.N
-    finally:
-        a.close()
-        b.close()
+    ctx = run["ctx"]
+    marks = list(np.cumsum(MULTI))
+    assert marks[-1] == G.N_STEPS
+    return R.replay(lambda: R.make_world(gpu, ctx.morph, run["profile"], flags, form, wide), ctx, run["reset"], [1] * G.N_STEPS,
+                    run["steps"], _lib.capacity(wide)[0], marks=marks)[0]
 
 
 @pytest.mark.parametrize("case", _cases(), ids=_id)
@@ -126,9 +84,7 @@ def test_terrain_bit_exact(gpu, oracle, tally, case):
     assert cov["over"] == 0 and (cov["n_edges"] > 0 or cov["n_boxes"] > 0)      # nobody left out, and the ground is met
     compared = sum(run_bucket(gpu, run, flags, form, wide) for run in runs)
     assert compared == G.N_STEPS * cov["creatures"]
-    t = tally.setdefault(terrain, [0, 0])
-    t[0], t[1] = t[0] + 1, t[1] + compared
-    print("%s: %d creature-steps compared" % (_id(case), compared))
+    R.count(tally, terrain, _id(case), compared)
 
 
 def test_set_terrain_refusals(gpu):
@@ -161,7 +117,7 @@ def test_set_terrain_refusals(gpu):
 def test_renderer_on_other_pitches_and_origins(gpu, terrain):
     """rem2d_world_render against the numpy pixel model on polylines whose pitch and x0 are not the reference's: the edge under a
     pixel is found from x0 and 1 / pitch (rem2d_raster.h r_shade)."""
-    import test_render_gpu as R
+    import env_harness as R
     from gym_rem2d_amd.env import BatchedModular2D
     from oracle import oracle as O
     O.build()

@@ -20,10 +20,10 @@ import numpy as np
 import pytest
 
 from conftest import oracle_terrain
+from replay import LAUNCH_FORMS, TICK_FORMS, need_gpu
 
 CONT = 1   # REM2D_FLAG_CONTINUOUS == oracle.FLAG_CONTINUOUS
-FORMS = {"step_train": (None, None), "velpost_per_step": (None, {"fuse_velpost": 1}), "two_launches_per_step": (None, {"fuse_velpost": 0}),
-         "train_128_lanes": (1, None), "per_step_128_lanes": (1, {"fuse_velpost": 0})}
+FORMS = {name: LAUNCH_FORMS[form] for name, form in TICK_FORMS.items()}      # id -> (tile shape for reset, launch options)
 
 
 # ---------------- host-side restatement of the split ----------------
@@ -221,13 +221,7 @@ def _reference(oracle, terrain, name, vel_iters=180):
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import __graft_entry__ as g
-    g.build()
-    from gym_rem2d_amd.world import BatchedWorld
-    return BatchedWorld
+    return need_gpu(world=True)
 
 
 def _compare(gpu, oracle, terrain, name, form, vel_iters=180):
