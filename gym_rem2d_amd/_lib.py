@@ -94,6 +94,8 @@ SENSE_MAX_RAYS = 64         # REM2D_SENSE_MAX_RAYS
 POLICY_ABI_VERSION = 1      # include/rem2d_policy.h
 POLICY_MAX_HIDDEN = 128     # REM2D_POLICY_MAX_HIDDEN
 POLICY_ACTIVATIONS = ("softsign", "relu")   # REM2D_POLICY_SOFTSIGN, REM2D_POLICY_RELU
+EPISODE_ABI_VERSION = 1     # include/rem2d_episode.h
+WHEN = {"done": 1, "frozen": 2, "steps": 4}   # REM2D_WHEN_DONE, REM2D_WHEN_FROZEN, REM2D_WHEN_STEPS
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -157,6 +159,11 @@ class Policy(C.Structure):
                 + [(k, C.c_int32) for k in ("n_sets", "reserved")]
                 + [(k, C.c_void_p) for k in ("w1", "b1", "w2", "b2", "index", "row_mask", "obs", "frac", "targets", "valid")]
                 + [("n_rows", C.c_int64)])
+
+
+class EpisodeOut(C.Structure):
+    """rem2d_episode_out (include/rem2d_episode.h): device arrays in population order the caller owns; any may be NULL."""
+    _fields_ = [(k, C.c_void_p) for k in ("reward", "done", "ended", "fitness", "steps", "episodes")]
 
 
 class Rem2dError(RuntimeError):
@@ -360,6 +367,12 @@ def lib(wide=False):
     L.rem2d_worlds_act.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Policy), C.c_void_p, C.c_void_p]
     if L.rem2d_policy_abi_version() != POLICY_ABI_VERSION:
         raise Rem2dError("%s: policy ABI version mismatch" % os.path.basename(path))
+    # episode boundaries (include/rem2d_episode.h)
+    L.rem2d_episode_abi_version.restype = C.c_int
+    L.rem2d_worlds_reset_where.argtypes = [C.POINTER(C.c_void_p), C.POINTER(Morph), C.c_int32, C.c_void_p, C.c_uint32, C.c_int32,
+                                           C.POINTER(EpisodeOut), C.c_int64, C.c_void_p]
+    if L.rem2d_episode_abi_version() != EPISODE_ABI_VERSION:
+        raise Rem2dError("%s: episode ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

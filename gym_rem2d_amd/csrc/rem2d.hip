@@ -43,6 +43,7 @@
 #include <rem2d_control.h> // the public header (include/); the quoted name below is the kernels' file beside this one
 #include <rem2d_sense.h>   // (likewise)
 #include <rem2d_policy.h>  // (likewise)
+#include <rem2d_episode.h> // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -100,6 +101,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_control.h"
 #include "rem2d_sense.h"
 #include "rem2d_policy.h"
+#include "rem2d_episode.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -1601,6 +1603,60 @@ extern "C" int rem2d_worlds_act(rem2d_world *const *worlds, int32_t n_worlds, co
     rc = policy_launch(p, (hipStream_t)stream);
     if (rc != REM2D_OK) return rc;
     return rem2d_worlds_control(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, stream);
+}
+
+// ---- episode boundaries (include/rem2d_episode.h, csrc/rem2d_episode.h) ----
+extern "C" int rem2d_episode_abi_version(void) { return REM2D_EPISODE_ABI_VERSION; }
+static_assert(sizeof(CtlTable) + sizeof(EpTable) + sizeof(EpArgs) + 16 <= 4096, "rem2d_reset_where_kernel: kernel arguments within the 4 KB kernarg limit");
+extern "C" int rem2d_worlds_reset_where(rem2d_world *const *worlds, const rem2d_morph *morphs, int32_t n_worlds, const uint8_t *mask_dev,
+                                        uint32_t when, int32_t max_steps, const rem2d_episode_out *out, int64_t n_rows, void *stream) {
+    // (arguments first, worlds after, everything before the first launch)
+    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "reset_where: no worlds");
+    if (!morphs) return fail(REM2D_E_INVALID, "reset_where: NULL morphologies");
+    if (when & ~(uint32_t)(REM2D_WHEN_DONE | REM2D_WHEN_FROZEN | REM2D_WHEN_STEPS))
+        return fail(REM2D_E_INVALID, "reset_where: unknown bits in `when` (" + std::to_string(when) + ")");
+    if ((when & REM2D_WHEN_STEPS) && max_steps <= 0)
+        return fail(REM2D_E_INVALID, "reset_where: REM2D_WHEN_STEPS needs max_steps > 0, not " + std::to_string(max_steps));
+    if (!mask_dev && when == 0)
+        return fail(REM2D_E_INVALID, "reset_where: no mask and no condition would reset every creature (that is rem2d_world_reset)");
+    if (n_rows < 0) return fail(REM2D_E_INVALID, "reset_where: negative row count");
+    for (int32_t i = 0; i < n_worlds; ++i)
+        if (!worlds[i]) return fail(REM2D_E_INVALID, "reset_where: world " + std::to_string(i) + " is NULL");
+    for (int32_t i = 0; i < n_worlds; ++i) {
+        const rem2d_morph *m = morphs + i;
+        if (!m->shape || !m->hx || !m->hy || !m->x || !m->y || !m->angle || !m->parent || !m->jround || !m->ax || !m->ay ||
+            !m->bx || !m->by || !m->torque || !m->lower || !m->upper || !m->amp || !m->phase || !m->freq || !m->offset ||
+            !m->istate)
+            return fail(REM2D_E_INVALID, "reset_where: morphology " + std::to_string(i) + " has NULL arrays");
+    }
+    for (int32_t i = 0; i < n_worlds; ++i) {
+        if (worlds[i]->cfg.lanes > 64) return fail(REM2D_E_INVALID, "reset_where: more than 64 lanes per creature");
+        if (worlds[i]->cfg.device != worlds[0]->cfg.device) return fail(REM2D_E_INVALID, "reset_where: the worlds must share a device");
+        if (!worlds[i]->haveReset) return fail(REM2D_E_STATE, "reset_where: rem2d_world_reset (or adopt) must be called first");
+    }
+    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
+    EpArgs A;
+    memset(&A, 0, sizeof(A));
+    A.mask = mask_dev;
+    if (out) A.out = *out;
+    A.nRows = n_rows;
+    A.when = when;
+    A.maxSteps = max_steps;
+    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
+        CtlTable Tb;
+        EpTable Te;
+        const int n = std::min(CTL_TABLE, (int)n_worlds - first);
+        const unsigned blocks = control_table(Tb, worlds, first, n);
+        memset(&Te, 0, sizeof(Te));
+        for (int i = 0; i < n; ++i) {
+            Te.w[i].M = morphs[first + i];
+            Te.w[i].env4 = worlds[first + i]->S.env4;
+        }
+        const unsigned per = CTL_THREADS / WAVE;
+        hipLaunchKernelGGL(rem2d_reset_where_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Te, A);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

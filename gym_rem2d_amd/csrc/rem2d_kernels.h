@@ -668,11 +668,11 @@ DEV void box_mass(float hx, float hy, float &mass, float &I) { // b2PolygonShape
     mass = m;
     I = Ib;
 }
-__global__ void rem2d_reset_kernel(State S, rem2d_morph M, int K) {
-    unsigned gl = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gl >= S.Lp) return;
-    unsigned env = gl / (unsigned)K, sub = gl % (unsigned)K;
-    bool real = env < S.nEnvs;
+// What a reset writes for arena lane gl = lane `sub` of creature `env` (real: a creature of the world, not padding): every per-lane
+// word, every pair slot and, on the root lane, every per-creature word.  One body for rem2d_reset_kernel (every lane of a world) and
+// rem2d_reset_where_kernel (rem2d_episode.h: the lanes of selected creatures), so that the two resets cannot drift.  St: whatever the
+// accessors of rem2d_state.h go through -- lane4, lane8, slot4, env4, env8, Lp, Np.
+template <class St> DEV void reset_lane(const St &S, const rem2d_morph &M, unsigned gl, unsigned env, unsigned sub, bool real) {
     int shape = real ? M.shape[gl] : 0;
     float hx = real ? M.hx[gl] : 0.0f, hy = real ? M.hy[gl] : 0.0f;
     float x = real ? M.x[gl] : 0.0f, y = real ? M.y[gl] : 0.0f, a = real ? M.angle[gl] : 0.0f;
@@ -729,6 +729,12 @@ __global__ void rem2d_reset_kernel(State S, rem2d_morph M, int K) {
         EI(E_FROZEN) = 0; EI(E_STEPS) = 0; EF(E_INVDT0) = 0.0f; EI(E_NEWFIX) = 1; EI(E_ERR) = 0;
         EI(E_POSITERS) = 0; EI(E_TOIEVENTS) = 0;
     }
+}
+__global__ void rem2d_reset_kernel(State S, rem2d_morph M, int K) {
+    unsigned gl = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gl >= S.Lp) return;
+    unsigned env = gl / (unsigned)K, sub = gl % (unsigned)K;
+    reset_lane(S, M, gl, env, sub, env < S.nEnvs);
 }
 
 #endif

@@ -50,6 +50,41 @@ class WallOfDeath:
         self.position += self.speed
 
 
+class Episodes:
+    """BatchedModular2D.episodes: the persistent population-order buffers reset_where() writes (include/rem2d_episode.h,
+    rem2d_episode_out), all ``[N]`` on the env's device.  ``reward`` float32 / ``done`` bool: every creature's reward / done as the last
+    step left them, read before anything was reset.  ``ended`` bool: whom the last call reset.  ``fitness`` float64 / ``steps`` int32:
+    evaluate()'s fitness and the length of the creature's LAST ended episode.  ``count`` int32: episodes ended since the upload."""
+    FIELDS = ("reward", "done", "ended", "fitness", "steps", "count")
+
+    def __init__(self, n, device):
+        z = torch.zeros
+        self.reward = z(n, dtype=torch.float32, device=device)
+        self.done = z(n, dtype=torch.bool, device=device)
+        self.ended = z(n, dtype=torch.bool, device=device)
+        self.fitness = z(n, dtype=torch.float64, device=device)
+        self.steps = z(n, dtype=torch.int32, device=device)
+        self.count = z(n, dtype=torch.int32, device=device)
+
+    def descriptor(self):
+        out = _lib.EpisodeOut()
+        out.reward, out.done, out.ended = self.reward.data_ptr(), self.done.data_ptr(), self.ended.data_ptr()
+        out.fitness, out.steps, out.episodes = self.fitness.data_ptr(), self.steps.data_ptr(), self.count.data_ptr()
+        return out
+
+
+def when_bits(when):
+    """The REM2D_WHEN_* bit set of a subset of ("done", "frozen", "steps") (a single name is accepted too)."""
+    if isinstance(when, str):
+        when = (when,)
+    bits = 0
+    for name in when or ():
+        if name not in _lib.WHEN:
+            raise ValueError("when: unknown condition %r (known: %s)" % (name, ", ".join(sorted(_lib.WHEN))))
+        bits |= _lib.WHEN[name]
+    return bits
+
+
 _GROUP_STREAMS = {}   # device -> the step-group streams of this process
 
 
@@ -99,6 +134,7 @@ class BatchedModular2D:
         self.robots = None
         self._reward = self._done = None
         self._policy = self._act_args = None   # set_policy()
+        self._episodes = self._episode_args = self._autoreset = None   # episodes / reset_where() / set_autoreset()
         self.last_episode = None      # evaluate.EpisodeReport of the population in place (None: no episode since its upload)
         over = launch_policy.read_overrides()   # (REM2D_MERGED_LAUNCH, REM2D_STEP_GROUPS, REM2D_GRAPH, REM2D_REBALANCE: read here, once)
         self.merged_launch = over.merged_launch   # False: step every lane bucket on its own stream instead of one merged grid
@@ -195,6 +231,8 @@ class BatchedModular2D:
         self._sense_rays = {}                                  # ray tables on the device, by content
         self._policy = None                                    # set_policy(): the device policy and its persistent buffers
         self._act_args = None
+        self._episodes = None                                  # reset_where()'s harvest buffers: made (zeroed) on first use after a reset
+        self._episode_args = None
         # how this population runs -- step groups, tile shape, train or per-step launches, rebalancing, which creatures share a
         # world -- is launch_policy.plan's decision, from the buckets' shapes, this env's settings and the REM2D_* overrides
         knobs = launch_policy.Knobs(self.step_groups, self.tile_shape, self.flags, self.options, self.rebalance_every,
@@ -418,6 +456,7 @@ class BatchedModular2D:
             self.group_streams = self.group_streams[:max(1, len(groups))]   # (the first is the caller's stream: None)
             self._group_args = None
             self._act_args = None   # (act() masks the rows no live world holds any more)
+            self._episode_args = None
         return alive_total
 
     @property
@@ -591,12 +630,94 @@ class BatchedModular2D:
 
     def step_policy(self, n_steps=1):
         """n_steps x (act(), step(1)), queued without any synchronisation: the closed loop with the controller on the device.
-        Returns what step() returns."""
+        Returns what step() returns.  With set_autoreset() in force every step is followed by reset_where(when, max_steps), and the
+        return value is ``(episodes.reward, episodes.done)`` of the last step: the terminal step's values on the rows that ended in
+        it, not the zeros their reset left in the arena."""
         out = self._reward, self._done
+        auto = self._autoreset
         for _ in range(int(n_steps)):
             self.act()
             out = self.step(1)
+            if auto is not None:
+                self.reset_where(when=auto[0], max_steps=auto[1])
+                out = self._episodes.reward, self._episodes.done
         return out
+
+    # ---- episode boundaries: a creature starts again the moment it ends (include/rem2d_episode.h) ----
+    @property
+    def episodes(self):
+        """The ``Episodes`` record of the population in place: made (all zero) on first use after a reset, written by reset_where()."""
+        if self._episodes is None:
+            if not self.worlds:
+                raise ValueError("episodes: no population in place (reset first)")
+            self._episodes = Episodes(self.n_envs, self.worlds[0][0].device)
+        return self._episodes
+
+    def reset_where(self, mask=None, when=(), max_steps=None):
+        """Begin a new episode for SOME creatures, in place, between two steps: those whose ``mask`` entry is set (bool / uint8
+        ``[N]`` on the env's device, population order; None = everyone) AND for whom one of the ``when`` conditions holds -- a subset
+        of ``("done", "frozen", "steps")``: the last step ended at the wall of death, evaluate()'s loop has ended, the episode has
+        run ``max_steps`` steps; empty = no condition.  One of the two must be given: everyone at once is reset*()'s job.  A selected
+        creature is rebuilt from its morphology exactly as a reset builds it and continues bit for bit like the same creature in a
+        freshly reset env; nobody else is touched.  Its joints are back under its own oscillators until the next act() /
+        set_joint_targets(): joint targets live in the controller words a reset rewrites.
+
+        One library call for all lane buckets and step groups (rem2d_worlds_reset_where), queued on the current stream; nothing
+        synchronises.  Before anything is reset, ``episodes`` receives every creature's reward / done of the last step, and for the
+        creatures that end, the fitness and length of the episode; their ``count`` goes up by one.  Returns ``episodes.ended``, the
+        persistent bool ``[N]`` buffer of whom this call reset (clone what must last).
+
+        Needs the device morphology of the last reset: after compact() the worlds hold adopted creatures without one, and the call
+        raises ValueError."""
+        if not self.worlds:
+            raise ValueError("reset_where: no population in place (reset first)")
+        bits = when_bits(when)
+        steps = 0 if max_steps is None else int(max_steps)
+        if bits & _lib.WHEN["steps"] and steps <= 0:
+            raise ValueError("reset_where: when 'steps' needs max_steps > 0")
+        if mask is None and bits == 0:
+            raise ValueError("reset_where: neither a mask nor a condition: that would reset everyone, which is reset()'s job")
+        if mask is not None:
+            dev = self.worlds[0][0].device
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("reset_where: mask must be a torch.bool or torch.uint8 tensor")
+            if tuple(mask.shape) != (self.n_envs,) or not mask.is_contiguous():
+                raise ValueError("reset_where: mask must be a contiguous tensor of one entry per creature [%d], not %s"
+                                 % (self.n_envs, list(mask.shape)))
+            if mask.device != dev:
+                raise ValueError("reset_where: mask must be on %s, not %s" % (dev, mask.device))
+        if self._episode_args is None:
+            if self._compacted or any(getattr(w, "_morph_dev", None) is None for w in self._control_worlds()):
+                raise ValueError("reset_where: compact() has moved creatures into adopted worlds, which keep no device morphology to "
+                                 "reset from -- upload the population again (reset*) instead of compact() where episodes restart")
+            worlds = self._control_worlds()
+            morphs = (_lib.Morph * len(worlds))()
+            for m, w in zip(morphs, worlds):
+                for k in _lib.MORPH_FIELDS:
+                    setattr(m, k, w._morph_dev[k].data_ptr())
+            self._episode_args = (worlds, _lib.world_array(worlds), morphs, self.episodes.descriptor())
+        worlds, arr, morphs, out = self._episode_args
+        self._episode_mask = mask   # (the tensor the queued kernel reads)
+        w0 = worlds[0]
+        _lib.check(w0.L.rem2d_worlds_reset_where(arr, morphs, len(worlds), None if mask is None else mask.data_ptr(), bits, steps,
+                                                 C.byref(out), self.n_envs, w0._stream()), w0.wide)
+        return self._episodes.ended
+
+    def set_autoreset(self, when=("done", "steps"), max_steps=4800):
+        """Let step_policy() follow every step with ``reset_where(when=when, max_steps=max_steps)``: a creature whose episode ends
+        starts the next one at once, on the device, and ``episodes`` collects the results.  ``when``: a non-empty subset of
+        ("done", "frozen", "steps"); ``max_steps``: the episode length for "steps" (gym's TimeLimit).  ``set_autoreset(None)``
+        switches it off.  step(), observe() and act() are not affected."""
+        if when is None:
+            self._autoreset = None
+            return
+        bits = when_bits(when)
+        if bits == 0:
+            raise ValueError("set_autoreset: `when` must name at least one condition (None switches auto-reset off)")
+        steps = 0 if max_steps is None else int(max_steps)
+        if bits & _lib.WHEN["steps"] and steps <= 0:
+            raise ValueError("set_autoreset: when 'steps' needs max_steps > 0")
+        self._autoreset = ((when,) if isinstance(when, str) else tuple(when), steps)
 
     def render(self, creatures=None, mode='rgb_array', **kw):
         """Frames of the creatures as they stand now: uint8 [n, H, W, 3] on the device (gym's rgb_array layout, one image per
