@@ -96,6 +96,7 @@ POLICY_MAX_HIDDEN = 128     # REM2D_POLICY_MAX_HIDDEN
 POLICY_ACTIVATIONS = ("softsign", "relu")   # REM2D_POLICY_SOFTSIGN, REM2D_POLICY_RELU
 EPISODE_ABI_VERSION = 1     # include/rem2d_episode.h
 WHEN = {"done": 1, "frozen": 2, "steps": 4}   # REM2D_WHEN_DONE, REM2D_WHEN_FROZEN, REM2D_WHEN_STEPS
+STREAM_ABI_VERSION = 1      # include/rem2d_stream.h
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -164,6 +165,16 @@ class Policy(C.Structure):
 class EpisodeOut(C.Structure):
     """rem2d_episode_out (include/rem2d_episode.h): device arrays in population order the caller owns; any may be NULL."""
     _fields_ = [(k, C.c_void_p) for k in ("reward", "done", "ended", "fitness", "steps", "episodes")]
+
+
+class Feed(C.Structure):
+    """rem2d_feed (include/rem2d_stream.h): the pending creatures of one lane count, device memory the caller owns."""
+    _fields_ = [("M", Morph), ("id", C.c_void_p), ("count", C.c_int32), ("lanes", C.c_int32), ("cursor", C.c_void_p)]
+
+
+class StreamOut(C.Structure):
+    """rem2d_stream_out (include/rem2d_stream.h): device arrays indexed by id the caller owns; any may be NULL."""
+    _fields_ = [(k, C.c_void_p) for k in ("fitness", "steps", "err", "finished")]
 
 
 class Rem2dError(RuntimeError):
@@ -373,6 +384,12 @@ def lib(wide=False):
                                            C.POINTER(EpisodeOut), C.c_int64, C.c_void_p]
     if L.rem2d_episode_abi_version() != EPISODE_ABI_VERSION:
         raise Rem2dError("%s: episode ABI version mismatch" % os.path.basename(path))
+    # streaming evaluation (include/rem2d_stream.h)
+    L.rem2d_stream_abi_version.restype = C.c_int
+    L.rem2d_worlds_refill.argtypes = [C.POINTER(C.c_void_p), C.POINTER(Morph), C.c_int32, C.POINTER(Feed), C.c_void_p, C.c_uint32,
+                                      C.c_int32, C.POINTER(StreamOut), C.c_int64, C.c_int64, C.c_void_p]
+    if L.rem2d_stream_abi_version() != STREAM_ABI_VERSION:
+        raise Rem2dError("%s: stream ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

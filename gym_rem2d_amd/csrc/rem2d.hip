@@ -44,6 +44,7 @@
 #include <rem2d_sense.h>   // (likewise)
 #include <rem2d_policy.h>  // (likewise)
 #include <rem2d_episode.h> // (likewise)
+#include <rem2d_stream.h>  // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -102,6 +103,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_sense.h"
 #include "rem2d_policy.h"
 #include "rem2d_episode.h"
+#include "rem2d_stream.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -1654,6 +1656,86 @@ extern "C" int rem2d_worlds_reset_where(rem2d_world *const *worlds, const rem2d_
         }
         const unsigned per = CTL_THREADS / WAVE;
         hipLaunchKernelGGL(rem2d_reset_where_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Te, A);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+
+// ---- streaming evaluation (include/rem2d_stream.h, csrc/rem2d_stream.h) ----
+extern "C" int rem2d_stream_abi_version(void) { return REM2D_STREAM_ABI_VERSION; }
+static_assert(sizeof(CtlTable) + sizeof(StTable) + sizeof(StArgs) + 16 <= 4096, "rem2d_refill_kernel: kernel arguments within the 4 KB kernarg limit");
+static bool morph_complete(const rem2d_morph *m) {
+    return m->shape && m->hx && m->hy && m->x && m->y && m->angle && m->parent && m->jround && m->ax && m->ay && m->bx && m->by &&
+           m->torque && m->lower && m->upper && m->amp && m->phase && m->freq && m->offset && m->istate;
+}
+extern "C" int rem2d_worlds_refill(rem2d_world *const *worlds, const rem2d_morph *morphs, int32_t n_worlds, const rem2d_feed *feeds,
+                                   int32_t *occupant_dev, uint32_t when, int32_t max_steps, const rem2d_stream_out *out, int64_t n_ids,
+                                   int64_t n_rows, void *stream) {
+    // (arguments first, worlds after, everything before the first launch)
+    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "refill: no worlds");
+    if (!morphs) return fail(REM2D_E_INVALID, "refill: NULL morphologies");
+    if (!feeds) return fail(REM2D_E_INVALID, "refill: NULL feeds");
+    if (!occupant_dev) return fail(REM2D_E_INVALID, "refill: NULL occupant array");
+    if (when & ~(uint32_t)(REM2D_WHEN_DONE | REM2D_WHEN_FROZEN | REM2D_WHEN_STEPS))
+        return fail(REM2D_E_INVALID, "refill: unknown bits in `when` (" + std::to_string(when) + ")");
+    if (when == 0) return fail(REM2D_E_INVALID, "refill: no condition (`when` == 0): nobody's episode could end");
+    if ((when & REM2D_WHEN_STEPS) && max_steps <= 0)
+        return fail(REM2D_E_INVALID, "refill: REM2D_WHEN_STEPS needs max_steps > 0, not " + std::to_string(max_steps));
+    if (n_rows < 0) return fail(REM2D_E_INVALID, "refill: negative row count");
+    if (n_ids < 0) return fail(REM2D_E_INVALID, "refill: negative id count");
+    for (int32_t i = 0; i < n_worlds; ++i)
+        if (!worlds[i]) return fail(REM2D_E_INVALID, "refill: world " + std::to_string(i) + " is NULL");
+    for (int32_t i = 0; i < n_worlds; ++i)
+        if (!morph_complete(morphs + i)) return fail(REM2D_E_INVALID, "refill: morphology " + std::to_string(i) + " has NULL arrays");
+    for (int32_t i = 0; i < n_worlds; ++i) {
+        const rem2d_feed *f = feeds + i;
+        if (f->count < 0) return fail(REM2D_E_INVALID, "refill: feed " + std::to_string(i) + " has a negative count");
+        if (!f->cursor) return fail(REM2D_E_INVALID, "refill: feed " + std::to_string(i) + " has no cursor");
+        if (f->count > 0 && (!morph_complete(&f->M) || !f->id))
+            return fail(REM2D_E_INVALID, "refill: feed " + std::to_string(i) + " has pending creatures and NULL arrays");
+    }
+    for (int32_t i = 0; i < n_worlds; ++i) {
+        const rem2d_world *w = worlds[i];
+        if (w->cfg.lanes > 64) return fail(REM2D_E_INVALID, "refill: more than 64 lanes per creature");
+        if (w->cfg.device != worlds[0]->cfg.device) return fail(REM2D_E_INVALID, "refill: the worlds must share a device");
+        if (feeds[i].lanes != w->cfg.lanes)
+            return fail(REM2D_E_INVALID, "refill: feed " + std::to_string(i) + " holds creatures of " + std::to_string(feeds[i].lanes) +
+                                             " lanes, its world creatures of " + std::to_string(w->cfg.lanes));
+    }
+    for (int32_t i = 0; i < n_worlds; ++i) {
+        const rem2d_world *w = worlds[i];
+        if (!tile_shape(w->tileShape).flex)
+            return fail(REM2D_E_STATE, "refill: world " + std::to_string(i) + " is on the static tile shape " + std::to_string(w->tileShape) +
+                                           ": the tile table of shapes 0 and 4 is planned from the joints of the creatures in it, "
+                                           "so its slots cannot take other creatures (use a flexible shape: 1, 2 or 3)");
+        if (!w->haveReset) return fail(REM2D_E_STATE, "refill: rem2d_world_reset (or adopt) must be called first");
+    }
+    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
+    StArgs A;
+    memset(&A, 0, sizeof(A));
+    A.occupant = occupant_dev;
+    if (out) A.out = *out;
+    A.nIds = n_ids;
+    A.nRows = n_rows;
+    A.when = when;
+    A.maxSteps = max_steps;
+    for (int first = 0; first < n_worlds; first += STREAM_TABLE) {
+        CtlTable Tb;
+        StTable Ts;
+        const int n = std::min(STREAM_TABLE, (int)n_worlds - first);
+        const unsigned blocks = control_table(Tb, worlds, first, n);
+        memset(&Ts, 0, sizeof(Ts));
+        for (int i = 0; i < n; ++i) {
+            const rem2d_feed &f = feeds[first + i];
+            Ts.w[i].M = morphs[first + i];
+            Ts.w[i].env4 = worlds[first + i]->S.env4;
+            Ts.w[i].F = f.M;
+            Ts.w[i].id = f.id;
+            Ts.w[i].cursor = f.cursor;
+            Ts.w[i].count = f.count;
+        }
+        const unsigned per = CTL_THREADS / WAVE;
+        hipLaunchKernelGGL(rem2d_refill_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Ts, A);
         HIP_TRY(hipGetLastError());
     }
     return REM2D_OK;

@@ -85,6 +85,57 @@ def when_bits(when):
     return bits
 
 
+class Stream:
+    """BatchedModular2D.stream: the record of a streamed evaluation (include/rem2d_stream.h), on the env's device.  Indexed by the
+    population's ids, ``[n_total]``: ``fitness`` float64 / ``steps`` int32 / ``err`` int32 (REM2D_ERR_* bits) of a creature's episode,
+    written when refill() finds it ended, and ``finished`` bool.  ``occupant`` int32 ``[slots]``: the id of the creature in each slot
+    (population-row order of the env), -1 = retired.  ``cursors`` int32, one per lane bucket: pending creatures handed out so far (it
+    may run past the bucket's pending count: ``handed_out()`` clamps it)."""
+
+    def __init__(self, n_total, occupant, pending, device):
+        z = torch.zeros
+        self.fitness = z(n_total, dtype=torch.float64, device=device)
+        self.steps = z(n_total, dtype=torch.int32, device=device)
+        self.err = z(n_total, dtype=torch.int32, device=device)
+        self.finished = z(n_total, dtype=torch.bool, device=device)
+        self.occupant = occupant
+        self.pending = list(pending)                  # pending creatures per lane bucket (host)
+        self.cursors = z(len(self.pending), dtype=torch.int32, device=device)
+
+    def descriptor(self):
+        out = _lib.StreamOut()
+        out.fitness, out.steps, out.err, out.finished = (self.fitness.data_ptr(), self.steps.data_ptr(), self.err.data_ptr(),
+                                                         self.finished.data_ptr())
+        return out
+
+    def handed_out(self):
+        """Pending creatures handed out so far, per lane bucket (a host read: it waits for the queued calls)."""
+        return [min(int(c), n) for c, n in zip(self.cursors.cpu().tolist(), self.pending)]
+
+
+def stream_slots(counts, lanes, slots):
+    """How many of ``slots`` each lane bucket gets (reset_stream): proportional to the buckets' creature counts, the slots left over
+    by the whole parts going one by one to the bucket that is furthest below its share (largest remainder; ties to the earlier
+    bucket), never more than the bucket has creatures.  Every bucket starts from a floor of ``min(count, 64 // lanes)`` -- one whole
+    wavefront of slots -- where ``slots`` covers those floors, else from one slot: fewer slots than buckets raise ValueError."""
+    counts = [int(c) for c in counts]
+    if any(c <= 0 for c in counts):
+        raise ValueError("reset_stream: an empty lane bucket")
+    if slots < len(counts):
+        raise ValueError("reset_stream: slots = %d is below the number of lane buckets (%d): every bucket needs a slot"
+                         % (slots, len(counts)))
+    total = sum(counts)
+    slots = min(int(slots), total)
+    have = [min(c, max(1, 64 // K)) for c, K in zip(counts, lanes)]
+    if sum(have) > slots:
+        have = [1] * len(counts)
+    share = [slots * c / float(total) for c in counts]
+    for _ in range(slots - sum(have)):
+        k = max((k for k in range(len(counts)) if have[k] < counts[k]), key=lambda k: (share[k] - have[k], -k))
+        have[k] += 1
+    return have
+
+
 _GROUP_STREAMS = {}   # device -> the step-group streams of this process
 
 
@@ -135,6 +186,7 @@ class BatchedModular2D:
         self._reward = self._done = None
         self._policy = self._act_args = None   # set_policy()
         self._episodes = self._episode_args = self._autoreset = None   # episodes / reset_where() / set_autoreset()
+        self._stream_rec = self._refill_args = None                    # reset_stream() / refill() / stream
         self.last_episode = None      # evaluate.EpisodeReport of the population in place (None: no episode since its upload)
         over = launch_policy.read_overrides()   # (REM2D_MERGED_LAUNCH, REM2D_STEP_GROUPS, REM2D_GRAPH, REM2D_REBALANCE: read here, once)
         self.merged_launch = over.merged_launch   # False: step every lane bucket on its own stream instead of one merged grid
@@ -233,13 +285,10 @@ class BatchedModular2D:
         self._act_args = None
         self._episodes = None                                  # reset_where()'s harvest buffers: made (zeroed) on first use after a reset
         self._episode_args = None
+        self._stream_rec = self._refill_args = None            # (a streamed evaluation ends with the upload that replaces it)
         # how this population runs -- step groups, tile shape, train or per-step launches, rebalancing, which creatures share a
         # world -- is launch_policy.plan's decision, from the buckets' shapes, this env's settings and the REM2D_* overrides
-        knobs = launch_policy.Knobs(self.step_groups, self.tile_shape, self.flags, self.options, self.rebalance_every,
-                                    self.BIG_POPULATION, self.TRAIN128_MAX, self.TRAIN128_UNIFORM, self.REBALANCE_EVERY,
-                                    self.MAX_WORLD_LANES, _lib.MAX_STEP_GROUPS, _lib.MAX_WORLDS_PER_STEP)
-        plan = self._plan = launch_policy.plan([launch_policy.bucket(m) for m, _ in batches], n_envs, knobs,
-                                               launch_policy.read_overrides())
+        plan = self._plan = self._make_plan(batches, n_envs)
         # (the names bench.py, tests and tools read)
         self._tile_shape_used, self._tile_shape_by_lanes, self._launch_options = plan.tile_shape, plan.tile_shape_by_lanes, plan.launch_options
         self._world_flags, self._rebalance_steps = plan.world_flags, plan.rebalance_steps
@@ -273,6 +322,12 @@ class BatchedModular2D:
             # set_joint_targets() find the population row of a creature through the same index (decided here, on the host array)
             w, idx = self.worlds[0]
             w.set_outputs(self._reward, self._done, idx.to(torch.int32))
+
+    def _make_plan(self, batches, n_envs):
+        knobs = launch_policy.Knobs(self.step_groups, self.tile_shape, self.flags, self.options, self.rebalance_every,
+                                    self.BIG_POPULATION, self.TRAIN128_MAX, self.TRAIN128_UNIFORM, self.REBALANCE_EVERY,
+                                    self.MAX_WORLD_LANES, _lib.MAX_STEP_GROUPS, _lib.MAX_WORLDS_PER_STEP)
+        return launch_policy.plan([launch_policy.bucket(m) for m, _ in batches], n_envs, knobs, launch_policy.read_overrides())
 
     def _world_options(self):
         return self._plan.world_options
@@ -403,6 +458,9 @@ class BatchedModular2D:
         group.  Fitness / steps / error bits of the dropped creatures stay readable through the population-order
         properties.  Buckets with fewer than ``min_envs`` creatures are left alone.  Returns the number of creatures
         still being stepped."""
+        if self._stream_rec is not None:
+            raise ValueError("compact: this env streams its population through a fixed window of slots (reset_stream): a finished "
+                             "creature's slot is refilled by refill(), there is nothing to compact")
         by_lanes = {}
         for wi, (w, idx) in enumerate(self.worlds):
             if wi not in self._inactive:
@@ -718,6 +776,98 @@ class BatchedModular2D:
         if bits & _lib.WHEN["steps"] and steps <= 0:
             raise ValueError("set_autoreset: when 'steps' needs max_steps > 0")
         self._autoreset = ((when,) if isinstance(when, str) else tuple(when), steps)
+
+    # ---- streaming evaluation: a population of any size through a fixed window of slots (include/rem2d_stream.h) ----
+    def reset_stream(self, batches, n_total, slots):
+        """Begin a streamed evaluation of a whole population: ``batches`` as reset_batches takes them -- [(Morphology, ids)] per lane
+        bucket, ``ids`` the creatures' indices in [0, n_total) -- of which only ``slots`` creatures are in an arena at any time.  Per
+        lane bucket the first ``slots_k`` creatures (``stream_slots``) are uploaded as reset_batches uploads them and the others
+        become the bucket's feed on the device, from which refill() takes the next one whenever a slot's creature has finished.  The
+        env then holds ``slots`` creatures (``n_envs``, reward / done, observe() rows: the slots), and ``stream`` holds the results
+        by id.  A slot takes creatures of its own lane count only.
+
+        The launch plan is launch_policy.plan's as always.  The worlds must be on a flexible tile shape (1, 2, 3: its tile table does
+        not depend on the creatures in it); a plan on the static shapes 0 or 4 (fixed-morphology populations beyond 2 048 blocks
+        per step group, REM2D_TILE_SHAPE) raises ValueError -- set ``env.tile_shape = 3`` there."""
+        batches = [(m, np.asarray(idx, dtype=np.int64)) for m, idx in batches]
+        n_total = int(n_total)
+        if sum(m.n_envs for m, _ in batches) != n_total or any(len(idx) != m.n_envs for m, idx in batches):
+            raise ValueError("reset_stream: the batches must hold every creature of the population (%d) once" % n_total)
+        if len({m.lanes for m, _ in batches}) != len(batches):
+            raise ValueError("reset_stream: one batch per lane count")
+        per = stream_slots([m.n_envs for m, _ in batches], [m.lanes for m, _ in batches], int(slots))
+        n_slots = sum(per)
+        first, rows, at = [], [], 0
+        for (m, idx), k in zip(batches, per):
+            first.append((m if k == m.n_envs else m.take(np.arange(k)), np.arange(at, at + k)))
+            rows.append(np.arange(at, at + k))
+            at += k
+        plan = self._make_plan(first, n_slots)
+        for m, _ in first:
+            shape = plan.tile_shape_by_lanes.get(m.lanes, plan.eff_tile_shape)
+            if shape in (0, 4):
+                raise ValueError("reset_stream: the launch plan puts the %d-lane bucket on the static tile shape %d, whose tile table "
+                                 "is planned from the joints of the creatures in it -- its slots cannot take other creatures (set "
+                                 "env.tile_shape = 3, or drop the REM2D_TILE_SHAPE override)" % (m.lanes, shape))
+        self.trees = self.robots = None
+        self._upload(first, n_slots)
+        dev = self.worlds[0][0].device
+        occupant = torch.full((n_slots,), -1, dtype=torch.int32, device=dev)
+        feeds = {}
+        rec = Stream(n_total, occupant, [m.n_envs - k for (m, _), k in zip(batches, per)], dev)
+        for b, ((m, idx), k, r) in enumerate(zip(batches, per, rows)):
+            occupant[torch.as_tensor(r, dtype=torch.long, device=dev)] = torch.as_tensor(idx[:k], dtype=torch.int32, device=dev)
+            feed = _lib.Feed()
+            feed.count, feed.lanes = m.n_envs - k, m.lanes
+            feed.cursor = rec.cursors[b:b + 1].data_ptr()
+            keep = None
+            if feed.count:
+                rest = m.take(np.arange(k, m.n_envs))
+                keep = {f: torch.from_numpy(np.ascontiguousarray(rest.arrays[f])).to(dev) for f in _lib.MORPH_FIELDS}
+                keep["id"] = torch.as_tensor(idx[k:], dtype=torch.int32, device=dev)
+                for f in _lib.MORPH_FIELDS:
+                    setattr(feed.M, f, keep[f].data_ptr())
+                feed.id = keep["id"].data_ptr()
+            feeds[m.lanes] = (feed, keep)   # (the tensors the queued kernels read)
+        rec.feeds = feeds
+        self._stream_rec = rec
+
+    @property
+    def stream(self):
+        """The ``Stream`` record of the streamed evaluation in place (reset_stream); dropped by every upload."""
+        if self._stream_rec is None:
+            raise ValueError("stream: no streamed evaluation in place (reset_stream first)")
+        return self._stream_rec
+
+    def refill(self, when=("frozen", "steps"), max_steps=None):
+        """Between two steps of a streamed evaluation: every slot whose creature's episode has ended -- one of the ``when``
+        conditions holds, as in reset_where -- has that creature's fitness / steps / error bits written to ``stream`` under its id,
+        and takes the next pending creature of its lane bucket, rebuilt exactly as a reset builds it; with nobody pending the slot is
+        retired (frozen, ``occupant`` -1).  One library call for all worlds (rem2d_worlds_refill), queued on the current stream;
+        nothing synchronises.  Returns ``stream``.  An attached policy is left alone: a row keeps its controller set."""
+        rec = self._stream_rec
+        if rec is None:
+            raise ValueError("refill: no streamed evaluation in place (reset_stream first)")
+        bits = when_bits(when)
+        steps = 0 if max_steps is None else int(max_steps)
+        if bits == 0:
+            raise ValueError("refill: `when` must name at least one condition")
+        if bits & _lib.WHEN["steps"] and steps <= 0:
+            raise ValueError("refill: when 'steps' needs max_steps > 0")
+        if self._refill_args is None:
+            worlds = self._control_worlds()
+            morphs = (_lib.Morph * len(worlds))()
+            feeds = (_lib.Feed * len(worlds))()
+            for i, w in enumerate(worlds):
+                for k in _lib.MORPH_FIELDS:
+                    setattr(morphs[i], k, w._morph_dev[k].data_ptr())
+                feeds[i] = rec.feeds[w.lanes][0]
+            self._refill_args = (worlds, _lib.world_array(worlds), morphs, feeds, rec.descriptor())
+        worlds, arr, morphs, feeds, out = self._refill_args
+        w0 = worlds[0]
+        _lib.check(w0.L.rem2d_worlds_refill(arr, morphs, len(worlds), feeds, rec.occupant.data_ptr(), bits, steps, C.byref(out),
+                                            rec.fitness.numel(), self.n_envs, w0._stream()), w0.wide)
+        return rec
 
     def render(self, creatures=None, mode='rgb_array', **kw):
         """Frames of the creatures as they stand now: uint8 [n, H, W, 3] on the device (gym's rgb_array layout, one image per

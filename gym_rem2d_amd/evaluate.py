@@ -93,7 +93,11 @@ def check_errors(env, on_error="raise"):
     creature), "ignore" returns it in the mask.  The capacity bits (REM2D_ERR_PAIR_OVERFLOW / _SOLVER_OVERFLOW) -- on_error:
     "raise" -> SolverOverflow with the creatures' real codes; "warn" -> warnings.warn and return the mask; "ignore" -> return the
     mask (every non-zero code)."""
-    err = env.errors()
+    return judge_errors(env.errors(), on_error)
+
+
+def judge_errors(err, on_error="raise"):
+    """check_errors' verdict on REM2D_ERR_* codes already read (int32 [N]; run_stream: ``stream.err``, indexed by id)."""
     bad = err != 0
     if on_error != "ignore" and bool(bad.any()):
         hand = (err & _lib.ERR_HANDOVER) != 0
@@ -270,21 +274,105 @@ def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_e
     return env.fitness.clone()
 
 
+def run_stream(env, batches, n_total, slots, max_steps=EPISODE_CAP, chunk=100, on_error="fallback"):
+    """run_episode for a population that does not get an arena per creature: ``batches`` ([(Morphology, ids)] per lane bucket, as
+    reset_batches takes them) are streamed through ``slots`` slots of ``env`` (BatchedModular2D.reset_stream) -- ``step(chunk)``,
+    ``refill()``, until every creature has finished; one small read per chunk.  A creature's episode ends when its fitness is final
+    (REM2D_F_FROZEN) or after ``max_steps`` steps, whichever a refill() finds first; its slot goes to the next pending creature of its
+    lane count.  Returns fitness[n_total] (float64 tensor on the env's device), the same values run_episode gives the same
+    population uploaded as a whole: creatures are independent.
+
+    The env needs REM2D_FLAG_SKIP_FROZEN (EVAL_FLAGS): a retired slot must stop costing steps.  ``max_steps`` must be a multiple of
+    ``chunk``: the step limit is judged between two step calls, and a creature loaded at a call boundary has to meet it exactly.
+    on_error: "raise" / "warn" / "ignore" judge ``stream.err`` as check_errors judges errors() (``env.last_episode`` is None after
+    them); "fallback" / "penalty" evaluate the creatures with any error bit -- a failed hand-over of the step train, a capacity
+    overflow -- again from reset in a fresh env on per-step launches through run_episode(on_error=...), which resolves overflow in
+    the wide build and applies the penalty, and leave the EpisodeReport (by id) in ``env.last_episode``."""
+    from .env import BatchedModular2D
+    if on_error not in ("fallback", "penalty", "raise", "warn", "ignore"):
+        raise ValueError("on_error must be 'fallback', 'penalty', 'raise', 'warn' or 'ignore', not %r" % (on_error,))
+    if not env.flags & _lib.FLAG_SKIP_FROZEN:
+        raise ValueError("run_stream: the env needs REM2D_FLAG_SKIP_FROZEN (flags=evaluate.EVAL_FLAGS): retired slots must stop being stepped")
+    max_steps, chunk = int(max_steps), int(chunk)
+    if chunk <= 0 or max_steps <= 0 or max_steps % chunk != 0:
+        raise ValueError("run_stream: max_steps (%d) must be a positive multiple of chunk (%d): the step limit is judged between step "
+                         "calls, and a creature loaded at a call boundary must meet it exactly" % (max_steps, chunk))
+    batches = [(m, np.asarray(idx, dtype=np.int64)) for m, idx in batches]
+    env.reset_stream(batches, n_total, slots)
+    st = env.stream
+    # every slot hands on at least one creature per max_steps steps: more chunks than this and something is wrong
+    limit = (max_steps // chunk) * (int(n_total) + 1)
+    policy, env.on_handover = env.on_handover, "flag"   # (flagged creatures are dealt with below, like run_episode_masked's)
+    try:
+        for _ in range(limit):
+            env.step(chunk)
+            env.refill(when=("frozen", "steps"), max_steps=max_steps)
+            if bool(st.finished.all()):
+                break
+        else:
+            raise _lib.Rem2dError("run_stream: %d creature(s) unfinished after %d chunks" % (int((~st.finished).sum()), limit))
+    finally:
+        env.on_handover = policy
+    env.handover_failures(clear=True)
+    fit, err = st.fitness.clone(), st.err.clone()
+    if on_error in ("raise", "warn", "ignore"):
+        env.last_episode = None
+        judge_errors(err, on_error)
+        return fit
+    bad = torch.nonzero(err != 0).flatten().cpu().numpy()
+    handover, overflow, unresolved = [], [], []
+    if bad.size:
+        opts = dict(env.options)
+        opts.pop("train_fault", None)
+        opts["fuse_velpost"] = 1                      # per-step launches: no hand-over between workgroups exists there
+        again = BatchedModular2D(hardcore=env.hardcore, flat=env.flat, seed=env._seed, device=env.device, flags=env.flags,
+                                 wide=env.wide, options=opts, on_handover="flag")
+        again.terrain = env._terrain()
+        sub = []
+        for m, idx in batches:
+            sel = np.nonzero(np.isin(idx, bad))[0]
+            if sel.size:
+                sub.append((m.take(sel), np.searchsorted(bad, idx[sel]).tolist()))
+        again.reset_batches(sub, int(bad.size))
+        try:
+            fit2 = run_episode(again, max_steps, chunk, on_error=on_error, compact=False)
+        except SolverOverflow as e:
+            raise SolverOverflow([int(bad[i]) for i in e.indices], e.codes)
+        finally:
+            report = again.last_episode
+            again.close()
+        where = torch.as_tensor(bad, dtype=torch.long, device=fit.device)
+        fit.index_copy_(0, where, fit2.to(fit.device))
+        handover = sorted(int(i) for i in bad[(err[where] & _lib.ERR_HANDOVER).cpu().numpy() != 0])
+        err.index_copy_(0, where, report.codes.to(err.device))
+        handover = sorted(set(handover) | {int(bad[i]) for i in report.handover})
+        overflow, unresolved = [int(bad[i]) for i in report.overflow], [int(bad[i]) for i in report.unresolved]
+    env.last_episode = EpisodeReport(err, handover, overflow, unresolved)
+    return fit
+
+
 def evaluate_population(individuals, tree_depth=None, env=None, max_steps=EPISODE_CAP, workers=None, on_error="fallback",
-                        **env_kw):
+                        slots=None, **env_kw):
     """Batched stand-in for ``toolbox.map(toolbox.evaluate, population)``: list of floats.
     The genotype -> phenotype step runs natively on ``workers`` host threads (encode.encode_native).
     on_error: what to do when a creature overflowed the engine's contact capacity ("fallback": re-evaluate it in the
     wide build and raise only if even that overflows, the default | "penalty": the same without ever raising, see
-    run_episode | "raise" | "warn" | "ignore")."""
+    run_episode | "raise" | "warn" | "ignore").
+    slots: None (the default) uploads every individual; a number below ``len(individuals)`` streams the population through that
+    many arena slots instead (run_stream: the same fitness from a fraction of the device memory; the env needs EVAL_FLAGS and
+    max_steps a multiple of 100)."""
     from .encode import encode_native
     from .env import BatchedModular2D
     own = env is None
     if own:
         env_kw.setdefault("flags", EVAL_FLAGS)
         env = BatchedModular2D(**env_kw)
-    env.reset_batches(encode_native(individuals, tree_depth, n_threads=workers or 0), len(individuals))
-    fit = run_episode(env, max_steps, on_error=on_error).cpu().tolist()
+    batches = encode_native(individuals, tree_depth, n_threads=workers or 0)
+    if slots is not None and len(individuals) > slots:
+        fit = run_stream(env, batches, len(individuals), slots, max_steps, on_error=on_error).cpu().tolist()
+    else:
+        env.reset_batches(batches, len(individuals))
+        fit = run_episode(env, max_steps, on_error=on_error).cpu().tolist()
     if own:
         env.close()
     return fit
