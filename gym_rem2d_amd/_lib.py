@@ -97,6 +97,8 @@ POLICY_ACTIVATIONS = ("softsign", "relu")   # REM2D_POLICY_SOFTSIGN, REM2D_POLIC
 EPISODE_ABI_VERSION = 1     # include/rem2d_episode.h
 WHEN = {"done": 1, "frozen": 2, "steps": 4}   # REM2D_WHEN_DONE, REM2D_WHEN_FROZEN, REM2D_WHEN_STEPS
 STREAM_ABI_VERSION = 1      # include/rem2d_stream.h
+EVOLVE_ABI_VERSION = 1      # include/rem2d_evolve.h
+EVOLVE_MAX_TOURNSIZE = 4    # REM2D_EVOLVE_MAX_TOURNSIZE
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -160,6 +162,15 @@ class Policy(C.Structure):
                 + [(k, C.c_int32) for k in ("n_sets", "reserved")]
                 + [(k, C.c_void_p) for k in ("w1", "b1", "w2", "b2", "index", "row_mask", "obs", "frac", "targets", "valid")]
                 + [("n_rows", C.c_int64)])
+
+
+class Evolve(C.Structure):
+    """rem2d_evolve (include/rem2d_evolve.h): device pointers the caller owns."""
+    _fields_ = ([(k, C.c_int32) for k in ("d", "hidden", "max_bodies", "n_sets", "group_size", "tournsize", "elite")]
+                + [("generation", C.c_uint32), ("rate_threshold", C.c_uint64), ("seed", C.c_uint64), ("sigma", C.c_float),
+                   ("reserved", C.c_int32)]
+                + [(k, C.c_void_p) for k in ("fitness", "w1", "b1", "w2", "b2", "child_w1", "child_b1", "child_w2", "child_b2",
+                                             "parent")])
 
 
 class EpisodeOut(C.Structure):
@@ -390,6 +401,12 @@ def lib(wide=False):
                                       C.c_int32, C.POINTER(StreamOut), C.c_int64, C.c_int64, C.c_void_p]
     if L.rem2d_stream_abi_version() != STREAM_ABI_VERSION:
         raise Rem2dError("%s: stream ABI version mismatch" % os.path.basename(path))
+    # evolving device policies (include/rem2d_evolve.h)
+    L.rem2d_evolve_abi_version.restype = C.c_int
+    for fn in (L.rem2d_policy_select, L.rem2d_policy_vary, L.rem2d_policy_evolve):
+        fn.argtypes = [C.POINTER(Evolve), C.c_void_p]
+    if L.rem2d_evolve_abi_version() != EVOLVE_ABI_VERSION:
+        raise Rem2dError("%s: evolve ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

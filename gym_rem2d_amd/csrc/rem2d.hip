@@ -45,6 +45,7 @@
 #include <rem2d_policy.h>  // (likewise)
 #include <rem2d_episode.h> // (likewise)
 #include <rem2d_stream.h>  // (likewise)
+#include <rem2d_evolve.h>  // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -104,6 +105,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_policy.h"
 #include "rem2d_episode.h"
 #include "rem2d_stream.h"
+#include "rem2d_evolve.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -1739,6 +1741,90 @@ extern "C" int rem2d_worlds_refill(rem2d_world *const *worlds, const rem2d_morph
         HIP_TRY(hipGetLastError());
     }
     return REM2D_OK;
+}
+
+// ---- evolving device policies (include/rem2d_evolve.h, csrc/rem2d_evolve.h) ----
+extern "C" int rem2d_evolve_abi_version(void) { return REM2D_EVOLVE_ABI_VERSION; }
+enum { EVOLVE_SELECT = 1, EVOLVE_VARY = 2 };
+// Checks an evolve descriptor for the calls in `stages`; `what` prefixes the message.  Nothing it points to is read.
+static int evolve_ok(const char *what, const rem2d_evolve *e, int stages) {
+    const std::string s = std::string(what) + ": ";
+    if (!e) return fail(REM2D_E_INVALID, s + "NULL descriptor");
+    if (e->max_bodies < 1 || e->max_bodies > REM2D_CONTROL_MAX_BODIES)
+        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(e->max_bodies));
+    if (e->hidden < 1 || e->hidden > REM2D_POLICY_MAX_HIDDEN)
+        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(e->hidden));
+    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * e->max_bodies;
+    if (e->d < d0 || e->d > d0 + REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
+                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(e->d));
+    if (e->n_sets < 1) return fail(REM2D_E_INVALID, s + "n_sets must be at least 1");
+    if (e->group_size < 1 || e->n_sets % e->group_size != 0)
+        return fail(REM2D_E_INVALID, s + "group_size must be a divisor of n_sets (" + std::to_string(e->n_sets) + "), not " + std::to_string(e->group_size));
+    if (e->tournsize < 1 || e->tournsize > REM2D_EVOLVE_MAX_TOURNSIZE)
+        return fail(REM2D_E_INVALID, s + "tournsize must be 1.." + std::to_string(REM2D_EVOLVE_MAX_TOURNSIZE) + ", not " + std::to_string(e->tournsize));
+    if (e->elite != 0 && e->elite != 1) return fail(REM2D_E_INVALID, s + "elite must be 0 or 1, not " + std::to_string(e->elite));
+    if (e->rate_threshold > (1ull << 32)) return fail(REM2D_E_INVALID, s + "rate_threshold must be at most 2^32");
+    if (!e->parent) return fail(REM2D_E_INVALID, s + "NULL device pointer (parent)");
+    if ((stages & EVOLVE_SELECT) && !e->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
+    if (stages & EVOLVE_VARY) {
+        const float *src[4] = {e->w1, e->b1, e->w2, e->b2};
+        const float *dst[4] = {e->child_w1, e->child_b1, e->child_w2, e->child_b2};
+        const char *const name[4] = {"w1", "b1", "w2", "b2"};
+        const size_t len[4] = {(size_t)e->d * (size_t)e->hidden, (size_t)e->hidden, (size_t)e->hidden * (size_t)e->max_bodies, (size_t)e->max_bodies};
+        for (int k = 0; k < 4; ++k)
+            if (!src[k] || !dst[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        for (int k = 0; k < 4; ++k)
+            for (int j = 0; j < 4; ++j) {
+                const uintptr_t a = (uintptr_t)dst[k], an = a + (uintptr_t)e->n_sets * len[k] * sizeof(float);
+                const uintptr_t b = (uintptr_t)src[j], bn = b + (uintptr_t)e->n_sets * len[j] * sizeof(float);
+                if (a < bn && b < an) return fail(REM2D_E_INVALID, s + "child_" + name[k] + " overlaps the parents' " + name[j]);
+            }
+    }
+    return REM2D_OK;
+}
+static void evolve_args(EvolveArgs &A, const rem2d_evolve *e) {
+    memset(&A, 0, sizeof(A));
+    A.fitness = e->fitness;
+    A.src[0] = e->w1; A.src[1] = e->b1; A.src[2] = e->w2; A.src[3] = e->b2;
+    A.dst[0] = e->child_w1; A.dst[1] = e->child_b1; A.dst[2] = e->child_w2; A.dst[3] = e->child_b2;
+    A.parent = e->parent;
+    A.rateThreshold = e->rate_threshold;
+    A.key0 = (unsigned)(e->seed & 0xffffffffull); A.key1 = (unsigned)(e->seed >> 32); A.generation = e->generation;
+    A.len[0] = e->d * e->hidden; A.len[1] = e->hidden; A.len[2] = e->hidden * e->max_bodies; A.len[3] = e->max_bodies;
+    // 16-byte accesses where a set of the array is whole float4s and both bases are aligned (every set's base then is too)
+    for (int k = 0; k < 4; ++k) A.vec[k] = A.len[k] % 4 == 0 && (uintptr_t)A.src[k] % 16 == 0 && (uintptr_t)A.dst[k] % 16 == 0;
+    A.G = e->n_sets; A.S = e->group_size; A.T = e->tournsize; A.elite = e->elite;
+    A.sigma = e->sigma;
+}
+// The stages of a checked descriptor on `st`.
+static int evolve_launch(const rem2d_evolve *e, int stages, hipStream_t st) {
+    EvolveArgs A;
+    evolve_args(A, e);
+    if (stages & EVOLVE_SELECT) {
+        hipLaunchKernelGGL(rem2d_evolve_select_kernel, dim3(((unsigned)e->n_sets + WAVE - 1) / WAVE), dim3(WAVE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    if (stages & EVOLVE_VARY) {
+        hipLaunchKernelGGL(rem2d_evolve_vary_kernel, dim3((unsigned)e->n_sets), dim3(WAVE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+extern "C" int rem2d_policy_select(const rem2d_evolve *e, void *stream) {
+    const int rc = evolve_ok("select", e, EVOLVE_SELECT);
+    if (rc != REM2D_OK) return rc;
+    return evolve_launch(e, EVOLVE_SELECT, (hipStream_t)stream);
+}
+extern "C" int rem2d_policy_vary(const rem2d_evolve *e, void *stream) {
+    const int rc = evolve_ok("vary", e, EVOLVE_VARY);
+    if (rc != REM2D_OK) return rc;
+    return evolve_launch(e, EVOLVE_VARY, (hipStream_t)stream);
+}
+extern "C" int rem2d_policy_evolve(const rem2d_evolve *e, void *stream) {
+    const int rc = evolve_ok("evolve", e, EVOLVE_SELECT | EVOLVE_VARY);
+    if (rc != REM2D_OK) return rc;
+    return evolve_launch(e, EVOLVE_SELECT | EVOLVE_VARY, (hipStream_t)stream);
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

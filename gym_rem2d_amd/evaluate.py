@@ -274,6 +274,41 @@ def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_e
     return env.fitness.clone()
 
 
+def run_policy_generations(env, policy, n_generations, seed=0, rate=0.05, sigma=0.1, tournsize=4, group_size=None, elite=0,
+                           max_steps=EPISODE_CAP, chunk=100, on_error="raise", log=None, on_generation=None):
+    """population.run_generations for device policies: the generational loop of run2D.run_deap (REM2D_main.py:280-298) with the
+    population -- the weight sets of ``policy``, one per creature of ``env`` (reset first) -- on the device throughout.  Generation
+    0's episode runs first; every generation is then ``policy.evolve`` (generation g = 1 .., this ``seed``), ``env.set_policy``,
+    ``env.reset_where`` of everyone and ``run_policy_episode(compact=False)`` -- compaction would drop the device morphology the
+    reset needs.  The generations from 1 on use two sets of weight buffers in turn; ``policy`` itself is never written.  Returns ``(policy, fitness, history)``: the last generation, its
+    fitness (float64 [N] on the device) and rows ``(gen, min, max, mean)``, the only numbers that leave the device.
+    ``on_generation(gen, policy, fitness)``, if given, is called after every episode, generation 0's included, with the tensors
+    themselves (a checkpoint hook: clone what must last, the weight buffers are overwritten two generations later).  The creatures
+    do not change: group_size names the blocks of consecutive creatures whose policies compete (those of one morphology)."""
+    n = env.n_envs
+    everyone = torch.ones(n, dtype=torch.uint8, device=env.worlds[0][0].device) if env.worlds else None
+    env.set_policy(policy)
+    policy = env.policy
+    fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
+    if on_generation:
+        on_generation(0, policy, fit)
+    spare, history = None, []
+    for gen in range(1, int(n_generations) + 1):
+        child = policy.evolve(fit, gen, seed=seed, rate=rate, sigma=sigma, tournsize=tournsize, group_size=group_size, elite=elite,
+                              out=spare)
+        spare, policy = (policy if gen > 1 else None), child    # (generation 0's buffers are the caller's: never written)
+        env.set_policy(policy)
+        env.reset_where(mask=everyone)
+        fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
+        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
+        history.append((gen,) + tuple(stats))
+        if on_generation:
+            on_generation(gen, policy, fit)
+        if log:
+            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+    return policy, fit, history
+
+
 def run_stream(env, batches, n_total, slots, max_steps=EPISODE_CAP, chunk=100, on_error="fallback"):
     """run_episode for a population that does not get an arena per creature: ``batches`` ([(Morphology, ids)] per lane bucket, as
     reset_batches takes them) are streamed through ``slots`` slots of ``env`` (BatchedModular2D.reset_stream) -- ``step(chunk)``,

@@ -92,6 +92,7 @@ class MLPPolicy:
         self.scale = DEFAULT_SCALE if scale is None else float(np.float32(scale))
         self.index, self.rays = index, rays
         self.n_sets, self.d, self.hidden, self.max_bodies, self.n_rays = G, D, H, MB, R
+        self.parents = None     # int32 [G] on a policy that evolve() made: the set each of its sets came from
 
     # ---- construction ----
     @classmethod
@@ -180,3 +181,80 @@ class MLPPolicy:
             _lib.check(_lib.lib(wide).rem2d_policy_forward(C.byref(p), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
                        wide)
         return out
+
+    # ---- the next generation (include/rem2d_evolve.h) ----
+    def evolve(self, fitness, generation, seed=0, rate=0.05, sigma=0.1, tournsize=4, group_size=None, elite=0, parents=None, out=None,
+               wide=False):
+        """The child policy of one generation, made on the device by one library call (rem2d_policy_evolve: tournament selection,
+        then per-element mutation; include/rem2d_evolve.h states both) on the current stream; nothing synchronises and the library
+        allocates nothing.  ``fitness``: float64 ``[G]`` on the policy's device, one per weight set (NaN loses to everything).
+        ``generation``, ``seed``: the random stream -- the same (seed, generation) gives the same children, bit for bit, in every
+        build.  ``rate``: the probability that an element is mutated (``floor(rate * 2**32)`` is what the library compares with);
+        ``sigma``: the step, the noise has unit variance.  ``tournsize`` 1..4; ``group_size``: sets compete within blocks of that many
+        consecutive sets (default: all of them; it must divide G); ``elite=1``: the first child of every block is the block's best
+        set, unmutated.  ``parents``: int32 ``[G]`` on the device, the parent of every child -- selection is skipped
+        (rem2d_policy_vary) and a value outside ``[0, G)`` leaves that child's words as they are.  ``out``: a policy of the same
+        shapes whose buffers -- the weights and, where it has one, ``.parents`` -- are overwritten and which is returned (the
+        grandparent, for double buffering); without it new tensors.
+
+        Returns the child ``MLPPolicy`` -- same activation, scale and rays -- with ``.parents``, int32 ``[G]``."""
+        dev, G = self.device, self.n_sets
+        if self.index is not None:
+            raise ValueError("evolve: a policy with an index shares weight sets among creatures; evolve the sets of take() instead")
+        if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
+            raise ValueError("evolve: fitness must be a torch.float64 tensor")
+        if tuple(fitness.shape) != (G,) or not fitness.is_contiguous():
+            raise ValueError("evolve: fitness must be a contiguous tensor of one entry per weight set [%d], not %s" % (G, list(fitness.shape)))
+        if fitness.device != dev:
+            raise ValueError("evolve: fitness must be on %s, not %s" % (dev, fitness.device))
+        S = G if group_size is None else int(group_size)
+        if S < 1 or G % S:
+            raise ValueError("evolve: group_size must divide the %d weight sets, not %d" % (G, S))
+        if not 1 <= int(tournsize) <= _lib.EVOLVE_MAX_TOURNSIZE:
+            raise ValueError("evolve: tournsize must be 1..%d, not %r" % (_lib.EVOLVE_MAX_TOURNSIZE, tournsize))
+        if elite not in (0, 1):
+            raise ValueError("evolve: elite must be 0 or 1, not %r" % (elite,))
+        if not 0.0 <= float(rate) <= 1.0:
+            raise ValueError("evolve: rate must be in [0, 1], not %r" % (rate,))
+        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("evolve: generation must fit 32 bits and seed 64 (unsigned)")
+        if parents is not None:
+            if (not isinstance(parents, torch.Tensor) or parents.dtype != torch.int32 or tuple(parents.shape) != (G,)
+                    or not parents.is_contiguous() or parents.device != dev):
+                raise ValueError("evolve: parents must be a contiguous torch.int32 [%d] tensor on %s" % (G, dev))
+        mine = (self.w1, self.b1, self.w2, self.b2)
+        if out is not None:
+            if out is self or not isinstance(out, MLPPolicy):
+                raise ValueError("evolve: out must be another MLPPolicy than the one that is evolved")
+            theirs = (out.w1, out.b1, out.w2, out.b2)
+            if out.index is not None or any(a.shape != b.shape or a.device != b.device for a, b in zip(mine, theirs)):
+                raise ValueError("evolve: out must have this policy's shapes and device, and no index")
+            for a in theirs:            # (the library checks it too; here the message can name the argument)
+                for b in mine:
+                    if a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
+                        raise ValueError("evolve: out shares memory with the policy that is evolved")
+        if dev.type != "cuda":
+            raise ValueError("evolve: the weights are on %s; move the policy to the GPU with .to(device)" % dev)
+        if out is None:             # (with parents= a skipped child keeps what its buffer held: zeros)
+            kids = tuple(torch.empty_like(t) for t in mine) if parents is None else tuple(torch.zeros_like(t) for t in mine)
+            child = self._like(*kids, None)
+        else:
+            child = out
+            child.activation, child.scale, child.rays = self.activation, self.scale, self.rays
+        if parents is not None:
+            child.parents = parents
+        elif child.parents is None or child.parents is self.parents:
+            child.parents = torch.empty(G, dtype=torch.int32, device=dev)
+        e = _lib.Evolve()
+        e.d, e.hidden, e.max_bodies, e.n_sets, e.group_size = self.d, self.hidden, self.max_bodies, G, S
+        e.tournsize, e.elite, e.generation = int(tournsize), int(elite), int(generation)
+        e.rate_threshold, e.seed, e.sigma, e.reserved = int(math.floor(float(rate) * 4294967296.0)), int(seed), float(sigma), 0
+        e.fitness = fitness.data_ptr()
+        e.w1, e.b1, e.w2, e.b2 = (t.data_ptr() for t in mine)
+        e.child_w1, e.child_b1, e.child_w2, e.child_b2 = (t.data_ptr() for t in (child.w1, child.b1, child.w2, child.b2))
+        e.parent = child.parents.data_ptr()
+        L = _lib.lib(wide)
+        call = L.rem2d_policy_evolve if parents is None else L.rem2d_policy_vary
+        with torch.cuda.device(dev):
+            _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
+        return child
