@@ -98,6 +98,7 @@ EPISODE_ABI_VERSION = 1     # include/rem2d_episode.h
 WHEN = {"done": 1, "frozen": 2, "steps": 4}   # REM2D_WHEN_DONE, REM2D_WHEN_FROZEN, REM2D_WHEN_STEPS
 STREAM_ABI_VERSION = 1      # include/rem2d_stream.h
 EVOLVE_ABI_VERSION = 1      # include/rem2d_evolve.h
+ORDER_ABI_VERSION = 1       # include/rem2d_order.h
 EVOLVE_MAX_TOURNSIZE = 4    # REM2D_EVOLVE_MAX_TOURNSIZE
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
@@ -407,6 +408,12 @@ def lib(wide=False):
         fn.argtypes = [C.POINTER(Evolve), C.c_void_p]
     if L.rem2d_evolve_abi_version() != EVOLVE_ABI_VERSION:
         raise Rem2dError("%s: evolve ABI version mismatch" % os.path.basename(path))
+    # the creature order, read back and made on demand (include/rem2d_order.h)
+    L.rem2d_order_abi_version.restype = C.c_int
+    L.rem2d_world_read_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rem2d_world_make_order.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    if L.rem2d_order_abi_version() != ORDER_ABI_VERSION:
+        raise Rem2dError("%s: order ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

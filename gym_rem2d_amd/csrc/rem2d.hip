@@ -46,6 +46,7 @@
 #include <rem2d_episode.h> // (likewise)
 #include <rem2d_stream.h>  // (likewise)
 #include <rem2d_evolve.h>  // (likewise)
+#include <rem2d_order.h>   // (the public header; it has no kernels of its own)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -471,8 +472,9 @@ extern "C" int rem2d_world_set_order(rem2d_world *w, const int32_t *order_dev, v
         w->hostOrder = true;
     } else {
         // back to the arena order.  With REM2D_OPT_REBALANCE on the kernels keep going through State::order (the library
-        // re-makes it every N steps), so the identity is written there instead of dropping the indirection
-        if (w->hostOrder && w->opt[REM2D_OPT_REBALANCE] > 0) {
+        // re-makes it every N steps), so the identity is written there instead of dropping the indirection -- and with it off as
+        // well: rem2d_world_read_order shows the array, and switching REM2D_OPT_REBALANCE on later starts from what it holds
+        if (w->hostOrder) {
             std::vector<int> ident((size_t)w->L.Np);
             for (int i = 0; i < w->L.Np; ++i) ident[(size_t)i] = i;
             HIP_TRY(hipDeviceSynchronize()); // (rare call: no kernel of any step group may still read the old order)
@@ -1257,9 +1259,11 @@ extern "C" int rem2d_groups_step_ex(const rem2d_step_group *groups, int32_t n_gr
             key = mix64(key, (uint64_t)(uintptr_t)w);
             key = mix64(key, w->epoch);
             // REM2D_OPT_REBALANCE: which steps of the call carry a re-ordering launch depends on where the call starts in the
-            // cadence -- part of the key, so that a replay re-orders every N env-steps exactly like the plain enqueue does
+            // cadence -- part of the key, so that a replay re-orders every N env-steps exactly like the plain enqueue does.  A world's
+            // very first step is a phase of its own (`every`): nothing is re-ordered in front of it, so a call captured there holds
+            // one launch less than the same call N steps later, which must not replay it
             const int every = w->opt[REM2D_OPT_REBALANCE];
-            if (every > 0) key = mix64(key, 0xabcd0000ull + (uint64_t)(w->stepsQueued % every));
+            if (every > 0) key = mix64(key, 0xabcd0000ull + (uint64_t)(w->stepsQueued == 0 ? every : w->stepsQueued % every));
         }
         key = mix64(key, 0xfeedull + (uint64_t)groups[g].n_worlds);
     }
@@ -1304,6 +1308,25 @@ extern "C" int rem2d_groups_step_ex(const rem2d_step_group *groups, int32_t n_gr
 }
 extern "C" int rem2d_groups_step(const rem2d_step_group *groups, int32_t n_groups, int32_t n_steps, void *stream, uint32_t flags) {
     return rem2d_groups_step_ex(groups, n_groups, n_steps, (float)(1.0 / 50), 6 * 30, 2 * 30, stream, flags);
+}
+
+// ---- the creature order, read back and made on demand (include/rem2d_order.h): host code around what is there ----
+extern "C" int rem2d_order_abi_version(void) { return REM2D_ORDER_ABI_VERSION; }
+extern "C" int rem2d_world_read_order(const rem2d_world *w, int32_t *out_dev, void *stream) {
+    if (!w) return fail(REM2D_E_INVALID, "read_order: world is NULL");
+    if (!out_dev) return fail(REM2D_E_INVALID, "read_order: NULL output array");
+    HIP_TRY(hipSetDevice(w->cfg.device));
+    HIP_TRY(hipMemcpyAsync(out_dev, w->S.order, (size_t)2 * w->L.Np * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return REM2D_OK;
+}
+extern "C" int rem2d_world_make_order(rem2d_world *w, int32_t pos_iters, void *stream) {
+    if (!w) return fail(REM2D_E_INVALID, "make_order: world is NULL");
+    if (w->cfg.flags & REM2D_FLAG_RETILE) return fail(REM2D_E_INVALID, "make_order: the world deals its creatures itself (REM2D_FLAG_RETILE)");
+    if (pos_iters < 1) return fail(REM2D_E_INVALID, "make_order: pos_iters must be >= 1");
+    HIP_TRY(hipSetDevice(w->cfg.device));
+    launch_rebalance(w, (hipStream_t)stream, pos_iters); // (the step paths' own launch: stepsQueued, stepsAtOrder, flags and options stay)
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
 }
 
 extern "C" int rem2d_tree_diversity(const double *pos_dev, const int32_t *count_dev, int32_t n_trees, int32_t max_nodes,

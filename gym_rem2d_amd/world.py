@@ -68,6 +68,21 @@ class BatchedWorld:
         self._order = full   # (kept alive until the asynchronous copy has run)
         self._check(self.L.rem2d_world_set_order(self.h, full.data_ptr(), self._stream()))
 
+    def order(self):
+        """The world's creature order as the library holds it now (rem2d_world_read_order): int32 ``[2, n_envs_padded]`` on the
+        device, a copy made on the current stream.  Row 0 is what the kernels read while an order is in use, row 1 its copy;
+        columns n_envs .. n_envs_padded - 1 are the padding slots, which hold themselves."""
+        out = torch.empty((2, self.n_envs_padded), dtype=torch.int32, device=self.device)
+        self._check(self.L.rem2d_world_read_order(self.h, out.data_ptr(), self._stream()))
+        return out
+
+    def make_order(self, pos_iters=60):
+        """Make the order from the state in place, now (rem2d_world_make_order): one launch of the kernel the `rebalance` launch
+        option runs every N env-steps -- creatures whose last step used all `pos_iters` position iterations first, then those that
+        used three or more, then the rest, each class in arena order.  Nothing else changes: not the option's cadence, and not
+        whether the kernels go through the order."""
+        self._check(self.L.rem2d_world_make_order(self.h, int(pos_iters), self._stream()))
+
     def set_option(self, name, value):
         """A launch option of this world (``_lib.OPTIONS``: pipeline, fuse_velpost, prio, prio_t1, prio_t2, heavy_per_wave,
         debug); in a step group the first world's options steer the group's launches."""

@@ -18,6 +18,7 @@ HOST_ONLY = {
     "rem2d_mutate_trees",
     "rem2d_tree_diversity",  # its CPU restatement is oracle.tree_distance_matrix (tests/test_diversity.py)
     "rem2d_selftest_scalar",  # its CPU restatement is rem2d_oracle_kat_scalar / rem2d_oracle_sincosf
+    "rem2d_world_read_order", "rem2d_world_make_order",  # include/rem2d_order.h: the twin has no launch shapes; tests/order_model.py states the order
 }
 
 
