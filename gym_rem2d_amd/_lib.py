@@ -100,6 +100,7 @@ STREAM_ABI_VERSION = 1      # include/rem2d_stream.h
 EVOLVE_ABI_VERSION = 1      # include/rem2d_evolve.h
 ORDER_ABI_VERSION = 1       # include/rem2d_order.h
 EVOLVE_MAX_TOURNSIZE = 4    # REM2D_EVOLVE_MAX_TOURNSIZE
+ES_ABI_VERSION = 1          # include/rem2d_es.h
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -172,6 +173,15 @@ class Evolve(C.Structure):
                    ("reserved", C.c_int32)]
                 + [(k, C.c_void_p) for k in ("fitness", "w1", "b1", "w2", "b2", "child_w1", "child_b1", "child_w2", "child_b2",
                                              "parent")])
+
+
+class Es(C.Structure):
+    """rem2d_es (include/rem2d_es.h): device pointers the caller owns."""
+    _fields_ = ([(k, C.c_int32) for k in ("d", "hidden", "max_bodies", "n_means", "group_size", "pair_chunk")]
+                + [("generation", C.c_uint32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("sigma", C.c_float), ("step", C.c_float)]
+                + [(k, C.c_void_p) for k in ("fitness", "util", "w1", "b1", "w2", "b2", "child_w1", "child_b1", "child_w2", "child_b2",
+                                             "new_w1", "new_b1", "new_w2", "new_b2", "scratch")]
+                + [("scratch_bytes", C.c_uint64)])
 
 
 class EpisodeOut(C.Structure):
@@ -414,6 +424,14 @@ def lib(wide=False):
     L.rem2d_world_make_order.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     if L.rem2d_order_abi_version() != ORDER_ABI_VERSION:
         raise Rem2dError("%s: order ABI version mismatch" % os.path.basename(path))
+    # an evolution strategy for device policies (include/rem2d_es.h)
+    L.rem2d_es_abi_version.restype = C.c_int
+    L.rem2d_es_scratch_bytes.restype = C.c_int64
+    L.rem2d_es_scratch_bytes.argtypes = [C.POINTER(Es)]
+    for fn in (L.rem2d_es_sample, L.rem2d_es_shape, L.rem2d_es_update, L.rem2d_es_step):
+        fn.argtypes = [C.POINTER(Es), C.c_void_p]
+    if L.rem2d_es_abi_version() != ES_ABI_VERSION:
+        raise Rem2dError("%s: es ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

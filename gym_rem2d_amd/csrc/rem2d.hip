@@ -47,6 +47,7 @@
 #include <rem2d_stream.h>  // (likewise)
 #include <rem2d_evolve.h>  // (likewise)
 #include <rem2d_order.h>   // (the public header; it has no kernels of its own)
+#include <rem2d_es.h>      // (as rem2d_evolve.h: the quoted name below is the kernels' file)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -107,6 +108,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_episode.h"
 #include "rem2d_stream.h"
 #include "rem2d_evolve.h"
+#include "rem2d_es.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -1848,6 +1850,170 @@ extern "C" int rem2d_policy_evolve(const rem2d_evolve *e, void *stream) {
     const int rc = evolve_ok("evolve", e, EVOLVE_SELECT | EVOLVE_VARY);
     if (rc != REM2D_OK) return rc;
     return evolve_launch(e, EVOLVE_SELECT | EVOLVE_VARY, (hipStream_t)stream);
+}
+
+// ---- an evolution strategy for device policies (include/rem2d_es.h, csrc/rem2d_es.h) ----
+extern "C" int rem2d_es_abi_version(void) { return REM2D_ES_ABI_VERSION; }
+enum { ES_SAMPLE = 1, ES_SHAPE = 2, ES_UPDATE = 4 };
+enum { ES_MAX_GRID = 1 << 24 }; // workgroups of one launch; what lies beyond goes into further launches
+// The split of a block's pairs for a descriptor whose shapes are good: pairs per wavefront and chunks per block.
+static void es_split(const rem2d_es *e, int &pairChunk, int &nChunks) {
+    const long long P = e->group_size / 2;
+    long long chunk = e->pair_chunk;
+    if (chunk == 0) {
+        // the library's choice: no split while the blocks alone fill the machine or a block is short; otherwise chunks of at
+        // least 64 pairs, as many as bring the launch to about 4096 wavefronts
+        const long long lens[4] = {(long long)e->d * e->hidden, e->hidden, (long long)e->hidden * e->max_bodies, e->max_bodies};
+        long long W = 0;
+        for (int k = 0; k < 4; ++k) W += (lens[k] + WAVE - 1) / WAVE;
+        const long long waves = W * (long long)e->n_means;
+        chunk = P;
+        if (waves < 1024 && P > 64) {
+            const long long want = (4096 + waves - 1) / waves;
+            chunk = (P + want - 1) / want;
+            if (chunk < 64) chunk = 64;
+        }
+    }
+    if (chunk > P) chunk = P;
+    pairChunk = (int)chunk;
+    nChunks = (int)((P + chunk - 1) / chunk);
+}
+// Checks the shapes and parameters of an es descriptor; `what` prefixes the message.  No pointer is looked at.
+static int es_shapes_ok(const std::string &s, const rem2d_es *e) {
+    if (!e) return fail(REM2D_E_INVALID, s + "NULL descriptor");
+    if (e->max_bodies < 1 || e->max_bodies > REM2D_CONTROL_MAX_BODIES)
+        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(e->max_bodies));
+    if (e->hidden < 1 || e->hidden > REM2D_POLICY_MAX_HIDDEN)
+        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(e->hidden));
+    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * e->max_bodies;
+    if (e->d < d0 || e->d > d0 + REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
+                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(e->d));
+    if (e->n_means < 1) return fail(REM2D_E_INVALID, s + "n_means must be at least 1");
+    if (e->group_size < 2 || e->group_size % 2 != 0)
+        return fail(REM2D_E_INVALID, s + "group_size must be even and at least 2, not " + std::to_string(e->group_size));
+    if ((long long)e->n_means * (long long)e->group_size > 2147483647ll)
+        return fail(REM2D_E_INVALID, s + "n_means * group_size must be at most 2^31 - 1");
+    if (e->pair_chunk < 0) return fail(REM2D_E_INVALID, s + "pair_chunk must be at least 0, not " + std::to_string(e->pair_chunk));
+    if (e->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0");
+    return REM2D_OK;
+}
+static size_t es_scratch_need(const rem2d_es *e) {
+    int pairChunk, nChunks;
+    es_split(e, pairChunk, nChunks);
+    if (nChunks == 1) return 0;
+    const size_t E = (size_t)e->d * e->hidden + (size_t)e->hidden + (size_t)e->hidden * e->max_bodies + (size_t)e->max_bodies;
+    return (size_t)e->n_means * (size_t)nChunks * E * sizeof(long long);
+}
+// Checks an es descriptor for the calls in `stages`.  Nothing it points to is read.
+static int es_ok(const char *what, const rem2d_es *e, int stages) {
+    const std::string s = std::string(what) + ": ";
+    const int rc = es_shapes_ok(s, e);
+    if (rc != REM2D_OK) return rc;
+    if ((stages & ES_SHAPE) && !e->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
+    if ((stages & (ES_SHAPE | ES_UPDATE)) && !e->util) return fail(REM2D_E_INVALID, s + "NULL device pointer (util)");
+    const float *mean[4] = {e->w1, e->b1, e->w2, e->b2};
+    const char *const name[4] = {"w1", "b1", "w2", "b2"};
+    const size_t len[4] = {(size_t)e->d * (size_t)e->hidden, (size_t)e->hidden, (size_t)e->hidden * (size_t)e->max_bodies, (size_t)e->max_bodies};
+    for (int pass = 0; pass < 2; ++pass) {
+        if (!(stages & (pass == 0 ? ES_SAMPLE : ES_UPDATE))) continue;
+        const float *dst[4] = {pass == 0 ? e->child_w1 : e->new_w1, pass == 0 ? e->child_b1 : e->new_b1,
+                               pass == 0 ? e->child_w2 : e->new_w2, pass == 0 ? e->child_b2 : e->new_b2};
+        const size_t sets = pass == 0 ? (size_t)e->n_means * (size_t)e->group_size : (size_t)e->n_means;
+        for (int k = 0; k < 4; ++k)
+            if (!mean[k] || !dst[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        for (int k = 0; k < 4; ++k)
+            for (int j = 0; j < 4; ++j) {
+                const uintptr_t a = (uintptr_t)dst[k], an = a + (uintptr_t)(sets * len[k] * sizeof(float));
+                const uintptr_t b = (uintptr_t)mean[j], bn = b + (uintptr_t)((size_t)e->n_means * len[j] * sizeof(float));
+                if (a < bn && b < an) return fail(REM2D_E_INVALID, s + (pass == 0 ? "child_" : "new_") + name[k] + " overlaps the mean's " + name[j]);
+            }
+    }
+    if (stages & ES_UPDATE) {
+        const size_t need = es_scratch_need(e);
+        if (need != 0) {
+            if (!e->scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
+            if ((uintptr_t)e->scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
+            if (e->scratch_bytes < (uint64_t)need)
+                return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(e->scratch_bytes) + " bytes, " + std::to_string(need) + " are needed");
+        }
+    }
+    return REM2D_OK;
+}
+static void es_args(EsArgs &A, const rem2d_es *e) {
+    memset(&A, 0, sizeof(A));
+    A.fitness = e->fitness;
+    A.util = e->util;
+    A.mean[0] = e->w1; A.mean[1] = e->b1; A.mean[2] = e->w2; A.mean[3] = e->b2;
+    A.child[0] = e->child_w1; A.child[1] = e->child_b1; A.child[2] = e->child_w2; A.child[3] = e->child_b2;
+    A.next[0] = e->new_w1; A.next[1] = e->new_b1; A.next[2] = e->new_w2; A.next[3] = e->new_b2;
+    A.scratch = (long long *)e->scratch;
+    A.key0 = (unsigned)(e->seed & 0xffffffffull); A.key1 = (unsigned)(e->seed >> 32); A.generation = e->generation;
+    A.len[0] = e->d * e->hidden; A.len[1] = e->hidden; A.len[2] = e->hidden * e->max_bodies; A.len[3] = e->max_bodies;
+    for (int k = 0; k < 4; ++k) {
+        // 16-byte accesses where a set of the array is whole float4s and both bases are aligned (every set's base then is too)
+        A.vec[k] = A.len[k] % 4 == 0 && (uintptr_t)A.mean[k] % 16 == 0 && (uintptr_t)A.child[k] % 16 == 0;
+        A.slots[k] = (A.len[k] + WAVE - 1) / WAVE;
+        A.off[k] = A.E;
+        A.W += A.slots[k];
+        A.E += A.len[k];
+    }
+    A.M = e->n_means; A.S = e->group_size;
+    es_split(e, A.pairChunk, A.nChunks);
+    A.sigma = e->sigma; A.step = e->step;
+}
+// `items` workgroups of `threads` threads of one kernel, ES_MAX_GRID of them per launch, each launch told its first item.
+template <typename K> static int es_launch_items(K kernel, long long items, int threads, EsArgs &A, hipStream_t st) {
+    for (long long base = 0; base < items; base += ES_MAX_GRID) {
+        const long long n = items - base < (long long)ES_MAX_GRID ? items - base : (long long)ES_MAX_GRID;
+        A.itemBase = base;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3((unsigned)threads), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+// The stages of a checked descriptor on `st`.
+static int es_launch(const rem2d_es *e, int stages, hipStream_t st) {
+    EsArgs A;
+    es_args(A, e);
+    const long long G = (long long)A.M * (long long)A.S;
+    int rc = REM2D_OK;
+    if (stages & ES_SAMPLE) rc = es_launch_items(rem2d_es_sample_kernel, G / 2, WAVE, A, st);
+    if (rc == REM2D_OK && (stages & ES_SHAPE)) {
+        A.itemBase = 0; // (ceil(G / ES_TILE) < 2^23 workgroups: one launch)
+        hipLaunchKernelGGL(rem2d_es_shape_kernel, dim3((unsigned)((G + ES_TILE - 1) / ES_TILE)), dim3(ES_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    if (rc == REM2D_OK && (stages & ES_UPDATE)) {
+        rc = es_launch_items(rem2d_es_update_kernel, (long long)A.M * (long long)A.nChunks * (long long)A.W, WAVE, A, st);
+        if (rc == REM2D_OK && A.nChunks > 1) rc = es_launch_items(rem2d_es_finish_kernel, (long long)A.M * (long long)A.W, WAVE, A, st);
+    }
+    return rc;
+}
+extern "C" int64_t rem2d_es_scratch_bytes(const rem2d_es *e) {
+    const int rc = es_shapes_ok("es_scratch_bytes: ", e);
+    if (rc != REM2D_OK) return rc;
+    return (int64_t)es_scratch_need(e);
+}
+extern "C" int rem2d_es_sample(const rem2d_es *e, void *stream) {
+    const int rc = es_ok("es_sample", e, ES_SAMPLE);
+    if (rc != REM2D_OK) return rc;
+    return es_launch(e, ES_SAMPLE, (hipStream_t)stream);
+}
+extern "C" int rem2d_es_shape(const rem2d_es *e, void *stream) {
+    const int rc = es_ok("es_shape", e, ES_SHAPE);
+    if (rc != REM2D_OK) return rc;
+    return es_launch(e, ES_SHAPE, (hipStream_t)stream);
+}
+extern "C" int rem2d_es_update(const rem2d_es *e, void *stream) {
+    const int rc = es_ok("es_update", e, ES_UPDATE);
+    if (rc != REM2D_OK) return rc;
+    return es_launch(e, ES_UPDATE, (hipStream_t)stream);
+}
+extern "C" int rem2d_es_step(const rem2d_es *e, void *stream) {
+    const int rc = es_ok("es_step", e, ES_SHAPE | ES_UPDATE);
+    if (rc != REM2D_OK) return rc;
+    return es_launch(e, ES_SHAPE | ES_UPDATE, (hipStream_t)stream);
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

@@ -309,6 +309,48 @@ def run_policy_generations(env, policy, n_generations, seed=0, rate=0.05, sigma=
     return policy, fit, history
 
 
+def run_policy_es(env, mean, n_generations, seed=0, sigma=0.1, lr=0.05, group_size=None, max_steps=EPISODE_CAP, chunk=100,
+                  on_error="raise", log=None, on_generation=None):
+    """An evolution strategy for device policies: ``mean`` holds one controller per block of ``group_size`` = S consecutive
+    creatures of ``env`` (reset first; the creatures of a block share a morphology, or are whatever the caller wants ranked
+    together; default: one block of everyone), M = n_envs / S sets in all.  Every generation g = 1 .. is ``mean.es_sample`` (the
+    S children of every mean, antithetic pairs, this ``seed``), ``env.set_policy``, ``env.reset_where`` of everyone,
+    ``run_policy_episode(compact=False)`` -- compaction would drop the device morphology the reset needs -- and ``es_update``:
+    centred ranks of the fitness within each block, the mean moved by ``lr / (S sigma)`` times the rank-weighted noise
+    (include/rem2d_es.h).  One child policy, two sets of mean buffers, one util and one scratch tensor are reused throughout;
+    ``mean`` itself is never written.  Returns ``(mean, fitness, history)``: the mean after the last update, the last generation's
+    fitness (float64 [N] on the device) and rows ``(gen, min, max, mean)``, the only numbers that leave the device.
+    ``on_generation(gen, children, fitness, mean)``, if given, is called after every update with the tensors themselves and the
+    NEW mean (a checkpoint hook: clone what must last, every buffer is overwritten one or two generations later)."""
+    if not env.worlds:
+        raise ValueError("run_policy_es: no population in place (reset first)")
+    n = env.n_envs
+    S = n if group_size is None else int(group_size)
+    if S < 2 or S % 2 or n % S or mean.n_sets * S != n:
+        raise ValueError("run_policy_es: %d creatures are not %d means times an even group_size (%r)" % (n, mean.n_sets, group_size))
+    dev = env.worlds[0][0].device
+    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
+    mean = mean.to(dev)
+    children, spare, scratch, fit, history = None, None, None, None, []
+    need = mean.es_scratch_bytes(S)
+    if need:
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    for gen in range(1, int(n_generations) + 1):
+        children = mean.es_sample(gen, seed=seed, sigma=sigma, group_size=S, out=children)
+        env.set_policy(children)
+        env.reset_where(mask=everyone)
+        fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
+        new = mean.es_update(fit, gen, seed=seed, sigma=sigma, lr=lr, group_size=S, out=spare, scratch=scratch)
+        spare, mean = (mean if gen > 1 else None), new      # (the first mean's buffers are the caller's: never written)
+        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
+        history.append((gen,) + tuple(stats))
+        if on_generation:
+            on_generation(gen, children, fit, mean)
+        if log:
+            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+    return mean, fit, history
+
+
 def run_stream(env, batches, n_total, slots, max_steps=EPISODE_CAP, chunk=100, on_error="fallback"):
     """run_episode for a population that does not get an arena per creature: ``batches`` ([(Morphology, ids)] per lane bucket, as
     reset_batches takes them) are streamed through ``slots`` slots of ``env`` (BatchedModular2D.reset_stream) -- ``step(chunk)``,

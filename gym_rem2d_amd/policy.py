@@ -93,6 +93,7 @@ class MLPPolicy:
         self.index, self.rays = index, rays
         self.n_sets, self.d, self.hidden, self.max_bodies, self.n_rays = G, D, H, MB, R
         self.parents = None     # int32 [G] on a policy that evolve() made: the set each of its sets came from
+        self.util = None        # int32 [M S] on a mean that es_update() made: the utilities of the children it was moved by
 
     # ---- construction ----
     @classmethod
@@ -258,3 +259,135 @@ class MLPPolicy:
         with torch.cuda.device(dev):
             _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
         return child
+
+    # ---- an evolution strategy around this policy as the mean (include/rem2d_es.h) ----
+    def _es_descriptor(self, what, generation, seed, group_size, pair_chunk=0):
+        """rem2d_es with this policy's shapes as the mean's, checked; no pointer is set."""
+        if self.index is not None:
+            raise ValueError("%s: a policy with an index shares weight sets among creatures; the mean is the sets of take() instead" % what)
+        if group_size is None or int(group_size) < 2 or int(group_size) % 2:
+            raise ValueError("%s: group_size (children per mean) must be even and at least 2, not %r" % (what, group_size))
+        if self.n_sets * int(group_size) > 2 ** 31 - 1:
+            raise ValueError("%s: %d means of group_size %d are more than 2^31 - 1 children" % (what, self.n_sets, int(group_size)))
+        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("%s: generation must fit 32 bits and seed 64 (unsigned)" % what)
+        if int(pair_chunk) < 0:
+            raise ValueError("%s: pair_chunk must be at least 0, not %r" % (what, pair_chunk))
+        e = _lib.Es()
+        e.d, e.hidden, e.max_bodies, e.n_means, e.group_size = self.d, self.hidden, self.max_bodies, self.n_sets, int(group_size)
+        e.pair_chunk, e.generation, e.reserved, e.seed = int(pair_chunk), int(generation), 0, int(seed)
+        return e
+
+    def _es_out(self, what, out, n_sets):
+        """``out`` checked as the destination of n_sets sets of this policy's per-set shapes that shares no memory with it."""
+        mine = (self.w1, self.b1, self.w2, self.b2)
+        if out is self or not isinstance(out, MLPPolicy):
+            raise ValueError("%s: out must be another MLPPolicy than the mean" % what)
+        theirs = (out.w1, out.b1, out.w2, out.b2)
+        if out.index is not None or any(tuple(a.shape) != (n_sets,) + tuple(b.shape[1:]) or a.device != b.device for a, b in zip(theirs, mine)):
+            raise ValueError("%s: out must have %d sets of this policy's shapes on its device, and no index" % (what, n_sets))
+        for a in theirs:            # (the library checks it too; here the message can name the argument)
+            for b in mine:
+                if a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
+                    raise ValueError("%s: out shares memory with the mean" % what)
+
+    def es_scratch_bytes(self, group_size, pair_chunk=0, wide=False):
+        """Bytes of scratch that ``es_update`` needs for this mean (rem2d_es_scratch_bytes); 0 where the update is one launch."""
+        e = self._es_descriptor("es_scratch_bytes", 0, 0, group_size, pair_chunk)
+        n = int(_lib.lib(wide).rem2d_es_scratch_bytes(C.byref(e)))
+        if n < 0:
+            _lib.check(n, wide)
+        return n
+
+    def es_sample(self, generation, seed=0, sigma=0.1, group_size=None, out=None, wide=False):
+        """The children of one generation of an evolution strategy whose mean this policy is: ``group_size`` = S sets around each
+        of its M sets, in antithetic pairs -- set ``b S + 2 q`` is ``mean[b] + sigma z`` and set ``b S + 2 q + 1`` is
+        ``mean[b] - sigma z`` -- made on the device by one library call (rem2d_es_sample; include/rem2d_es.h states the draw) on the
+        current stream; nothing synchronises and the library allocates nothing.  ``generation``, ``seed``: the random stream -- the
+        same pair gives the same children, bit for bit, in every build, and ``es_update`` regenerates the same noise from it.
+        ``out``: a policy of M S sets of the same per-set shapes whose weights are overwritten and which is returned; without it
+        new tensors.
+
+        Returns the child ``MLPPolicy`` of M S sets -- same activation, scale and rays."""
+        e = self._es_descriptor("es_sample", generation, seed, group_size)
+        G = self.n_sets * e.group_size
+        if out is not None:
+            self._es_out("es_sample", out, G)
+        if self.device.type != "cuda":
+            raise ValueError("es_sample: the weights are on %s; move the policy to the GPU with .to(device)" % self.device)
+        mine = (self.w1, self.b1, self.w2, self.b2)
+        if out is None:
+            child = self._like(*(torch.empty((G,) + tuple(t.shape[1:]), dtype=torch.float32, device=self.device) for t in mine), None)
+        else:
+            child = out
+            child.activation, child.scale, child.rays = self.activation, self.scale, self.rays
+        e.sigma = float(sigma)
+        e.w1, e.b1, e.w2, e.b2 = (t.data_ptr() for t in mine)
+        e.child_w1, e.child_b1, e.child_w2, e.child_b2 = (t.data_ptr() for t in (child.w1, child.b1, child.w2, child.b2))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib(wide).rem2d_es_sample(C.byref(e), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), wide)
+        return child
+
+    def es_update(self, fitness, generation, seed=0, sigma=0.1, lr=0.05, group_size=None, out=None, scratch=None, util=None,
+                  pair_chunk=0, wide=False):
+        """The new mean after one generation: the children's ``fitness`` -- float64 ``[M S]`` on the policy's device, in the order of
+        ``es_sample`` -- is turned into centred ranks within each block of S (ties averaged, NaN lowest) and the mean moves by
+        ``lr / (S sigma)`` times the rank-weighted sum of the noise, which the library regenerates from ``(seed, generation)``: the
+        children are not read, no noise was stored, and the sum is exact in 64-bit integers, so the result is the same bits whatever
+        the launch shape (rem2d_es_step; include/rem2d_es.h).  On the current stream; nothing synchronises and the library allocates
+        nothing.  ``sigma``, ``seed``, ``generation``, ``group_size``: what ``es_sample`` was given.  ``util``: int32 ``[M S]`` on the
+        device, the caller's own utilities instead of ranks -- ``fitness`` is not looked at (rem2d_es_update).  ``out``: a policy of
+        this policy's shapes whose weights -- and, where it has one, ``.util`` -- are overwritten and which is returned; without it
+        new tensors.  ``scratch``: a contiguous int64 tensor of at least ``es_scratch_bytes(group_size, pair_chunk) / 8`` entries
+        on the device; without it one is allocated where the update needs it (few means of many children).  ``pair_chunk``: pairs
+        per wavefront, 0 for the library's choice; no result depends on it.
+
+        Returns the new mean ``MLPPolicy`` -- same activation, scale and rays -- with ``.util``, int32 ``[M S]``."""
+        dev = self.device
+        e = self._es_descriptor("es_update", generation, seed, group_size, pair_chunk)
+        S = e.group_size
+        G = self.n_sets * S
+        if util is None:
+            if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
+                raise ValueError("es_update: fitness must be a torch.float64 tensor")
+            if tuple(fitness.shape) != (G,) or not fitness.is_contiguous():
+                raise ValueError("es_update: fitness must be a contiguous tensor of one entry per child [%d], not %s" % (G, list(fitness.shape)))
+            if fitness.device != dev:
+                raise ValueError("es_update: fitness must be on %s, not %s" % (dev, fitness.device))
+        elif (not isinstance(util, torch.Tensor) or util.dtype != torch.int32 or tuple(util.shape) != (G,) or not util.is_contiguous()
+              or util.device != dev):
+            raise ValueError("es_update: util must be a contiguous torch.int32 [%d] tensor on %s" % (G, dev))
+        if not float(sigma) > 0.0 or not math.isfinite(float(sigma)):
+            raise ValueError("es_update: sigma must be positive and finite, not %r" % (sigma,))
+        need = self.es_scratch_bytes(S, pair_chunk, wide)
+        if scratch is not None and (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.int64 or not scratch.is_contiguous()
+                                    or scratch.device != dev or scratch.numel() * 8 < need):
+            raise ValueError("es_update: scratch must be a contiguous torch.int64 tensor of at least %d entries on %s" % (need // 8, dev))
+        if out is not None:
+            self._es_out("es_update", out, self.n_sets)
+        if dev.type != "cuda":
+            raise ValueError("es_update: the weights are on %s; move the policy to the GPU with .to(device)" % dev)
+        mine = (self.w1, self.b1, self.w2, self.b2)
+        if out is None:
+            new = self._like(*(torch.empty_like(t) for t in mine), None)
+        else:
+            new = out
+            new.activation, new.scale, new.rays = self.activation, self.scale, self.rays
+        if util is not None:
+            new.util = util
+        elif new.util is None or tuple(new.util.shape) != (G,) or new.util.device != dev or new.util is self.util:
+            new.util = torch.empty(G, dtype=torch.int32, device=dev)
+        if scratch is None and need:
+            scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
+        e.sigma = float(sigma)
+        e.step = float(np.float32(float(lr) / (2.0 * (S - 1) * S * float(sigma))))
+        e.fitness = None if util is not None else fitness.data_ptr()
+        e.util = new.util.data_ptr()
+        e.w1, e.b1, e.w2, e.b2 = (t.data_ptr() for t in mine)
+        e.new_w1, e.new_b1, e.new_w2, e.new_b2 = (t.data_ptr() for t in (new.w1, new.b1, new.w2, new.b2))
+        e.scratch, e.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel() * 8)
+        L = _lib.lib(wide)
+        call = L.rem2d_es_step if util is None else L.rem2d_es_update
+        with torch.cuda.device(dev):
+            _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
+        return new
