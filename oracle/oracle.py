@@ -102,6 +102,7 @@ def _load(path):
         L.rem2d_oracle_get_contacts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.rem2d_oracle_get_manifold.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rem2d_oracle_get_fat_aabb.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rem2d_oracle_toi_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.rem2d_oracle_sincosf.argtypes = [C.c_float, C.c_void_p, C.c_void_p]
         L.rem2d_oracle_sin.restype = C.c_double
         L.rem2d_oracle_sin.argtypes = [C.c_double]
@@ -288,6 +289,13 @@ class World:
     @property
     def toi_dynamic_advances(self):
         return lib().rem2d_oracle_toi_dynamic_advances(self.h)
+
+    def toi_counters(self, reset=False):
+        """SolveTOI's read-only counters since their last reset -> dict(ties, count_max, count_skips, island_max, bodies): see
+        rem2d_oracle_toi_counters."""
+        out = np.zeros(5, dtype=np.int32)
+        lib().rem2d_oracle_toi_counters(self.h, _ptr(out), 1 if reset else 0)
+        return dict(zip(("ties", "count_max", "count_skips", "island_max", "bodies"), (int(v) for v in out)))
 
 
 # ---- standalone pieces for the known-answer tests ----

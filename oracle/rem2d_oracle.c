@@ -508,6 +508,11 @@ struct o_world {
     f32 staticAlpha0[O_MAX_STATICS];
     unsigned char staticIslandFlag[O_MAX_STATICS];
     int toiDynamicAdvances; /* times a static's alpha0 forced bB->m_sweep.Advance (provably never) */
+    /* bookkeeping only (no arithmetic reads them; rem2d_oracle_toi_counters): TOI events whose alpha pass held a LATER pair of the
+     * winner's body with the same minimal alpha; the most TOI events one pair took in one step; alpha-pass visits skipped by
+     * toiCount > b2_maxSubSteps; the most contacts in a sub-step island; events per body of the step under way */
+    int toiTies, toiCountMax, toiCountSkips, toiIslandMax;
+    unsigned char toiBodyEvent[O_MAX_BODIES];
     /* Modular2D state */
     double wod;
     int overflow;
@@ -2833,12 +2838,12 @@ static void world_solve_toi(o_world *w, const step_t *step) {
         }
     }
     for (;;) {
-        int minContact = -1;
+        int minContact = -1, tie = 0;
         f32 minAlpha = 1.0f;
         for (int k = 0; k < w->wcount; ++k) {
             contact_t *c = &w->contacts[w->wlist[k]];
             if (!c->enabled) continue;
-            if (c->toiCount > B2_MAX_SUB_STEPS) continue;
+            if (c->toiCount > B2_MAX_SUB_STEPS) { w->toiCountSkips++; continue; }
             f32 alpha = 1.0f;
             if (c->toiFlag) {
                 alpha = c->toi;
@@ -2876,9 +2881,11 @@ static void world_solve_toi(o_world *w, const step_t *step) {
                 c->toi = alpha;
                 c->toiFlag = 1;
             }
+            if (minContact >= 0 && alpha == minAlpha && c->body == w->contacts[minContact].body) tie = 1; /* (counter only) */
             if (alpha < minAlpha) {
                 minContact = w->wlist[k];
                 minAlpha = alpha;
+                tie = 0;
             }
         }
         if (minContact < 0 || 1.0f - 10.0f * B2_EPSILON < minAlpha) {
@@ -2896,6 +2903,7 @@ static void world_solve_toi(o_world *w, const step_t *step) {
         contact_update(w, mc);
         mc->toiFlag = 0;
         ++mc->toiCount;
+        if (mc->toiCount > w->toiCountMax) w->toiCountMax = mc->toiCount;
         if (!mc->enabled || !mc->touching) {
             mc->enabled = 0;
             w->staticAlpha0[sA0] = backup1;
@@ -2905,6 +2913,8 @@ static void world_solve_toi(o_world *w, const step_t *step) {
         }
         body_set_awake(w, bB, 1);
         w->toiEvents++;
+        w->toiTies += tie;
+        w->toiBodyEvent[bBi] = 1;
         /* Build the island: static A (slot IDX_STATIC), B, the contact, then B's other contacts */
         is->nbody = is->ncontact = is->njoint = 0;
         bB->islandIndex = 0;
@@ -2944,6 +2954,7 @@ static void world_solve_toi(o_world *w, const step_t *step) {
         subStep.positionIterations = 20;
         subStep.velocityIterations = step->velocityIterations;
         subStep.warmStarting = 0;
+        if (is->ncontact > w->toiIslandMax) w->toiIslandMax = is->ncontact;
         island_solve_toi(w, is, &subStep, 0);
         for (int i = 0; i < nIslandStatics; ++i) w->staticIslandFlag[islandStatics[i]] = 0;
         for (int i = 0; i < is->nbody; ++i) {
@@ -3083,6 +3094,15 @@ void rem2d_oracle_get_fat_aabb(const o_world *w, int body, float *out) {
 int rem2d_oracle_position_iterations(const o_world *w) { return w->lastPositionIterations; }
 int rem2d_oracle_toi_events(const o_world *w) { return w->toiEvents; }
 int rem2d_oracle_toi_dynamic_advances(const o_world *w) { return w->toiDynamicAdvances; }
+void rem2d_oracle_toi_counters(o_world *w, int *out, int reset) {
+    int bodies = 0;
+    for (int i = 0; i < w->nbody; ++i) bodies += w->toiBodyEvent[i];
+    out[0] = w->toiTies; out[1] = w->toiCountMax; out[2] = w->toiCountSkips; out[3] = w->toiIslandMax; out[4] = bodies;
+    if (reset) {
+        w->toiTies = w->toiCountMax = w->toiCountSkips = w->toiIslandMax = 0;
+        memset(w->toiBodyEvent, 0, sizeof(w->toiBodyEvent));
+    }
+}
 
 int rem2d_oracle_is_f64(void) { return (int)(sizeof(f32) == 8); }
 void rem2d_oracle_box_mass(float hx, float hy, float *mass, float *I) {

@@ -103,6 +103,11 @@ int rem2d_oracle_position_iterations(const o_world *); /* of last Solve */
 int rem2d_oracle_toi_events(const o_world *);          /* cumulative TOI sub-steps */
 /* times SolveTOI had to advance a dynamic body's sweep because its static partner's alpha0 was ahead */
 int rem2d_oracle_toi_dynamic_advances(const o_world *);
+/* Read-only counters of SolveTOI since the last reset of them (test infrastructure: no arithmetic reads them).  out[5]:
+ * TOI events whose alpha pass held a later pair of the same body with the same minimal alpha (the first one won);
+ * the most TOI events one pair took within one step (a pair beyond b2_maxSubSteps = 8 is skipped); alpha-pass visits skipped
+ * by that rule; the most contacts in one sub-step island; bodies that had at least one TOI event. */
+void rem2d_oracle_toi_counters(o_world *, int *out, int reset);
 
 /* standalone pieces for known-answer tests */
 void rem2d_oracle_sincosf(float a, float *s, float *c);

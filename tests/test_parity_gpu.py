@@ -587,6 +587,13 @@ def test_scalar_helpers_special_values(gpu, oracle):
     g2 = out2.cpu().numpy().reshape(5, m)
     sc = np.array([oracle.sincosf(float(x)) for x in ang[::7]], dtype=np.float32)
     assert np.array_equal(bits(g2[3][::7].copy()), bits(sc[:, 0].copy())) and np.array_equal(bits(g2[4][::7].copy()), bits(sc[:, 1].copy()))
+    # the appended specials sit at 199000 .. 199005, of which the stride of 7 meets one: +-0, both denormals and the huge angles, each
+    special = slice(199000, 199006)
+    assert ang[special].tolist() == [0.0, -0.0, np.float32(1e-45), np.float32(-1e-40), 1e6, -3e7] and np.signbit(ang[199001])
+    sp = np.array([oracle.sincosf(float(x)) for x in ang[special]], dtype=np.float32)
+    print("b2Rot::Set specials: angle, device (s, c), oracle (s, c):", [(float(x), float(g2[3][199000 + i]), float(g2[4][199000 + i]),
+                                                                       float(sp[i, 0]), float(sp[i, 1])) for i, x in enumerate(ang[special])])
+    assert np.array_equal(bits(g2[3][special].copy()), bits(sp[:, 0].copy())) and np.array_equal(bits(g2[4][special].copy()), bits(sp[:, 1].copy()))
 
 
 def test_worlds_step_argument_errors(gpu, flat_terrain):
