@@ -101,6 +101,10 @@ EVOLVE_ABI_VERSION = 1      # include/rem2d_evolve.h
 ORDER_ABI_VERSION = 1       # include/rem2d_order.h
 EVOLVE_MAX_TOURNSIZE = 4    # REM2D_EVOLVE_MAX_TOURNSIZE
 ES_ABI_VERSION = 1          # include/rem2d_es.h
+NOVELTY_ABI_VERSION = 1     # include/rem2d_novelty.h
+NOVELTY_MAX_WIDTH = 32      # REM2D_NOVELTY_MAX_WIDTH
+NOVELTY_MAX_K = 32          # REM2D_NOVELTY_MAX_K
+NOVELTY_MAX_SAMPLES = 16    # REM2D_NOVELTY_MAX_SAMPLES
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -182,6 +186,14 @@ class Es(C.Structure):
                 + [(k, C.c_void_p) for k in ("fitness", "util", "w1", "b1", "w2", "b2", "child_w1", "child_b1", "child_w2", "child_b2",
                                              "new_w1", "new_b1", "new_w2", "new_b2", "scratch")]
                 + [("scratch_bytes", C.c_uint64)])
+
+
+class Novelty(C.Structure):
+    """rem2d_novelty (include/rem2d_novelty.h): device pointers the caller owns."""
+    _fields_ = ([(k, C.c_int32) for k in ("width", "n_rows", "group_size", "k", "capacity")]
+                + [("generation", C.c_uint32), ("seed", C.c_uint64), ("add_threshold", C.c_uint64)]
+                + [(k, C.c_void_p) for k in ("desc", "archive", "total", "novelty", "add_mask")]
+                + [("reserved", C.c_int32)])
 
 
 class EpisodeOut(C.Structure):
@@ -432,6 +444,13 @@ def lib(wide=False):
         fn.argtypes = [C.POINTER(Es), C.c_void_p]
     if L.rem2d_es_abi_version() != ES_ABI_VERSION:
         raise Rem2dError("%s: es ABI version mismatch" % os.path.basename(path))
+    # behavioural novelty (include/rem2d_novelty.h)
+    L.rem2d_novelty_abi_version.restype = C.c_int
+    L.rem2d_worlds_describe.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    for fn in (L.rem2d_novelty_score, L.rem2d_novelty_add, L.rem2d_novelty_step):
+        fn.argtypes = [C.POINTER(Novelty), C.c_void_p]
+    if L.rem2d_novelty_abi_version() != NOVELTY_ABI_VERSION:
+        raise Rem2dError("%s: novelty ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

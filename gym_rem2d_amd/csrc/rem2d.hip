@@ -48,6 +48,7 @@
 #include <rem2d_evolve.h>  // (likewise)
 #include <rem2d_order.h>   // (the public header; it has no kernels of its own)
 #include <rem2d_es.h>      // (as rem2d_evolve.h: the quoted name below is the kernels' file)
+#include <rem2d_novelty.h> // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -109,6 +110,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_stream.h"
 #include "rem2d_evolve.h"
 #include "rem2d_es.h"
+#include "rem2d_novelty.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -2014,6 +2016,108 @@ extern "C" int rem2d_es_step(const rem2d_es *e, void *stream) {
     const int rc = es_ok("es_step", e, ES_SHAPE | ES_UPDATE);
     if (rc != REM2D_OK) return rc;
     return es_launch(e, ES_SHAPE | ES_UPDATE, (hipStream_t)stream);
+}
+
+// ---- behavioural novelty (include/rem2d_novelty.h, csrc/rem2d_novelty.h) ----
+extern "C" int rem2d_novelty_abi_version(void) { return REM2D_NOVELTY_ABI_VERSION; }
+static_assert(sizeof(CtlTable) + sizeof(NvTable) + 32 <= 4096, "rem2d_describe_kernel: kernel arguments within the 4 KB kernarg limit");
+static_assert(2 * REM2D_NOVELTY_MAX_SAMPLES <= REM2D_NOVELTY_MAX_WIDTH, "a descriptor row is a score row");
+extern "C" int rem2d_worlds_describe(rem2d_world *const *worlds, int32_t n_worlds, int32_t period, int32_t n_samples, float *out_dev,
+                                     int64_t out_rows, void *stream) {
+    if (period < 1) return fail(REM2D_E_INVALID, "describe: period must be at least 1, not " + std::to_string(period));
+    if (n_samples < 1 || n_samples > REM2D_NOVELTY_MAX_SAMPLES)
+        return fail(REM2D_E_INVALID, "describe: n_samples must be 1.." + std::to_string(REM2D_NOVELTY_MAX_SAMPLES) + ", not " + std::to_string(n_samples));
+    const int rc = control_worlds_ok("describe", worlds, n_worlds, 1, out_rows, out_dev);
+    if (rc != REM2D_OK) return rc;
+    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
+    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
+        CtlTable Tb;
+        NvTable Te;
+        const int n = std::min(CTL_TABLE, (int)n_worlds - first);
+        const unsigned blocks = control_table(Tb, worlds, first, n);
+        memset(&Te, 0, sizeof(Te));
+        for (int i = 0; i < n; ++i) Te.env4[i] = worlds[first + i]->S.env4;
+        const unsigned per = CTL_THREADS / WAVE;
+        hipLaunchKernelGGL(rem2d_describe_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Te,
+                           (int)period, (int)n_samples, out_dev, (long long)out_rows);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+enum { NV_SCORE = 1, NV_ADD = 2 };
+// Checks a novelty descriptor for the calls in `stages`.  Nothing it points to is read.
+static int nv_ok(const char *what, const rem2d_novelty *n, int stages) {
+    const std::string s = std::string(what) + ": ";
+    if (!n) return fail(REM2D_E_INVALID, s + "NULL descriptor");
+    if (n->width < 1 || n->width > REM2D_NOVELTY_MAX_WIDTH)
+        return fail(REM2D_E_INVALID, s + "width must be 1.." + std::to_string(REM2D_NOVELTY_MAX_WIDTH) + ", not " + std::to_string(n->width));
+    if (n->n_rows < 1) return fail(REM2D_E_INVALID, s + "n_rows must be at least 1, not " + std::to_string(n->n_rows));
+    if (n->group_size < 1 || n->n_rows % n->group_size != 0)
+        return fail(REM2D_E_INVALID, s + "group_size must be at least 1 and divide n_rows (" + std::to_string(n->n_rows) + "), not " + std::to_string(n->group_size));
+    if (n->k < 1 || n->k > REM2D_NOVELTY_MAX_K)
+        return fail(REM2D_E_INVALID, s + "k must be 1.." + std::to_string(REM2D_NOVELTY_MAX_K) + ", not " + std::to_string(n->k));
+    if (n->capacity < 0) return fail(REM2D_E_INVALID, s + "capacity must be at least 0, not " + std::to_string(n->capacity));
+    if (n->add_threshold > (1ull << 32)) return fail(REM2D_E_INVALID, s + "add_threshold must be at most 2^32");
+    if (n->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0");
+    if (!n->desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (desc)");
+    if (!n->total) return fail(REM2D_E_INVALID, s + "NULL device pointer (total)");
+    if (n->capacity > 0 && !n->archive) return fail(REM2D_E_INVALID, s + "NULL device pointer (archive)");
+    if ((stages & NV_SCORE) && !n->novelty) return fail(REM2D_E_INVALID, s + "NULL device pointer (novelty)");
+    const uintptr_t d = (uintptr_t)n->desc, dn = d + (uintptr_t)((size_t)n->n_rows * (size_t)n->width * sizeof(float));
+    if (n->capacity > 0) {
+        const size_t M = (size_t)(n->n_rows / n->group_size);
+        const uintptr_t a = (uintptr_t)n->archive, an = a + (uintptr_t)(M * (size_t)n->capacity * (size_t)n->width * sizeof(float));
+        if (a < dn && d < an) return fail(REM2D_E_INVALID, s + "archive overlaps desc");
+    }
+    if (stages & NV_SCORE) {
+        const uintptr_t a = (uintptr_t)n->novelty, an = a + (uintptr_t)((size_t)n->n_rows * sizeof(double));
+        if (a < dn && d < an) return fail(REM2D_E_INVALID, s + "novelty overlaps desc");
+    }
+    return REM2D_OK;
+}
+template <int BP> static void nv_launch_score(const NvArgs &A, int kp, dim3 grid, hipStream_t st) {
+    if (kp <= 2) hipLaunchKernelGGL((rem2d_novelty_score_kernel<BP, 2>), grid, dim3(NV_TILE), 0, st, A);
+    else if (kp <= 8) hipLaunchKernelGGL((rem2d_novelty_score_kernel<BP, 8>), grid, dim3(NV_TILE), 0, st, A);
+    else if (kp <= 16) hipLaunchKernelGGL((rem2d_novelty_score_kernel<BP, 16>), grid, dim3(NV_TILE), 0, st, A);
+    else hipLaunchKernelGGL((rem2d_novelty_score_kernel<BP, 32>), grid, dim3(NV_TILE), 0, st, A);
+}
+// The stages of a checked descriptor on `st`.
+static int nv_launch(const rem2d_novelty *n, int stages, hipStream_t st) {
+    NvArgs A;
+    memset(&A, 0, sizeof(A));
+    A.desc = n->desc; A.archive = n->archive; A.total = (long long *)n->total; A.novelty = n->novelty; A.mask = n->add_mask;
+    A.threshold = n->add_threshold;
+    A.key0 = (unsigned)(n->seed & 0xffffffffull); A.key1 = (unsigned)(n->seed >> 32); A.generation = n->generation;
+    A.B = n->width; A.G = n->n_rows; A.S = n->group_size; A.k = n->k; A.cap = n->capacity;
+    if (stages & NV_SCORE) {
+        const dim3 grid((unsigned)(((long long)A.G + NV_TILE - 1) / NV_TILE));
+        if (A.B <= 2) nv_launch_score<2>(A, A.k, grid, st);
+        else if (A.B <= 4) nv_launch_score<4>(A, A.k, grid, st);
+        else if (A.B <= 8) nv_launch_score<8>(A, A.k, grid, st);
+        else if (A.B <= 16) nv_launch_score<16>(A, A.k, grid, st);
+        else nv_launch_score<32>(A, A.k, grid, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (stages & NV_ADD) {
+        hipLaunchKernelGGL(rem2d_novelty_add_kernel, dim3((unsigned)(A.G / A.S)), dim3(NV_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+extern "C" int rem2d_novelty_score(const rem2d_novelty *n, void *stream) {
+    const int rc = nv_ok("novelty_score", n, NV_SCORE);
+    if (rc != REM2D_OK) return rc;
+    return nv_launch(n, NV_SCORE, (hipStream_t)stream);
+}
+extern "C" int rem2d_novelty_add(const rem2d_novelty *n, void *stream) {
+    const int rc = nv_ok("novelty_add", n, NV_ADD);
+    if (rc != REM2D_OK) return rc;
+    return nv_launch(n, NV_ADD, (hipStream_t)stream);
+}
+extern "C" int rem2d_novelty_step(const rem2d_novelty *n, void *stream) {
+    const int rc = nv_ok("novelty_step", n, NV_SCORE | NV_ADD);
+    if (rc != REM2D_OK) return rc;
+    return nv_launch(n, NV_SCORE | NV_ADD, (hipStream_t)stream);
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

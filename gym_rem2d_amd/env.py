@@ -187,6 +187,7 @@ class BatchedModular2D:
         self._policy = self._act_args = None   # set_policy()
         self._episodes = self._episode_args = self._autoreset = None   # episodes / reset_where() / set_autoreset()
         self._stream_rec = self._refill_args = None                    # reset_stream() / refill() / stream
+        self._descriptor = None                                        # set_descriptor() / describe() / behaviour
         self.last_episode = None      # evaluate.EpisodeReport of the population in place (None: no episode since its upload)
         over = launch_policy.read_overrides()   # (REM2D_MERGED_LAUNCH, REM2D_STEP_GROUPS, REM2D_GRAPH, REM2D_REBALANCE: read here, once)
         self.merged_launch = over.merged_launch   # False: step every lane bucket on its own stream instead of one merged grid
@@ -286,6 +287,7 @@ class BatchedModular2D:
         self._episodes = None                                  # reset_where()'s harvest buffers: made (zeroed) on first use after a reset
         self._episode_args = None
         self._stream_rec = self._refill_args = None            # (a streamed evaluation ends with the upload that replaces it)
+        self._descriptor = None                                # set_descriptor(): period, samples and the behaviour buffer
         # how this population runs -- step groups, tile shape, train or per-step launches, rebalancing, which creatures share a
         # world -- is launch_policy.plan's decision, from the buckets' shapes, this env's settings and the REM2D_* overrides
         plan = self._plan = self._make_plan(batches, n_envs)
@@ -699,6 +701,55 @@ class BatchedModular2D:
             if auto is not None:
                 self.reset_where(when=auto[0], max_steps=auto[1])
                 out = self._episodes.reward, self._episodes.done
+        return out
+
+    # ---- behaviour descriptors: where a creature went, sampled over its episode (include/rem2d_novelty.h) ----
+    def set_descriptor(self, period, samples=None):
+        """Give the population in place (after reset; a new upload drops it) a behaviour descriptor: the root position sampled
+        ``samples`` = K times (1 .. 16), every ``period`` steps, in ``behaviour``, float32 ``[N, 2 * samples]`` on the device, rows
+        in population order, allocated here, once, zeroed.  ``set_descriptor(None)`` detaches it.  Nothing records by itself:
+        ``describe()`` does, and ``evaluate.run_behaviour_episode`` calls it at the right steps.  step(), step_policy(), act()
+        and reset_where() are not affected.
+
+        Auto-reset and streaming are out of scope with a descriptor: a finished episode's row would be overwritten by the next
+        episode's before anyone reads it.  While ``set_autoreset`` is in force or a streamed evaluation is in place this raises
+        ValueError (and so does ``describe()``)."""
+        if period is None:
+            self._descriptor = None
+            return
+        if not self.worlds:
+            raise ValueError("set_descriptor: no population in place (reset first)")
+        if self._autoreset is not None or self._stream_rec is not None:
+            raise ValueError("set_descriptor: descriptors are not recorded under auto-reset or streaming: a finished episode's row "
+                             "would be overwritten before anyone reads it (set_autoreset(None) / upload the population with reset*)")
+        if samples is None or not 1 <= int(samples) <= _lib.NOVELTY_MAX_SAMPLES:
+            raise ValueError("set_descriptor: samples must be 1 .. %d, not %r" % (_lib.NOVELTY_MAX_SAMPLES, samples))
+        if int(period) < 1 or int(period) > 2 ** 31 - 1:
+            raise ValueError("set_descriptor: period must be 1 .. 2^31 - 1 steps, not %r" % (period,))
+        self._descriptor = (int(period), int(samples),
+                            torch.zeros((self.n_envs, 2 * int(samples)), dtype=torch.float32, device=self.worlds[0][0].device))
+
+    @property
+    def behaviour(self):
+        """The descriptor buffer of set_descriptor(), float32 ``[N, 2 * samples]`` (clone what must last), or None."""
+        return None if self._descriptor is None else self._descriptor[2]
+
+    def describe(self):
+        """Record where every creature is now: a creature whose episode is still running (not frozen) writes its root position
+        to every slot k of its ``behaviour`` row with ``(k + 1) * period >=`` its step count; a creature whose episode is over
+        writes nothing, so its row keeps what it held when it ended.  Called once after a reset and then every ``period`` steps,
+        slot k holds the position at step ``(k + 1) * period``, or the last one recorded before the episode ended.  One library call
+        for all lane buckets and step groups (rem2d_worlds_describe), queued on the current stream like observe(); nothing
+        synchronises.  Returns ``behaviour``."""
+        if self._descriptor is None:
+            raise ValueError("describe: no descriptor set (set_descriptor first)")
+        if self._autoreset is not None or self._stream_rec is not None:
+            raise ValueError("describe: descriptors are not recorded under auto-reset or streaming")
+        period, samples, out = self._descriptor
+        worlds = self._control_worlds()
+        if worlds:
+            from . import novelty
+            novelty.describe(worlds, period, samples, out)
         return out
 
     # ---- episode boundaries: a creature starts again the moment it ends (include/rem2d_episode.h) ----

@@ -351,6 +351,109 @@ def run_policy_es(env, mean, n_generations, seed=0, sigma=0.1, lr=0.05, group_si
     return mean, fit, history
 
 
+def run_behaviour_episode(env, period, samples, max_steps=EPISODE_CAP, on_error="raise"):
+    """An episode that records where every creature went: ``env.set_descriptor(period, samples)`` (kept where the env already has
+    that descriptor), ``describe()`` once at step 0, then ``period`` steps and ``describe()`` in turn -- ``env.step_policy`` if a
+    policy is attached, else ``env.step``, so the reference's oscillator-driven creatures are described as well -- until ``samples``
+    periods have run, or ``max_steps`` steps, or everyone is frozen (one small read per period).  Never compacts: compaction would
+    retire rows.  Returns ``(fitness, behaviour)``: float64 ``[N]`` (a clone) and the env's float32 ``[N, 2 * samples]`` descriptor
+    buffer itself (clone what must last), slot k the root position at step ``(k + 1) * period`` or the last one recorded before the
+    creature's episode ended (include/rem2d_novelty.h).  on_error: "raise" | "warn" | "ignore", as run_policy_episode."""
+    if on_error not in ("raise", "warn", "ignore"):
+        raise ValueError("on_error must be 'raise', 'warn' or 'ignore', not %r" % (on_error,))
+    if not env.worlds:
+        raise ValueError("run_behaviour_episode: no population in place (reset first)")
+    have = env._descriptor
+    if have is None or have[0] != int(period) or have[1] != (None if samples is None else int(samples)):
+        env.set_descriptor(period, samples)
+    period, samples = env._descriptor[:2]
+    step = env.step if env.policy is None else env.step_policy
+    env.last_episode = None
+    env.describe()
+    done_steps = 0
+    for _ in range(samples):
+        n = min(period, int(max_steps) - done_steps)
+        if n <= 0:
+            break
+        step(n)
+        done_steps += n
+        env.describe()
+        if bool((env.frozen != 0).all()):
+            break
+    check_errors(env, on_error)
+    return env.fitness.clone(), env.behaviour
+
+
+def _es_ranks(mean, values, group_size, out):
+    """Centred ranks of float64 ``values`` within blocks of group_size into int32 ``out`` (rem2d_es_shape: ties averaged, NaN lowest)."""
+    import ctypes as C
+    e = mean._es_descriptor("run_policy_nses", 0, 0, group_size)
+    e.fitness, e.util = values.data_ptr(), out.data_ptr()
+    dev = values.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rem2d_es_shape(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out
+
+
+def run_policy_nses(env, mean, n_generations, archive, k=15, rate=0.02, weights=(1, 1), period=None, samples=4, seed=0, sigma=0.1,
+                    lr=0.05, group_size=None, max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None):
+    """run_policy_es with behavioural novelty beside the fitness (NS-ES / NSR-ES): every generation is ``mean.es_sample``,
+    ``env.set_policy``, ``env.reset_where`` of everyone, ``run_behaviour_episode`` (``samples`` root positions, one every ``period``
+    steps; default period: ``max_steps`` over ``samples``, rounded up, so that the samples span the episode -- the episode ends after
+    ``min(samples * period, max_steps)`` steps), ``archive.step`` (a ``novelty.NoveltyArchive`` of M blocks of width ``2 * samples``
+    on the env's device: the k-nearest-neighbour novelty of every child among its block's peers and archive, then a share ``rate``
+    of the children joins the archive), the centred ranks of the fitness and of the novelty within each block, and
+    ``es_update(util = w_f * ranks(fitness) + w_n * ranks(novelty))`` with the integer ``weights`` (w_f, w_n): (1, 0) is
+    run_policy_es bit for bit, (0, 1) is NS-ES, (1, 1) NSR-ES.  The combination is int32 arithmetic on the device.  One child policy,
+    two sets of mean buffers and one each of novelty, rank and scratch tensors are reused throughout; ``mean`` itself is never
+    written.  Returns ``(mean, fitness, history)`` as run_policy_es, the history rows being ``(gen, min, max, mean)`` of the fitness.
+    ``on_generation(gen, children, fitness, mean, behaviour, novelty, util)``, if given, is called after every update with the
+    tensors themselves and the NEW mean (clone what must last)."""
+    if not env.worlds:
+        raise ValueError("run_policy_nses: no population in place (reset first)")
+    n = env.n_envs
+    S = n if group_size is None else int(group_size)
+    if S < 2 or S % 2 or n % S or mean.n_sets * S != n:
+        raise ValueError("run_policy_nses: %d creatures are not %d means times an even group_size (%r)" % (n, mean.n_sets, group_size))
+    wf, wn = (int(w) for w in weights)
+    if (wf, wn) != tuple(weights) or abs(wf) > 32767 or abs(wn) > 32767:
+        raise ValueError("run_policy_nses: weights must be two integers of at most 15 bits, not %r" % (weights,))
+    samples = int(samples)
+    period = -(-int(max_steps) // samples) if period is None else int(period)
+    if archive.n_blocks != mean.n_sets or archive.width != 2 * samples:
+        raise ValueError("run_policy_nses: the archive must have %d blocks of width %d, not %d of %d"
+                         % (mean.n_sets, 2 * samples, archive.n_blocks, archive.width))
+    dev = env.worlds[0][0].device
+    if archive.device != dev:
+        raise ValueError("run_policy_nses: the archive must be on %s, not %s" % (dev, archive.device))
+    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
+    mean = mean.to(dev)
+    children, spare, scratch, fit, history = None, None, None, None, []
+    need = mean.es_scratch_bytes(S)
+    if need:
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    nov = torch.empty(n, dtype=torch.float64, device=dev)
+    util_f, util_n, util = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    for gen in range(1, int(n_generations) + 1):
+        children = mean.es_sample(gen, seed=seed, sigma=sigma, group_size=S, out=children)
+        env.set_policy(children)
+        env.reset_where(mask=everyone)
+        fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+        archive.step(behaviour, gen, k=k, seed=seed, rate=rate, group_size=S, out=nov)
+        _es_ranks(mean, fit, S, util_f)
+        _es_ranks(mean, nov, S, util_n)
+        torch.add(util_f.mul_(wf), util_n, alpha=wn, out=util)
+        new = mean.es_update(None, gen, seed=seed, sigma=sigma, lr=lr, group_size=S, out=spare, scratch=scratch, util=util)
+        spare, mean = (mean if gen > 1 else None), new      # (the first mean's buffers are the caller's: never written)
+        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
+        history.append((gen,) + tuple(stats))
+        if on_generation:
+            on_generation(gen, children, fit, mean, behaviour, nov, util)
+        if log:
+            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+    return mean, fit, history
+
+
 def run_stream(env, batches, n_total, slots, max_steps=EPISODE_CAP, chunk=100, on_error="fallback"):
     """run_episode for a population that does not get an arena per creature: ``batches`` ([(Morphology, ids)] per lane bucket, as
     reset_batches takes them) are streamed through ``slots`` slots of ``env`` (BatchedModular2D.reset_stream) -- ``step(chunk)``,
