@@ -105,6 +105,10 @@ NOVELTY_ABI_VERSION = 1     # include/rem2d_novelty.h
 NOVELTY_MAX_WIDTH = 32      # REM2D_NOVELTY_MAX_WIDTH
 NOVELTY_MAX_K = 32          # REM2D_NOVELTY_MAX_K
 NOVELTY_MAX_SAMPLES = 16    # REM2D_NOVELTY_MAX_SAMPLES
+ELITES_ABI_VERSION = 1      # include/rem2d_elites.h
+ELITES_MAX_WIDTH = 32       # REM2D_ELITES_MAX_WIDTH
+ELITES_MAX_DIMS = 4         # REM2D_ELITES_MAX_DIMS
+ELITES_MAX_CELLS = 65536    # REM2D_ELITES_MAX_CELLS
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -194,6 +198,17 @@ class Novelty(C.Structure):
                 + [("generation", C.c_uint32), ("seed", C.c_uint64), ("add_threshold", C.c_uint64)]
                 + [(k, C.c_void_p) for k in ("desc", "archive", "total", "novelty", "add_mask")]
                 + [("reserved", C.c_int32)])
+
+
+class Elites(C.Structure):
+    """rem2d_elites (include/rem2d_elites.h): device pointers the caller owns."""
+    _fields_ = ([(k, C.c_int32) for k in ("d", "hidden", "max_bodies", "width", "n_blocks", "group_size", "n_children", "n_dims")]
+                + [("word", C.c_int32 * 4), ("bins", C.c_int32 * 4), ("lo", C.c_float * 4), ("inv", C.c_float * 4)]
+                + [("generation", C.c_uint32), ("sigma", C.c_float), ("rate_threshold", C.c_uint64), ("seed", C.c_uint64)]
+                + [(k, C.c_void_p) for k in ("desc", "fitness", "mask", "w1", "b1", "w2", "b2", "elite_fitness", "elite_desc",
+                                             "elite_w1", "elite_b1", "elite_w2", "elite_b2", "count", "cell", "winner", "child_w1",
+                                             "child_b1", "child_w2", "child_b2", "parent", "n_filled", "scratch")]
+                + [("scratch_bytes", C.c_uint64), ("reserved", C.c_int32)])
 
 
 class EpisodeOut(C.Structure):
@@ -451,6 +466,14 @@ def lib(wide=False):
         fn.argtypes = [C.POINTER(Novelty), C.c_void_p]
     if L.rem2d_novelty_abi_version() != NOVELTY_ABI_VERSION:
         raise Rem2dError("%s: novelty ABI version mismatch" % os.path.basename(path))
+    # MAP-Elites for device policies (include/rem2d_elites.h)
+    L.rem2d_elites_abi_version.restype = C.c_int
+    L.rem2d_elites_scratch_bytes.restype = C.c_int64
+    L.rem2d_elites_scratch_bytes.argtypes = [C.POINTER(Elites)]
+    for fn in (L.rem2d_elites_insert, L.rem2d_elites_sample, L.rem2d_elites_emit):
+        fn.argtypes = [C.POINTER(Elites), C.c_void_p]
+    if L.rem2d_elites_abi_version() != ELITES_ABI_VERSION:
+        raise Rem2dError("%s: elites ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

@@ -49,6 +49,7 @@
 #include <rem2d_order.h>   // (the public header; it has no kernels of its own)
 #include <rem2d_es.h>      // (as rem2d_evolve.h: the quoted name below is the kernels' file)
 #include <rem2d_novelty.h> // (likewise)
+#include <rem2d_elites.h>  // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -111,6 +112,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_evolve.h"
 #include "rem2d_es.h"
 #include "rem2d_novelty.h"
+#include "rem2d_elites.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -2118,6 +2120,196 @@ extern "C" int rem2d_novelty_step(const rem2d_novelty *n, void *stream) {
     const int rc = nv_ok("novelty_step", n, NV_SCORE | NV_ADD);
     if (rc != REM2D_OK) return rc;
     return nv_launch(n, NV_SCORE | NV_ADD, (hipStream_t)stream);
+}
+
+// ---- MAP-Elites for device policies (include/rem2d_elites.h, csrc/rem2d_elites.h) ----
+extern "C" int rem2d_elites_abi_version(void) { return REM2D_ELITES_ABI_VERSION; }
+static_assert(REM2D_ELITES_MAX_WIDTH == REM2D_NOVELTY_MAX_WIDTH, "an elite's descriptor row is a score row");
+static_assert(REM2D_ELITES_MAX_WIDTH <= WAVE, "rem2d_elites_commit_kernel: a lane per descriptor word");
+enum { EL_INSERT = 1, EL_SAMPLE = 2, EL_VARY = 4 };
+static bool el_finite(float v) { return std::isfinite(v); }
+// Checks the shapes and parameters of an elites descriptor; `s` prefixes the message.  No pointer is looked at.
+static int el_shapes_ok(const std::string &s, const rem2d_elites *e) {
+    if (!e) return fail(REM2D_E_INVALID, s + "NULL descriptor");
+    if (e->max_bodies < 1 || e->max_bodies > REM2D_CONTROL_MAX_BODIES)
+        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(e->max_bodies));
+    if (e->hidden < 1 || e->hidden > REM2D_POLICY_MAX_HIDDEN)
+        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(e->hidden));
+    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * e->max_bodies;
+    if (e->d < d0 || e->d > d0 + REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
+                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(e->d));
+    if (e->width < 1 || e->width > REM2D_ELITES_MAX_WIDTH)
+        return fail(REM2D_E_INVALID, s + "width must be 1.." + std::to_string(REM2D_ELITES_MAX_WIDTH) + ", not " + std::to_string(e->width));
+    if (e->n_blocks < 1) return fail(REM2D_E_INVALID, s + "n_blocks must be at least 1, not " + std::to_string(e->n_blocks));
+    if (e->n_dims < 1 || e->n_dims > REM2D_ELITES_MAX_DIMS)
+        return fail(REM2D_E_INVALID, s + "n_dims must be 1.." + std::to_string(REM2D_ELITES_MAX_DIMS) + ", not " + std::to_string(e->n_dims));
+    long long cells = 1;
+    for (int i = 0; i < e->n_dims; ++i) {
+        const std::string at = "[" + std::to_string(i) + "]";
+        if (e->word[i] < 0 || e->word[i] >= e->width)
+            return fail(REM2D_E_INVALID, s + "word" + at + " must be 0.." + std::to_string(e->width - 1) + ", not " + std::to_string(e->word[i]));
+        if (e->bins[i] < 1) return fail(REM2D_E_INVALID, s + "bins" + at + " must be at least 1, not " + std::to_string(e->bins[i]));
+        cells *= (long long)e->bins[i];
+        if (cells > (long long)REM2D_ELITES_MAX_CELLS)
+            return fail(REM2D_E_INVALID, s + "the product of bins must be at most " + std::to_string(REM2D_ELITES_MAX_CELLS) + " cells");
+        if (!el_finite(e->lo[i])) return fail(REM2D_E_INVALID, s + "lo" + at + " must be finite");
+        if (!el_finite(e->inv[i]) || !(e->inv[i] > 0.0f)) return fail(REM2D_E_INVALID, s + "inv" + at + " must be finite and positive");
+    }
+    if ((long long)e->n_blocks * cells > 2147483647ll) return fail(REM2D_E_INVALID, s + "n_blocks times the cells must be at most 2^31 - 1");
+    if (e->rate_threshold > (1ull << 32)) return fail(REM2D_E_INVALID, s + "rate_threshold must be at most 2^32");
+    if (e->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0");
+    return REM2D_OK;
+}
+static long long el_cells(const rem2d_elites *e) {
+    long long cells = 1;
+    for (int i = 0; i < e->n_dims; ++i) cells *= (long long)e->bins[i];
+    return cells;
+}
+static size_t el_scratch_need(const rem2d_elites *e) {
+    return (size_t)e->n_blocks * (size_t)el_cells(e) * (sizeof(unsigned long long) + sizeof(int));
+}
+static bool el_overlap(const void *a, size_t an, const void *b, size_t bn) {
+    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+    return p < q + (uintptr_t)bn && q < p + (uintptr_t)an;
+}
+// Checks an elites descriptor for the calls in `stages`.  Nothing it points to is read.
+static int el_ok(const char *what, const rem2d_elites *e, int stages) {
+    const std::string s = std::string(what) + ": ";
+    const int rc = el_shapes_ok(s, e);
+    if (rc != REM2D_OK) return rc;
+    const size_t slots = (size_t)e->n_blocks * (size_t)el_cells(e);
+    const size_t len[4] = {(size_t)e->d * (size_t)e->hidden, (size_t)e->hidden, (size_t)e->hidden * (size_t)e->max_bodies, (size_t)e->max_bodies};
+    const char *const name[4] = {"w1", "b1", "w2", "b2"};
+    const float *elite[4] = {e->elite_w1, e->elite_b1, e->elite_w2, e->elite_b2};
+    if (stages & EL_INSERT) {
+        if (e->group_size < 1) return fail(REM2D_E_INVALID, s + "group_size must be at least 1, not " + std::to_string(e->group_size));
+        if ((long long)e->n_blocks * (long long)e->group_size > 2147483647ll)
+            return fail(REM2D_E_INVALID, s + "n_blocks * group_size must be at most 2^31 - 1");
+    }
+    if (stages & (EL_SAMPLE | EL_VARY)) {
+        if (e->n_children < 1 || e->n_children % e->n_blocks != 0)
+            return fail(REM2D_E_INVALID, s + "n_children must be a positive multiple of n_blocks (" + std::to_string(e->n_blocks) + "), not " + std::to_string(e->n_children));
+    }
+    if (!e->count) return fail(REM2D_E_INVALID, s + "NULL device pointer (count)");
+    if (stages & EL_INSERT) {
+        const size_t G = (size_t)e->n_blocks * (size_t)e->group_size;
+        if (!e->desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (desc)");
+        if (!e->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
+        if (!e->elite_fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (elite_fitness)");
+        if (!e->elite_desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (elite_desc)");
+        if (!e->cell) return fail(REM2D_E_INVALID, s + "NULL device pointer (cell)");
+        if (!e->winner) return fail(REM2D_E_INVALID, s + "NULL device pointer (winner)");
+        const float *src[4] = {e->w1, e->b1, e->w2, e->b2};
+        for (int k = 0; k < 4; ++k)
+            if (!src[k] || !elite[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        const size_t dn = G * (size_t)e->width * sizeof(float);
+        if (el_overlap(e->desc, dn, e->elite_fitness, slots * sizeof(double))) return fail(REM2D_E_INVALID, s + "desc overlaps elite_fitness");
+        if (el_overlap(e->desc, dn, e->elite_desc, slots * (size_t)e->width * sizeof(float))) return fail(REM2D_E_INVALID, s + "desc overlaps elite_desc");
+        if (el_overlap(e->desc, dn, e->count, slots * sizeof(int))) return fail(REM2D_E_INVALID, s + "desc overlaps count");
+        for (int k = 0; k < 4; ++k)
+            if (el_overlap(e->desc, dn, elite[k], slots * len[k] * sizeof(float))) return fail(REM2D_E_INVALID, s + "desc overlaps elite_" + name[k]);
+        for (int k = 0; k < 4; ++k)
+            for (int j = 0; j < 4; ++j)
+                if (el_overlap(src[j], G * len[j] * sizeof(float), elite[k], slots * len[k] * sizeof(float)))
+                    return fail(REM2D_E_INVALID, s + "elite_" + name[k] + " overlaps the evaluated sets' " + name[j]);
+    }
+    if (stages & (EL_SAMPLE | EL_VARY)) {
+        if (!e->parent) return fail(REM2D_E_INVALID, s + "NULL device pointer (parent)");
+        if (!e->n_filled) return fail(REM2D_E_INVALID, s + "NULL device pointer (n_filled)");
+    }
+    if (stages & EL_VARY) {
+        const float *dst[4] = {e->child_w1, e->child_b1, e->child_w2, e->child_b2};
+        for (int k = 0; k < 4; ++k)
+            if (!dst[k] || !elite[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        for (int k = 0; k < 4; ++k)
+            for (int j = 0; j < 4; ++j)
+                if (el_overlap(dst[k], (size_t)e->n_children * len[k] * sizeof(float), elite[j], slots * len[j] * sizeof(float)))
+                    return fail(REM2D_E_INVALID, s + "child_" + name[k] + " overlaps elite_" + name[j]);
+    }
+    const size_t need = el_scratch_need(e);
+    if (!e->scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
+    if ((uintptr_t)e->scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
+    if (e->scratch_bytes < (uint64_t)need)
+        return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(e->scratch_bytes) + " bytes, " + std::to_string(need) + " are needed");
+    return REM2D_OK;
+}
+// The stages of a checked descriptor on `st`.
+static int el_launch(const rem2d_elites *e, int stages, hipStream_t st) {
+    ElArgs A;
+    EvolveArgs E;
+    memset(&A, 0, sizeof(A));
+    memset(&E, 0, sizeof(E));
+    const long long C = el_cells(e), slots = (long long)e->n_blocks * C;
+    A.desc = e->desc; A.fitness = e->fitness; A.mask = e->mask;
+    A.eliteFitness = e->elite_fitness; A.eliteDesc = e->elite_desc;
+    A.count = e->count; A.cell = e->cell; A.winner = e->winner; A.parent = e->parent; A.nFilled = e->n_filled;
+    A.key = (unsigned long long *)e->scratch;
+    A.row = (int *)(A.key + slots);
+    for (int i = 0; i < e->n_dims; ++i) { A.lo[i] = e->lo[i]; A.inv[i] = e->inv[i]; A.word[i] = e->word[i]; A.bins[i] = e->bins[i]; }
+    A.key0 = (unsigned)(e->seed & 0xffffffffull); A.key1 = (unsigned)(e->seed >> 32); A.generation = e->generation;
+    A.nDims = e->n_dims; A.B = e->width; A.M = e->n_blocks; A.S = e->group_size; A.C = (int)C;
+    E.len[0] = e->d * e->hidden; E.len[1] = e->hidden; E.len[2] = e->hidden * e->max_bodies; E.len[3] = e->max_bodies;
+    float *const elite[4] = {e->elite_w1, e->elite_b1, e->elite_w2, e->elite_b2};
+    if (stages & EL_INSERT) {
+        const long long G = (long long)A.M * (long long)A.S;
+        const float *src[4] = {e->w1, e->b1, e->w2, e->b2};
+        for (int k = 0; k < 4; ++k) {
+            E.src[k] = src[k];
+            E.dst[k] = elite[k];
+            E.vec[k] = E.len[k] % 4 == 0 && (uintptr_t)E.src[k] % 16 == 0 && (uintptr_t)E.dst[k] % 16 == 0;
+        }
+        hipLaunchKernelGGL(rem2d_elites_clear_kernel, dim3((unsigned)((slots + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rem2d_elites_key_kernel, dim3((unsigned)((G + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rem2d_elites_row_kernel, dim3((unsigned)((G + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rem2d_elites_commit_kernel, dim3((unsigned)slots), dim3(WAVE), 0, st, A, E);
+        HIP_TRY(hipGetLastError());
+    }
+    if (stages & EL_SAMPLE) {
+        A.perBlock = e->n_children / e->n_blocks;
+        hipLaunchKernelGGL(rem2d_elites_sample_kernel, dim3((unsigned)A.M), dim3(EL_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    if (stages & EL_VARY) {
+        // rem2d_evolve_vary_kernel as it is: the elite arrays are the "parents", M C bounds p, a workgroup per child
+        float *const dst[4] = {e->child_w1, e->child_b1, e->child_w2, e->child_b2};
+        for (int k = 0; k < 4; ++k) {
+            E.src[k] = elite[k];
+            E.dst[k] = dst[k];
+            E.vec[k] = E.len[k] % 4 == 0 && (uintptr_t)E.src[k] % 16 == 0 && (uintptr_t)E.dst[k] % 16 == 0;
+        }
+        E.parent = e->parent;
+        E.rateThreshold = e->rate_threshold;
+        E.key0 = A.key0; E.key1 = A.key1; E.generation = e->generation;
+        E.G = (int)slots; E.S = 1; E.T = 1; E.elite = 0;
+        E.sigma = e->sigma;
+        hipLaunchKernelGGL(rem2d_evolve_vary_kernel, dim3((unsigned)e->n_children), dim3(WAVE), 0, st, E);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+extern "C" int64_t rem2d_elites_scratch_bytes(const rem2d_elites *e) {
+    const int rc = el_shapes_ok("elites_scratch_bytes: ", e);
+    if (rc != REM2D_OK) return rc;
+    return (int64_t)el_scratch_need(e);
+}
+extern "C" int rem2d_elites_insert(const rem2d_elites *e, void *stream) {
+    const int rc = el_ok("elites_insert", e, EL_INSERT);
+    if (rc != REM2D_OK) return rc;
+    return el_launch(e, EL_INSERT, (hipStream_t)stream);
+}
+extern "C" int rem2d_elites_sample(const rem2d_elites *e, void *stream) {
+    const int rc = el_ok("elites_sample", e, EL_SAMPLE);
+    if (rc != REM2D_OK) return rc;
+    return el_launch(e, EL_SAMPLE, (hipStream_t)stream);
+}
+extern "C" int rem2d_elites_emit(const rem2d_elites *e, void *stream) {
+    const int rc = el_ok("elites_emit", e, EL_SAMPLE | EL_VARY);
+    if (rc != REM2D_OK) return rc;
+    return el_launch(e, EL_SAMPLE | EL_VARY, (hipStream_t)stream);
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

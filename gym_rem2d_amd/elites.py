@@ -1,0 +1,273 @@
+"""MAP-Elites for device policies (include/rem2d_elites.h): per block of creatures -- a morphology -- a grid over behaviour space
+whose every cell keeps the best controller ever seen there, with its fitness and its descriptor row, on the device.
+
+``EliteGrid.insert`` files a whole evaluated population (an ``MLPPolicy``, its float64 fitness and its float32 descriptors, as
+``evaluate.run_behaviour_episode`` returns them) into the grids; ``EliteGrid.emit`` makes the next children, mutated copies of
+uniformly drawn elites, with the mutation of ``MLPPolicy.evolve``; ``evaluate.run_policy_map_elites`` is the loop.
+
+Nothing here allocates after the grid was made and ``out=`` is given; every call is one library call queued on the current stream;
+nothing synchronises.  tests/elites_model.py restates every output bit in numpy."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .policy import MLPPolicy
+
+
+def rate_threshold(rate):
+    """floor(rate * 2^32), the ``rate_threshold`` of a rate in [0, 1] (the product of a binary64 by 2^32 is exact)"""
+    return int(math.floor(float(rate) * 4294967296.0))
+
+
+def _check_dims(dims, width):
+    """dims [(word, lo, hi, bins), ...] -> (word, bins, lo float32, inv float32) lists, checked"""
+    try:
+        dims = [tuple(d) for d in dims]
+    except TypeError:
+        raise ValueError("EliteGrid: dims must be a list of (word, lo, hi, bins)")
+    if not 1 <= len(dims) <= _lib.ELITES_MAX_DIMS or any(len(d) != 4 for d in dims):
+        raise ValueError("EliteGrid: dims must be 1 .. %d tuples (word, lo, hi, bins), not %r" % (_lib.ELITES_MAX_DIMS, dims))
+    word, bins, lo, inv, cells = [], [], [], [], 1
+    for i, (w, l, h, n) in enumerate(dims):
+        if int(w) != w or not 0 <= int(w) < width:
+            raise ValueError("EliteGrid: dims[%d]: word must be 0 .. %d, not %r" % (i, width - 1, w))
+        if int(n) != n or int(n) < 1:
+            raise ValueError("EliteGrid: dims[%d]: bins must be at least 1, not %r" % (i, n))
+        with np.errstate(all="ignore"):
+            l32, h32 = np.float32(l), np.float32(h)
+            v = np.float32(int(n)) / (h32 - l32)
+        if not np.isfinite(l32) or not np.isfinite(h32) or not h32 > l32:
+            raise ValueError("EliteGrid: dims[%d]: lo and hi must be finite binary32 values with lo < hi, not %r, %r" % (i, l, h))
+        if not np.isfinite(v) or not v > 0:
+            raise ValueError("EliteGrid: dims[%d]: bins / (hi - lo) is not a finite positive binary32 value" % i)
+        cells *= int(n)
+        if cells > _lib.ELITES_MAX_CELLS:
+            raise ValueError("EliteGrid: the product of bins must be at most %d cells" % _lib.ELITES_MAX_CELLS)
+        word.append(int(w)); bins.append(int(n)); lo.append(float(l32)); inv.append(float(v))
+    return word, bins, lo, inv, cells
+
+
+class EliteGrid:
+    """``n_blocks`` grids of C = the product of the ``bins`` cells over descriptor rows of ``width`` words; ``dims``: one
+    ``(word, lo, hi, bins)`` per dimension (1 .. 4), the cell of a row along it being ``int((row[word] - lo) * (bins / (hi - lo)))``
+    in binary32, clamped to ``[0, bins - 1]`` (the header states every rounding).  ``like``: an ``MLPPolicy`` whose per-set shapes,
+    activation, scale and rays the elites have.  The tensors, zeroed to begin with, all on ``device``:
+
+    ``fitness`` float64 ``[M, C]``, ``desc`` float32 ``[M, C, width]``, ``count`` int32 ``[M, C]`` (a cell is empty iff its count is
+    0), ``w1 [M C, D, H]``, ``b1``, ``w2``, ``b2`` (slot ``b C + q`` is one weight set), ``winner`` int32 ``[M, C]`` and, after an
+    ``insert`` of G rows, ``cell`` int32 ``[G]``."""
+
+    def __init__(self, n_blocks, dims, width, like, device=None):
+        n_blocks, width = int(n_blocks), int(width)
+        if n_blocks < 1:
+            raise ValueError("EliteGrid: n_blocks must be at least 1, not %r" % (n_blocks,))
+        if not 1 <= width <= _lib.ELITES_MAX_WIDTH:
+            raise ValueError("EliteGrid: width must be 1 .. %d, not %r" % (_lib.ELITES_MAX_WIDTH, width))
+        if not isinstance(like, MLPPolicy):
+            raise ValueError("EliteGrid: like must be an MLPPolicy (the shapes of the weight sets the grid keeps)")
+        self.word, self.bins, self.lo, self.inv, C_ = _check_dims(dims, width)
+        if n_blocks * C_ > 2 ** 31 - 1:
+            raise ValueError("EliteGrid: %d blocks of %d cells are more than 2^31 - 1 slots" % (n_blocks, C_))
+        self.n_blocks, self.width, self.n_cells, self.dims = n_blocks, width, C_, [tuple(d) for d in dims]
+        self.d, self.hidden, self.max_bodies = like.d, like.hidden, like.max_bodies
+        self.like = like
+        dev = "cpu" if device is None else device
+        slots = n_blocks * C_
+        self.fitness = torch.zeros((n_blocks, C_), dtype=torch.float64, device=dev)
+        self.device = self.fitness.device                   # (with its index: "cuda" became "cuda:0")
+        dev = self.device
+        self.desc = torch.zeros((n_blocks, C_, width), dtype=torch.float32, device=dev)
+        self.count = torch.zeros((n_blocks, C_), dtype=torch.int32, device=dev)
+        self.winner = torch.full((n_blocks, C_), -1, dtype=torch.int32, device=dev)
+        self.w1 = torch.zeros((slots, like.d, like.hidden), dtype=torch.float32, device=dev)
+        self.b1 = torch.zeros((slots, like.hidden), dtype=torch.float32, device=dev)
+        self.w2 = torch.zeros((slots, like.hidden, like.max_bodies), dtype=torch.float32, device=dev)
+        self.b2 = torch.zeros((slots, like.max_bodies), dtype=torch.float32, device=dev)
+        self.filled = torch.zeros(n_blocks, dtype=torch.int32, device=dev)     # n_filled as the last sample / emit wrote it
+        self.scratch = torch.zeros((slots * 12 + 7) // 8, dtype=torch.int64, device=dev)
+        self.cell = None
+        self._keep = None
+
+    # ---- what the grid holds (torch on its own tensors) ----
+    @property
+    def n_filled(self):
+        """int64 ``[M]``: the filled cells of every block"""
+        return (self.count != 0).sum(dim=1)
+
+    def coverage(self):
+        """float64 ``[M]``: the filled share of every block's cells"""
+        return self.n_filled.to(torch.float64) / float(self.n_cells)
+
+    def qd_score(self):
+        """float64 ``[M]``: the sum of the fitness over every block's filled cells"""
+        return torch.where(self.count != 0, self.fitness, torch.zeros_like(self.fitness)).sum(dim=1)
+
+    def elites(self, block):
+        """The ``MLPPolicy`` of the filled cells of ``block``, in ascending cell order (a copy)."""
+        b = int(block)
+        if not 0 <= b < self.n_blocks:
+            raise ValueError("elites: block must be 0 .. %d, not %r" % (self.n_blocks - 1, block))
+        q = torch.nonzero(self.count[b] != 0).flatten()
+        if q.numel() == 0:
+            raise ValueError("elites: block %d has no filled cell" % b)
+        sel = q + b * self.n_cells
+        return self.like._like(self.w1[sel], self.b1[sel], self.w2[sel], self.b2[sel], None)
+
+    # ---- checkpoints ----
+    _STATE = ("fitness", "desc", "count", "w1", "b1", "w2", "b2")
+
+    def state_dict(self):
+        return {k: getattr(self, k).clone() for k in self._STATE}
+
+    def load_state_dict(self, state):
+        for k in self._STATE:
+            have, t = getattr(self, k), state[k]
+            if tuple(t.shape) != tuple(have.shape) or t.dtype != have.dtype:
+                raise ValueError("load_state_dict: %s must be %s %s, not %s %s" % (k, have.dtype, list(have.shape), t.dtype, list(t.shape)))
+        for k in self._STATE:
+            getattr(self, k).copy_(state[k])
+
+    # ---- the library's descriptor ----
+    def _descriptor(self, generation=0, seed=0, rate=0.0, sigma=0.0):
+        e = _lib.Elites()
+        e.d, e.hidden, e.max_bodies, e.width, e.n_blocks, e.n_dims = self.d, self.hidden, self.max_bodies, self.width, self.n_blocks, len(self.word)
+        for i in range(len(self.word)):
+            e.word[i], e.bins[i], e.lo[i], e.inv[i] = self.word[i], self.bins[i], self.lo[i], self.inv[i]
+        e.generation, e.sigma, e.rate_threshold, e.seed, e.reserved = int(generation), float(sigma), rate_threshold(rate), int(seed), 0
+        e.elite_fitness, e.elite_desc, e.count = self.fitness.data_ptr(), self.desc.data_ptr(), self.count.data_ptr()
+        e.elite_w1, e.elite_b1, e.elite_w2, e.elite_b2 = (t.data_ptr() for t in (self.w1, self.b1, self.w2, self.b2))
+        e.winner, e.n_filled = self.winner.data_ptr(), self.filled.data_ptr()
+        e.scratch, e.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel() * 8
+        return e
+
+    def _call(self, name, e, wide):
+        L = _lib.lib(wide)
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(L, name)(C.byref(e), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), wide)
+
+    def _fits(self, what, policy, n_sets=None):
+        if not isinstance(policy, MLPPolicy) or policy.index is not None:
+            raise ValueError("%s: the policy must be an MLPPolicy without an index" % what)
+        if (policy.d, policy.hidden, policy.max_bodies) != (self.d, self.hidden, self.max_bodies):
+            raise ValueError("%s: the policy's sets are [%d, %d] -> [%d], the grid's [%d, %d] -> [%d]"
+                             % (what, policy.d, policy.hidden, policy.max_bodies, self.d, self.hidden, self.max_bodies))
+        if policy.device != self.device:
+            raise ValueError("%s: the policy must be on %s, not %s" % (what, self.device, policy.device))
+        if n_sets is not None and policy.n_sets != n_sets:
+            raise ValueError("%s: the policy must have %d weight sets, not %d" % (what, n_sets, policy.n_sets))
+        mine = (self.w1, self.b1, self.w2, self.b2)
+        for a in (policy.w1, policy.b1, policy.w2, policy.b2):
+            for b in mine:
+                if a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
+                    raise ValueError("%s: the policy shares memory with the grid" % what)
+
+    def insert(self, policy, fitness, desc, mask=None, group_size=None, wide=False):
+        """File the G evaluated sets of ``policy`` into the grids (rem2d_elites_insert): ``fitness`` float64 ``[G]``, ``desc``
+        float32 ``[G, width]``, ``mask`` bool / uint8 ``[G]`` (None: everyone), all on the grid's device; blocks of ``group_size``
+        consecutive rows (default G over n_blocks).  Per block and cell the row of greatest fitness (ties: the lowest row; NaN
+        fitness and rows with a non-finite selected word are not admitted) replaces the incumbent iff the cell is empty or it is
+        strictly better.  Returns ``winner`` int32 ``[M, C]``: the row that took the cell, or -1; ``self.cell`` int32 ``[G]`` is
+        every row's cell, -1 for a row that was not admitted."""
+        dev = self.device
+        self._fits("insert", policy)
+        G = policy.n_sets
+        if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
+            raise ValueError("insert: fitness must be a torch.float64 tensor")
+        if tuple(fitness.shape) != (G,) or not fitness.is_contiguous() or fitness.device != dev:
+            raise ValueError("insert: fitness must be a contiguous tensor of one entry per weight set [%d] on %s, not %s" % (G, dev, list(fitness.shape)))
+        if not isinstance(desc, torch.Tensor) or desc.dtype != torch.float32:
+            raise ValueError("insert: desc must be a torch.float32 tensor")
+        if tuple(desc.shape) != (G, self.width) or not desc.is_contiguous() or desc.device != dev:
+            raise ValueError("insert: desc must be a contiguous tensor [%d, %d] on %s, not %s" % (G, self.width, dev, list(desc.shape)))
+        if group_size is None:
+            if G % self.n_blocks:
+                raise ValueError("insert: %d rows are not %d blocks of one group_size" % (G, self.n_blocks))
+            group_size = G // self.n_blocks
+        S = int(group_size)
+        if S < 1 or S * self.n_blocks != G:
+            raise ValueError("insert: %d rows in groups of %r are not the grid's %d blocks" % (G, group_size, self.n_blocks))
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("insert: mask must be a torch.bool or torch.uint8 tensor")
+            if tuple(mask.shape) != (G,) or not mask.is_contiguous() or mask.device != dev:
+                raise ValueError("insert: mask must be a contiguous tensor of one entry per row [%d] on %s, not %s" % (G, dev, list(mask.shape)))
+        for name, other in (("fitness", self.fitness), ("desc", self.desc), ("count", self.count), ("w1", self.w1), ("b1", self.b1),
+                            ("w2", self.w2), ("b2", self.b2)):
+            a, an = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
+            b, bn = desc.data_ptr(), desc.data_ptr() + desc.numel() * 4
+            if a < bn and b < an:
+                raise ValueError("insert: desc shares memory with the grid's %s" % name)
+        if dev.type != "cuda":
+            raise ValueError("insert: the grid is on %s; make it on the GPU (device=...)" % dev)
+        if self.cell is None or tuple(self.cell.shape) != (G,):
+            self.cell = torch.empty(G, dtype=torch.int32, device=dev)
+        e = self._descriptor()
+        e.group_size = S
+        e.desc, e.fitness, e.mask = desc.data_ptr(), fitness.data_ptr(), None if mask is None else mask.data_ptr()
+        e.w1, e.b1, e.w2, e.b2 = (t.data_ptr() for t in (policy.w1, policy.b1, policy.w2, policy.b2))
+        e.cell = self.cell.data_ptr()
+        self._keep = (policy, fitness, desc, mask)          # (the tensors the queued kernels read)
+        self._call("rem2d_elites_insert", e, wide)
+        return self.winner
+
+    def _draw(self, what, generation, seed, n_children, parents):
+        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("%s: generation must fit 32 bits and seed 64 (unsigned)" % what)
+        n = self.n_blocks if n_children is None else int(n_children)
+        if n < 1 or n % self.n_blocks or n > 2 ** 31 - 1:
+            raise ValueError("%s: n_children must be a positive multiple of the grid's %d blocks, not %r" % (what, self.n_blocks, n_children))
+        if parents is not None and (not isinstance(parents, torch.Tensor) or parents.dtype != torch.int32 or tuple(parents.shape) != (n,)
+                                    or not parents.is_contiguous() or parents.device != self.device):
+            raise ValueError("%s: parents must be a contiguous torch.int32 [%d] tensor on %s" % (what, n, self.device))
+        return n
+
+    def sample(self, generation, seed=0, n_children=None, out=None, wide=False):
+        """The draw alone (rem2d_elites_sample): ``parents`` int32 ``[n_children]``, for each child the slot ``b C + q`` of a
+        uniformly drawn filled cell of its block -- a function of ``(seed, generation, child)`` and the set of filled cells -- or -1
+        where the block's grid is empty; ``n_children`` consecutive children per block, a multiple of n_blocks.  ``self.filled``
+        int32 ``[M]`` holds the filled cells it counted.  ``out``: the int32 tensor to write."""
+        n = self._draw("sample", generation, seed, n_children, out)
+        if self.device.type != "cuda":
+            raise ValueError("sample: the grid is on %s; make it on the GPU (device=...)" % self.device)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=self.device)
+        e = self._descriptor(generation, seed)
+        e.n_children, e.parent = n, out.data_ptr()
+        self._call("rem2d_elites_sample", e, wide)
+        return out
+
+    def emit(self, generation, seed=0, rate=0.05, sigma=0.1, n_children=None, out=None, wide=False):
+        """The next children (rem2d_elites_emit): ``n_children`` sets (a multiple of n_blocks; default: those of ``out``, else one
+        per block), child c a copy of the elite ``sample`` draws for it, mutated as ``MLPPolicy.evolve`` mutates -- ``rate`` the
+        probability that an element is hit, ``sigma`` the step, the same ``(seed, generation)`` the same bits in every build.  A
+        child of a block whose grid is empty keeps the words its buffer holds (zeros in a new one).  ``out``: an ``MLPPolicy`` of
+        n_children sets of the grid's shapes whose weights and ``.parents`` are overwritten and which is returned.
+
+        Returns the child ``MLPPolicy`` with ``.parents`` int32 ``[n_children]`` (slots of the grid, or -1)."""
+        if out is not None:
+            self._fits("emit", out, None if n_children is None else int(n_children))
+            if n_children is None:
+                n_children = out.n_sets
+        have = None if out is None else out.parents
+        n = self._draw("emit", generation, seed, n_children, None)
+        if not 0.0 <= float(rate) <= 1.0:
+            raise ValueError("emit: rate must be in [0, 1], not %r" % (rate,))
+        if self.device.type != "cuda":
+            raise ValueError("emit: the grid is on %s; make it on the GPU (device=...)" % self.device)
+        dev = self.device
+        if out is None:
+            out = self.like._like(*(torch.zeros((n,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+                                     for t in (self.w1, self.b1, self.w2, self.b2)), None)
+        else:
+            out.activation, out.scale, out.rays = self.like.activation, self.like.scale, self.like.rays
+        if have is None or have.dtype != torch.int32 or tuple(have.shape) != (n,) or have.device != dev or not have.is_contiguous():
+            have = torch.empty(n, dtype=torch.int32, device=dev)
+        out.parents = have
+        e = self._descriptor(generation, seed, rate, sigma)
+        e.n_children, e.parent = n, have.data_ptr()
+        e.child_w1, e.child_b1, e.child_w2, e.child_b2 = (t.data_ptr() for t in (out.w1, out.b1, out.w2, out.b2))
+        self._call("rem2d_elites_emit", e, wide)
+        return out

@@ -454,6 +454,61 @@ def run_policy_nses(env, mean, n_generations, archive, k=15, rate=0.02, weights=
     return mean, fit, history
 
 
+def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples=4, seed=0, rate=0.05, sigma=0.1, group_size=None,
+                          max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None):
+    """MAP-Elites for device policies: ``grid`` (an ``elites.EliteGrid`` of M = n_envs / ``group_size`` blocks over descriptor rows
+    of ``2 * samples`` words on the env's device) keeps, per block of consecutive creatures -- a morphology -- and per cell of
+    behaviour space, the best controller seen so far.  Generation 0 evaluates ``policy`` (one weight set per creature of ``env``,
+    reset first) with ``run_behaviour_episode`` (``samples`` root positions, one every ``period`` steps; default period:
+    ``max_steps`` over ``samples``, rounded up) and inserts it; every generation g = 1 .. is ``grid.emit`` (generation g, this
+    ``seed``, ``rate`` and ``sigma`` as ``MLPPolicy.evolve`` takes them) into ONE reused child policy, ``env.set_policy``,
+    ``env.reset_where`` of everyone, ``run_behaviour_episode`` and ``grid.insert``.  Emit reads the grid, not the previous children,
+    so there is no double buffer; a block whose grid is still empty (nobody admissible so far) runs its children again as they are;
+    ``policy`` itself is never written.  Returns ``(grid, fitness, history)``: the last generation's fitness (float64 [N] on the
+    device) and rows ``(gen, min, max, mean, filled cells, qd_score)``, generation 0's included, the only numbers that leave the
+    device.  ``on_generation(gen, children, fitness, behaviour, grid)``, if given, is called after every insert with the tensors
+    themselves (clone what must last).  Like ``describe`` it raises under auto-reset or streaming."""
+    from .elites import EliteGrid
+    if not isinstance(grid, EliteGrid):
+        raise ValueError("run_policy_map_elites: grid must be an elites.EliteGrid")
+    if not env.worlds:
+        raise ValueError("run_policy_map_elites: no population in place (reset first)")
+    if env._autoreset is not None or env._stream_rec is not None:
+        raise ValueError("run_policy_map_elites: descriptors are not recorded under auto-reset or streaming")
+    n = env.n_envs
+    S = n // grid.n_blocks if group_size is None else int(group_size)
+    if S < 1 or S * grid.n_blocks != n:
+        raise ValueError("run_policy_map_elites: %d creatures in groups of %r are not the grid's %d blocks" % (n, group_size, grid.n_blocks))
+    if policy.index is not None or policy.n_sets != n:
+        raise ValueError("run_policy_map_elites: the policy must hold one weight set per creature (%d), without an index" % n)
+    samples = int(samples)
+    if grid.width != 2 * samples:
+        raise ValueError("run_policy_map_elites: the grid must be over rows of %d words (2 * samples), not %d" % (2 * samples, grid.width))
+    period = -(-int(max_steps) // samples) if period is None else int(period)
+    dev = env.worlds[0][0].device
+    if grid.device != dev:
+        raise ValueError("run_policy_map_elites: the grid must be on %s, not %s" % (dev, grid.device))
+    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
+    policy = policy.to(dev)
+    children, fit, history = policy, None, []
+    for gen in range(0, int(n_generations) + 1):
+        if gen > 0:
+            if children is policy:      # the one child buffer, made of the caller's sets: what a still empty block runs again
+                children = policy._like(policy.w1.clone(), policy.b1.clone(), policy.w2.clone(), policy.b2.clone(), None)
+            grid.emit(gen, seed=seed, rate=rate, sigma=sigma, n_children=n, out=children)
+            env.reset_where(mask=everyone)
+        env.set_policy(children)
+        fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+        grid.insert(children, fit, behaviour, group_size=S)
+        stats = torch.stack((fit.min(), fit.max(), fit.mean(), grid.n_filled.sum().to(torch.float64), grid.qd_score().sum())).cpu().tolist()
+        history.append((gen,) + tuple(stats[:3]) + (int(stats[3]), stats[4]))
+        if on_generation:
+            on_generation(gen, children, fit, behaviour, grid)
+        if log:
+            log("Generation %d : Min %s, Max %s, Avg %s, Cells %d, QD %s" % history[-1])
+    return grid, fit, history
+
+
 def run_stream(env, batches, n_total, slots, max_steps=EPISODE_CAP, chunk=100, on_error="fallback"):
     """run_episode for a population that does not get an arena per creature: ``batches`` ([(Morphology, ids)] per lane bucket, as
     reset_batches takes them) are streamed through ``slots`` slots of ``env`` (BatchedModular2D.reset_stream) -- ``step(chunk)``,
