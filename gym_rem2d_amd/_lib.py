@@ -109,6 +109,9 @@ ELITES_ABI_VERSION = 1      # include/rem2d_elites.h
 ELITES_MAX_WIDTH = 32       # REM2D_ELITES_MAX_WIDTH
 ELITES_MAX_DIMS = 4         # REM2D_ELITES_MAX_DIMS
 ELITES_MAX_CELLS = 65536    # REM2D_ELITES_MAX_CELLS
+SNES_ABI_VERSION = 1        # include/rem2d_snes.h
+SNES_MAX_GROUP = 8192       # REM2D_SNES_MAX_GROUP
+SNES_ADAM, SNES_NATURAL = 1, 2   # REM2D_SNES_ADAM, REM2D_SNES_NATURAL
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -209,6 +212,20 @@ class Elites(C.Structure):
                                              "elite_w1", "elite_b1", "elite_w2", "elite_b2", "count", "cell", "winner", "child_w1",
                                              "child_b1", "child_w2", "child_b2", "parent", "n_filled", "scratch")]
                 + [("scratch_bytes", C.c_uint64), ("reserved", C.c_int32)])
+
+
+SNES_ARRAYS = ("w1", "b1", "w2", "b2")
+
+
+class Snes(C.Structure):
+    """rem2d_snes (include/rem2d_snes.h): device pointers the caller owns."""
+    _fields_ = ([(k, C.c_int32) for k in ("d", "hidden", "max_bodies", "n_means", "group_size", "pair_chunk")]
+                + [("generation", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64)]
+                + [(k, C.c_float) for k in ("mstep", "sstep", "beta1", "omb1", "beta2", "omb2", "alpha", "eps", "sigma_min", "sigma_max")]
+                + [("fitness", C.c_void_p), ("util", C.c_void_p)]
+                + [(pre + k, C.c_void_p) for pre in ("", "sigma_", "m1_", "m2_", "child_", "new_", "new_sigma_", "new_m1_", "new_m2_")
+                   for k in SNES_ARRAYS]
+                + [("scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)])
 
 
 class EpisodeOut(C.Structure):
@@ -474,6 +491,14 @@ def lib(wide=False):
         fn.argtypes = [C.POINTER(Elites), C.c_void_p]
     if L.rem2d_elites_abi_version() != ELITES_ABI_VERSION:
         raise Rem2dError("%s: elites ABI version mismatch" % os.path.basename(path))
+    # an adaptive evolution strategy for device policies (include/rem2d_snes.h)
+    L.rem2d_snes_abi_version.restype = C.c_int
+    L.rem2d_snes_scratch_bytes.restype = C.c_int64
+    L.rem2d_snes_scratch_bytes.argtypes = [C.POINTER(Snes)]
+    for fn in (L.rem2d_snes_sample, L.rem2d_snes_update, L.rem2d_snes_step):
+        fn.argtypes = [C.POINTER(Snes), C.c_void_p]
+    if L.rem2d_snes_abi_version() != SNES_ABI_VERSION:
+        raise Rem2dError("%s: snes ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

@@ -50,6 +50,7 @@
 #include <rem2d_es.h>      // (as rem2d_evolve.h: the quoted name below is the kernels' file)
 #include <rem2d_novelty.h> // (likewise)
 #include <rem2d_elites.h>  // (likewise)
+#include <rem2d_snes.h>    // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -113,6 +114,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_es.h"
 #include "rem2d_novelty.h"
 #include "rem2d_elites.h"
+#include "rem2d_snes.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -2018,6 +2020,163 @@ extern "C" int rem2d_es_step(const rem2d_es *e, void *stream) {
     const int rc = es_ok("es_step", e, ES_SHAPE | ES_UPDATE);
     if (rc != REM2D_OK) return rc;
     return es_launch(e, ES_SHAPE | ES_UPDATE, (hipStream_t)stream);
+}
+
+// ---- an adaptive evolution strategy for device policies (include/rem2d_snes.h, csrc/rem2d_snes.h) ----
+extern "C" int rem2d_snes_abi_version(void) { return REM2D_SNES_ABI_VERSION; }
+enum { SN_SAMPLE = 1, SN_SHAPE = 2, SN_UPDATE = 4 };
+// The shapes of an snes descriptor as an es descriptor: what es_shapes_ok, es_split and es_args read.  No pointer is set.
+static rem2d_es sn_as_es(const rem2d_snes *e) {
+    rem2d_es x;
+    memset(&x, 0, sizeof(x));
+    x.d = e->d; x.hidden = e->hidden; x.max_bodies = e->max_bodies; x.n_means = e->n_means; x.group_size = e->group_size;
+    x.pair_chunk = e->pair_chunk; x.generation = e->generation; x.seed = e->seed;
+    return x;
+}
+// Checks the shapes and parameters of an snes descriptor; `what` prefixes the message.  No pointer is looked at.
+static int sn_shapes_ok(const std::string &s, const rem2d_snes *e) {
+    if (!e) return fail(REM2D_E_INVALID, s + "NULL descriptor");
+    const rem2d_es x = sn_as_es(e);
+    const int rc = es_shapes_ok(s, &x);
+    if (rc != REM2D_OK) return rc;
+    if (e->group_size > REM2D_SNES_MAX_GROUP)
+        return fail(REM2D_E_INVALID, s + "group_size must be at most " + std::to_string(REM2D_SNES_MAX_GROUP) + ", not " + std::to_string(e->group_size));
+    if (e->flags & ~(REM2D_SNES_ADAM | REM2D_SNES_NATURAL)) return fail(REM2D_E_INVALID, s + "unknown bits in flags: " + std::to_string(e->flags));
+    return REM2D_OK;
+}
+static size_t sn_scratch_need(const rem2d_snes *e) {
+    const rem2d_es x = sn_as_es(e);
+    return 2 * es_scratch_need(&x); // two int64 per element per chunk
+}
+struct SnBuf {
+    uintptr_t at;
+    size_t bytes;
+    std::string name;
+};
+// Checks an snes descriptor for the calls in `stages`.  Nothing it points to is read.
+static int sn_ok(const char *what, const rem2d_snes *e, int stages) {
+    const std::string s = std::string(what) + ": ";
+    const int rc = sn_shapes_ok(s, e);
+    if (rc != REM2D_OK) return rc;
+    const bool adam = (e->flags & REM2D_SNES_ADAM) != 0;
+    if ((stages & SN_SHAPE) && !e->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
+    if ((stages & (SN_SHAPE | SN_UPDATE)) && !e->util) return fail(REM2D_E_INVALID, s + "NULL device pointer (util)");
+    const char *const name[4] = {"w1", "b1", "w2", "b2"};
+    const size_t len[4] = {(size_t)e->d * (size_t)e->hidden, (size_t)e->hidden, (size_t)e->hidden * (size_t)e->max_bodies, (size_t)e->max_bodies};
+    const size_t M = (size_t)e->n_means, G = M * (size_t)e->group_size;
+    const float *mean[4] = {e->w1, e->b1, e->w2, e->b2}, *sigma[4] = {e->sigma_w1, e->sigma_b1, e->sigma_w2, e->sigma_b2};
+    const float *m1[4] = {e->m1_w1, e->m1_b1, e->m1_w2, e->m1_b2}, *m2[4] = {e->m2_w1, e->m2_b1, e->m2_w2, e->m2_b2};
+    const float *child[4] = {e->child_w1, e->child_b1, e->child_w2, e->child_b2}, *next[4] = {e->new_w1, e->new_b1, e->new_w2, e->new_b2};
+    const float *nsig[4] = {e->new_sigma_w1, e->new_sigma_b1, e->new_sigma_w2, e->new_sigma_b2};
+    const float *nm1[4] = {e->new_m1_w1, e->new_m1_b1, e->new_m1_w2, e->new_m1_b2}, *nm2[4] = {e->new_m2_w1, e->new_m2_b1, e->new_m2_w2, e->new_m2_b2};
+    std::vector<SnBuf> in, out;
+    auto add = [&](std::vector<SnBuf> &to, const float *const *p, const char *prefix, size_t sets) {
+        for (int k = 0; k < 4; ++k) {
+            if (!p[k]) return false;
+            to.push_back({(uintptr_t)p[k], sets * len[k] * sizeof(float), std::string(prefix) + name[k]});
+        }
+        return true;
+    };
+    bool all = add(in, mean, "the mean's ", M) && add(in, sigma, "sigma_", M);
+    if (stages & SN_SAMPLE) all = all && add(out, child, "child_", G);
+    if (stages & SN_UPDATE) {
+        all = all && add(out, next, "new_", M) && add(out, nsig, "new_sigma_", M);
+        if (adam) all = all && add(in, m1, "m1_", M) && add(in, m2, "m2_", M) && add(out, nm1, "new_m1_", M) && add(out, nm2, "new_m2_", M);
+    }
+    if (!all) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights or state)");
+    size_t need = 0;
+    if (stages & SN_UPDATE) {
+        if (!(e->sigma_min > 0.0f) || !(e->sigma_min <= e->sigma_max) || !std::isfinite(e->sigma_min) || !std::isfinite(e->sigma_max))
+            return fail(REM2D_E_INVALID, s + "sigma_min and sigma_max must be finite with 0 < sigma_min <= sigma_max");
+        in.push_back({(uintptr_t)e->util, G * sizeof(int32_t), "util"});
+        need = sn_scratch_need(e);
+        if (need != 0) {
+            if (!e->scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
+            if ((uintptr_t)e->scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
+            if (e->scratch_bytes < (uint64_t)need)
+                return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(e->scratch_bytes) + " bytes, " + std::to_string(need) + " are needed");
+            out.push_back({(uintptr_t)e->scratch, need, "scratch"});
+        }
+    }
+    if ((stages & SN_SHAPE)) in.push_back({(uintptr_t)e->fitness, G * sizeof(double), "fitness"});
+    for (size_t i = 0; i < out.size(); ++i) {
+        for (size_t j = 0; j < in.size(); ++j)
+            if (out[i].at < in[j].at + in[j].bytes && in[j].at < out[i].at + out[i].bytes)
+                return fail(REM2D_E_INVALID, s + out[i].name + " overlaps " + in[j].name);
+        for (size_t j = 0; j < i; ++j)
+            if (out[i].at < out[j].at + out[j].bytes && out[j].at < out[i].at + out[i].bytes)
+                return fail(REM2D_E_INVALID, s + out[i].name + " overlaps " + out[j].name);
+    }
+    return REM2D_OK;
+}
+static void sn_args(SnArgs &B, const rem2d_snes *e) {
+    memset(&B, 0, sizeof(B));
+    rem2d_es x = sn_as_es(e);
+    x.fitness = e->fitness; x.util = e->util;
+    x.w1 = e->w1; x.b1 = e->b1; x.w2 = e->w2; x.b2 = e->b2;
+    x.child_w1 = e->child_w1; x.child_b1 = e->child_b1; x.child_w2 = e->child_w2; x.child_b2 = e->child_b2;
+    x.new_w1 = e->new_w1; x.new_b1 = e->new_b1; x.new_w2 = e->new_w2; x.new_b2 = e->new_b2;
+    x.scratch = e->scratch;
+    es_args(B.es, &x);
+    B.sigma[0] = e->sigma_w1; B.sigma[1] = e->sigma_b1; B.sigma[2] = e->sigma_w2; B.sigma[3] = e->sigma_b2;
+    B.m1[0] = e->m1_w1; B.m1[1] = e->m1_b1; B.m1[2] = e->m1_w2; B.m1[3] = e->m1_b2;
+    B.m2[0] = e->m2_w1; B.m2[1] = e->m2_b1; B.m2[2] = e->m2_w2; B.m2[3] = e->m2_b2;
+    B.nextSigma[0] = e->new_sigma_w1; B.nextSigma[1] = e->new_sigma_b1; B.nextSigma[2] = e->new_sigma_w2; B.nextSigma[3] = e->new_sigma_b2;
+    B.nextM1[0] = e->new_m1_w1; B.nextM1[1] = e->new_m1_b1; B.nextM1[2] = e->new_m1_w2; B.nextM1[3] = e->new_m1_b2;
+    B.nextM2[0] = e->new_m2_w1; B.nextM2[1] = e->new_m2_b1; B.nextM2[2] = e->new_m2_w2; B.nextM2[3] = e->new_m2_b2;
+    for (int k = 0; k < 4; ++k) B.es.vec[k] = B.es.vec[k] && (uintptr_t)B.sigma[k] % 16 == 0; // the third base of the sample
+    B.flags = e->flags;
+    B.mstep = e->mstep; B.sstep = e->sstep; B.beta1 = e->beta1; B.omb1 = e->omb1; B.beta2 = e->beta2; B.omb2 = e->omb2;
+    B.alpha = e->alpha; B.eps = e->eps; B.sigmaMin = e->sigma_min; B.sigmaMax = e->sigma_max;
+}
+// `items` workgroups of one wavefront of one kernel, ES_MAX_GRID of them per launch, each launch told its first item.
+template <typename K> static int sn_launch_items(K kernel, long long items, SnArgs &B, hipStream_t st) {
+    for (long long base = 0; base < items; base += ES_MAX_GRID) {
+        const long long n = items - base < (long long)ES_MAX_GRID ? items - base : (long long)ES_MAX_GRID;
+        B.es.itemBase = base;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(WAVE), 0, st, B);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+// The stages of a checked descriptor on `st`.
+static int sn_launch(const rem2d_snes *e, int stages, hipStream_t st) {
+    SnArgs B;
+    sn_args(B, e);
+    const EsArgs &A = B.es;
+    const long long G = (long long)A.M * (long long)A.S;
+    int rc = REM2D_OK;
+    if (stages & SN_SAMPLE) rc = sn_launch_items(rem2d_snes_sample_kernel, G / 2, B, st);
+    if (rc == REM2D_OK && (stages & SN_SHAPE)) {
+        B.es.itemBase = 0;
+        hipLaunchKernelGGL(rem2d_es_shape_kernel, dim3((unsigned)((G + ES_TILE - 1) / ES_TILE)), dim3(ES_TILE), 0, st, B.es);
+        HIP_TRY(hipGetLastError());
+    }
+    if (rc == REM2D_OK && (stages & SN_UPDATE)) {
+        rc = sn_launch_items(rem2d_snes_update_kernel, (long long)A.M * (long long)A.nChunks * (long long)A.W, B, st);
+        if (rc == REM2D_OK && A.nChunks > 1) rc = sn_launch_items(rem2d_snes_finish_kernel, (long long)A.M * (long long)A.W, B, st);
+    }
+    return rc;
+}
+extern "C" int64_t rem2d_snes_scratch_bytes(const rem2d_snes *e) {
+    const int rc = sn_shapes_ok("snes_scratch_bytes: ", e);
+    if (rc != REM2D_OK) return rc;
+    return (int64_t)sn_scratch_need(e);
+}
+extern "C" int rem2d_snes_sample(const rem2d_snes *e, void *stream) {
+    const int rc = sn_ok("snes_sample", e, SN_SAMPLE);
+    if (rc != REM2D_OK) return rc;
+    return sn_launch(e, SN_SAMPLE, (hipStream_t)stream);
+}
+extern "C" int rem2d_snes_update(const rem2d_snes *e, void *stream) {
+    const int rc = sn_ok("snes_update", e, SN_UPDATE);
+    if (rc != REM2D_OK) return rc;
+    return sn_launch(e, SN_UPDATE, (hipStream_t)stream);
+}
+extern "C" int rem2d_snes_step(const rem2d_snes *e, void *stream) {
+    const int rc = sn_ok("snes_step", e, SN_SHAPE | SN_UPDATE);
+    if (rc != REM2D_OK) return rc;
+    return sn_launch(e, SN_SHAPE | SN_UPDATE, (hipStream_t)stream);
 }
 
 // ---- behavioural novelty (include/rem2d_novelty.h, csrc/rem2d_novelty.h) ----

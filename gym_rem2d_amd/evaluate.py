@@ -351,6 +351,38 @@ def run_policy_es(env, mean, n_generations, seed=0, sigma=0.1, lr=0.05, group_si
     return mean, fit, history
 
 
+def run_policy_snes(env, es, n_generations, seed=0, max_steps=EPISODE_CAP, chunk=100, on_error="raise", log=None, on_generation=None):
+    """``run_policy_es`` around a ``policy.SeparableES`` (per-parameter sigma, Adam on request; include/rem2d_snes.h): ``es`` holds one
+    mean per block of ``es.group_size`` consecutive creatures of ``env`` (reset first).  Every generation g = 1 .. is ``es.sample``,
+    ``env.set_policy``, ``env.reset_where`` of everyone, ``run_policy_episode(compact=False)`` and ``es.update``.  The strategy's own
+    buffers are reused throughout: after the first generation nothing is allocated.  Returns ``(mean, fitness, history)`` as
+    ``run_policy_es`` does; ``on_generation(gen, children, fitness, mean)`` likewise (``es.sigma``, ``es.t`` and ``es.state()`` are
+    there for a checkpoint hook)."""
+    if not env.worlds:
+        raise ValueError("run_policy_snes: no population in place (reset first)")
+    n, S = env.n_envs, es.group_size
+    if n % S or es.mean.n_sets * S != n:
+        raise ValueError("run_policy_snes: %d creatures are not %d means times the strategy's group_size %d" % (n, es.mean.n_sets, S))
+    dev = env.worlds[0][0].device
+    if es.device != dev:
+        raise ValueError("run_policy_snes: the strategy is on %s, the population on %s" % (es.device, dev))
+    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
+    fit, history = None, []
+    for gen in range(1, int(n_generations) + 1):
+        children = es.sample(gen, seed=seed)
+        env.set_policy(children)
+        env.reset_where(mask=everyone)
+        fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
+        mean = es.update(fit, gen, seed=seed)
+        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
+        history.append((gen,) + tuple(stats))
+        if on_generation:
+            on_generation(gen, children, fit, mean)
+        if log:
+            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+    return es.mean, fit, history
+
+
 def run_behaviour_episode(env, period, samples, max_steps=EPISODE_CAP, on_error="raise"):
     """An episode that records where every creature went: ``env.set_descriptor(period, samples)`` (kept where the env already has
     that descriptor), ``describe()`` once at step 0, then ``period`` steps and ``describe()`` in turn -- ``env.step_policy`` if a

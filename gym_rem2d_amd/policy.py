@@ -391,3 +391,228 @@ class MLPPolicy:
         with torch.cuda.device(dev):
             _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
         return new
+
+
+class SeparableES:
+    """An adaptive evolution strategy around an ``MLPPolicy`` as the mean (include/rem2d_snes.h): the antithetic sampling of
+    ``MLPPolicy.es_sample`` with a step size PER PARAMETER -- a sigma tensor of the mean's shapes, adapted every update from the
+    same utilities (a separable NES) -- and, with ``adam=(beta1, beta2, eps)``, Adam on the mean.  ``mean``: M sets without an
+    ``index`` (copied: the caller's tensors are never written); ``group_size`` = S children per set, even, 2 .. 8192.  ``sigma``:
+    what every sigma word starts from; ``lr``: the mean's rate (``mean += lr / (S sigma) * sum rank z`` without Adam, Adam's step size
+    with it); ``lr_sigma``: sigma's rate (``log sigma += lr_sigma / (2 S) * sum rank (z^2 - 1)``, the exponential in its (1,1) Pade
+    form; 0 keeps sigma fixed); ``natural``: the mean's step is scaled by each element's sigma; ``sigma_bounds``: sigma is clamped to
+    them.  The object owns two sets of the mean, sigma and (with Adam) the moments m1, m2, which ``update`` writes in turn, the
+    update count ``t``, one child policy, one util and one scratch tensor: after the first generation nothing is allocated.
+    Everything runs on the device by library calls whose results are the same bits whatever the launch shape; tests/snes_model.py
+    restates them."""
+
+    def __init__(self, mean, group_size, sigma=0.1, lr=0.05, lr_sigma=4.0, adam=None, natural=False, sigma_bounds=(1e-6, 10.0)):
+        if not isinstance(mean, MLPPolicy):
+            raise ValueError("SeparableES: mean must be an MLPPolicy")
+        if mean.index is not None:
+            raise ValueError("SeparableES: a policy with an index shares weight sets among creatures; the mean is the sets of take() instead")
+        S = None if group_size is None else int(group_size)
+        if S is None or S < 2 or S % 2 or S > _lib.SNES_MAX_GROUP:
+            raise ValueError("SeparableES: group_size (children per mean) must be even and 2..%d, not %r" % (_lib.SNES_MAX_GROUP, group_size))
+        if mean.n_sets * S > 2 ** 31 - 1:
+            raise ValueError("SeparableES: %d means of group_size %d are more than 2^31 - 1 children" % (mean.n_sets, S))
+        if not float(sigma) > 0.0 or not math.isfinite(float(sigma)):
+            raise ValueError("SeparableES: sigma must be positive and finite, not %r" % (sigma,))
+        if not math.isfinite(float(lr)):
+            raise ValueError("SeparableES: lr must be finite, not %r" % (lr,))
+        if not float(lr_sigma) >= 0.0 or not math.isfinite(float(lr_sigma)):
+            raise ValueError("SeparableES: lr_sigma must be finite and at least 0, not %r" % (lr_sigma,))
+        if adam is not None:
+            try:
+                adam = tuple(float(v) for v in adam)
+            except TypeError:
+                adam = ()
+            if len(adam) != 3 or not 0.0 <= adam[0] < 1.0 or not 0.0 <= adam[1] < 1.0 or not adam[2] > 0.0 or not math.isfinite(adam[2]):
+                raise ValueError("SeparableES: adam must be None or (beta1, beta2, eps) with the betas in [0, 1) and eps positive")
+        try:
+            lo, hi = (float(np.float32(v)) for v in sigma_bounds)
+        except (TypeError, ValueError):
+            lo, hi = math.nan, math.nan
+        if not (0.0 < lo <= hi) or not math.isfinite(hi):
+            raise ValueError("SeparableES: sigma_bounds must be finite (min, max) with 0 < min <= max, not %r" % (sigma_bounds,))
+        if not lo <= float(sigma) <= hi:
+            raise ValueError("SeparableES: sigma %r lies outside sigma_bounds %r" % (sigma, sigma_bounds))
+        self.group_size, self.sigma0, self.lr, self.lr_sigma = S, float(sigma), float(lr), float(lr_sigma)
+        self.adam, self.natural, self.sigma_bounds = adam, bool(natural), (lo, hi)
+        self.t = 0
+        own = [t.clone() for t in (mean.w1, mean.b1, mean.w2, mean.b2)]
+        self.mean = mean._like(*own, None)
+        self._spare_mean = mean._like(*(torch.empty_like(t) for t in own), None)
+        self.sigma = [torch.full_like(t, float(sigma)) for t in own]
+        self._spare_sigma = [torch.empty_like(t) for t in own]
+        self.m1 = self.m2 = self._spare_m1 = self._spare_m2 = None
+        if adam is not None:
+            self.m1, self.m2 = [torch.zeros_like(t) for t in own], [torch.zeros_like(t) for t in own]
+            self._spare_m1, self._spare_m2 = [torch.empty_like(t) for t in own], [torch.empty_like(t) for t in own]
+        self._children = self._scratch = self._util = None
+
+    @property
+    def device(self):
+        return self.mean.device
+
+    @property
+    def flags(self):
+        return (_lib.SNES_ADAM if self.adam is not None else 0) | (_lib.SNES_NATURAL if self.natural else 0)
+
+    def scalars(self, t):
+        """The ten binary32 scalars of update number t = 1, 2, ..., each computed in Python floats and rounded once."""
+        S = self.group_size
+        f = lambda v: float(np.float32(v))
+        c = dict(mstep=f(self.lr / (2.0 * (S - 1) * S * self.sigma0)), sstep=f(self.lr_sigma / (4.0 * (S - 1) * S)), beta1=0.0, omb1=0.0,
+                 beta2=0.0, omb2=0.0, alpha=0.0, eps=0.0, sigma_min=self.sigma_bounds[0], sigma_max=self.sigma_bounds[1])
+        if self.adam is not None:
+            b1, b2, eps = self.adam
+            c.update(mstep=f(1.0 / (2.0 * (S - 1) * S)), beta1=f(b1), omb1=f(1.0 - b1), beta2=f(b2), omb2=f(1.0 - b2), eps=f(eps),
+                     alpha=f(self.lr * math.sqrt(1.0 - b2 ** int(t)) / (1.0 - b1 ** int(t))))
+        return c
+
+    def _descriptor(self, what, generation, seed, pair_chunk=0):
+        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("%s: generation must fit 32 bits and seed 64 (unsigned)" % what)
+        if int(pair_chunk) < 0:
+            raise ValueError("%s: pair_chunk must be at least 0, not %r" % (what, pair_chunk))
+        m = self.mean
+        e = _lib.Snes()
+        e.d, e.hidden, e.max_bodies, e.n_means, e.group_size = m.d, m.hidden, m.max_bodies, m.n_sets, self.group_size
+        e.pair_chunk, e.generation, e.flags, e.seed = int(pair_chunk), int(generation), self.flags, int(seed)
+        return e
+
+    @staticmethod
+    def _point(e, prefix, tensors):
+        for k, t in zip(_lib.SNES_ARRAYS, tensors):
+            setattr(e, prefix + k, t.data_ptr())
+
+    def scratch_bytes(self, pair_chunk=0, wide=False):
+        """Bytes of scratch that ``update`` needs (rem2d_snes_scratch_bytes); 0 where the update is one launch."""
+        e = self._descriptor("SeparableES.scratch_bytes", 0, 0, pair_chunk)
+        n = int(_lib.lib(wide).rem2d_snes_scratch_bytes(C.byref(e)))
+        if n < 0:
+            _lib.check(n, wide)
+        return n
+
+    def sample(self, generation, seed=0, out=None, wide=False):
+        """The children of one generation: set ``b S + 2 q`` is ``mean[b] + sigma[b] z`` and set ``b S + 2 q + 1`` is
+        ``mean[b] - sigma[b] z``, element by element (rem2d_snes_sample), on the current stream.  ``out``: a policy of M S sets of the
+        mean's per-set shapes whose weights are overwritten and which is returned; without it the object's own child policy,
+        allocated by the first call and overwritten by every later one."""
+        e = self._descriptor("SeparableES.sample", generation, seed)
+        G = self.mean.n_sets * self.group_size
+        mine = (self.mean.w1, self.mean.b1, self.mean.w2, self.mean.b2)
+        if out is not None:
+            self.mean._es_out("SeparableES.sample", out, G)
+            for a in (out.w1, out.b1, out.w2, out.b2):
+                for b in self.sigma:
+                    if a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
+                        raise ValueError("SeparableES.sample: out shares memory with sigma")
+        if self.device.type != "cuda":
+            raise ValueError("SeparableES.sample: the weights are on %s; build the strategy around a mean on the GPU" % self.device)
+        if out is None:
+            if self._children is None:
+                self._children = self.mean._like(*(torch.empty((G,) + tuple(t.shape[1:]), dtype=torch.float32, device=self.device) for t in mine), None)
+            child = self._children
+        else:
+            child = out
+            child.activation, child.scale, child.rays = self.mean.activation, self.mean.scale, self.mean.rays
+        self._point(e, "", mine)
+        self._point(e, "sigma_", self.sigma)
+        self._point(e, "child_", (child.w1, child.b1, child.w2, child.b2))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib(wide).rem2d_snes_sample(C.byref(e), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), wide)
+        return child
+
+    def update(self, fitness, generation, seed=0, util=None, scratch=None, pair_chunk=0, wide=False):
+        """One update from the children's ``fitness`` -- float64 ``[M S]`` on the device, in the order of ``sample`` -- ranked within
+        each block (rem2d_snes_step), or from the caller's ``util`` (int32 ``[M S]`` on the device; ``fitness`` is not looked at:
+        rem2d_snes_update).  ``generation``, ``seed``: what ``sample`` was given -- the draws are regenerated, not read.  The new mean,
+        sigma and moments go to the object's spare buffers, which then become the current ones; ``t`` counts the update.
+        ``scratch``: a contiguous int64 tensor of at least ``scratch_bytes(pair_chunk) / 8`` entries; without it the object's own.
+        ``pair_chunk``: pairs per wavefront, 0 for the library's choice; no result depends on it.
+
+        Returns the new mean ``MLPPolicy`` (``self.mean``) with ``.util``, int32 ``[M S]``."""
+        dev = self.device
+        e = self._descriptor("SeparableES.update", generation, seed, pair_chunk)
+        G = self.mean.n_sets * self.group_size
+        if util is None:
+            if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
+                raise ValueError("SeparableES.update: fitness must be a torch.float64 tensor")
+            if tuple(fitness.shape) != (G,) or not fitness.is_contiguous():
+                raise ValueError("SeparableES.update: fitness must be a contiguous tensor of one entry per child [%d], not %s" % (G, list(fitness.shape)))
+            if fitness.device != dev:
+                raise ValueError("SeparableES.update: fitness must be on %s, not %s" % (dev, fitness.device))
+        elif (not isinstance(util, torch.Tensor) or util.dtype != torch.int32 or tuple(util.shape) != (G,) or not util.is_contiguous()
+              or util.device != dev):
+            raise ValueError("SeparableES.update: util must be a contiguous torch.int32 [%d] tensor on %s" % (G, dev))
+        need = self.scratch_bytes(pair_chunk, wide)
+        if scratch is not None and (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.int64 or not scratch.is_contiguous()
+                                    or scratch.device != dev or scratch.numel() * 8 < need):
+            raise ValueError("SeparableES.update: scratch must be a contiguous torch.int64 tensor of at least %d entries on %s" % (need // 8, dev))
+        if dev.type != "cuda":
+            raise ValueError("SeparableES.update: the weights are on %s; build the strategy around a mean on the GPU" % dev)
+        new = self._spare_mean
+        if util is not None:
+            new.util = util
+        else:                       # (one util per set of buffers, both made by the first call)
+            if self._util is None:
+                self._util = [torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2)]
+            new.util = self._util[self.t % 2]
+        if scratch is None and need:
+            if self._scratch is None or self._scratch.numel() * 8 < need:
+                self._scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
+            scratch = self._scratch
+        for k, v in self.scalars(self.t + 1).items():
+            setattr(e, k, v)
+        e.fitness = None if util is not None else fitness.data_ptr()
+        e.util = new.util.data_ptr()
+        self._point(e, "", (self.mean.w1, self.mean.b1, self.mean.w2, self.mean.b2))
+        self._point(e, "sigma_", self.sigma)
+        self._point(e, "new_", (new.w1, new.b1, new.w2, new.b2))
+        self._point(e, "new_sigma_", self._spare_sigma)
+        if self.adam is not None:
+            self._point(e, "m1_", self.m1)
+            self._point(e, "m2_", self.m2)
+            self._point(e, "new_m1_", self._spare_m1)
+            self._point(e, "new_m2_", self._spare_m2)
+        e.scratch, e.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel() * 8)
+        L = _lib.lib(wide)
+        call = L.rem2d_snes_step if util is None else L.rem2d_snes_update
+        with torch.cuda.device(dev):
+            _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
+        self.mean, self._spare_mean = new, self.mean
+        self.sigma, self._spare_sigma = self._spare_sigma, self.sigma
+        self.m1, self._spare_m1 = self._spare_m1, self.m1
+        self.m2, self._spare_m2 = self._spare_m2, self.m2
+        self.t += 1
+        return self.mean
+
+    # ---- checkpoints ----
+    def state(self):
+        """A plain dict for a checkpoint: ``mean``, ``sigma`` and, with Adam, ``m1`` and ``m2`` -- lists of four CPU tensors (w1, b1, w2,
+        b2) -- and the update count ``t``."""
+        cpu = lambda ts: [t.detach().cpu().clone() for t in ts]
+        s = {"mean": cpu((self.mean.w1, self.mean.b1, self.mean.w2, self.mean.b2)), "sigma": cpu(self.sigma), "t": int(self.t)}
+        if self.adam is not None:
+            s["m1"], s["m2"] = cpu(self.m1), cpu(self.m2)
+        return s
+
+    def load_state(self, state):
+        """Continue from ``state()``'s dict: the tensors are copied into the object's current buffers (same shapes), ``t`` is set."""
+        names = ("mean", "sigma") + (("m1", "m2") if self.adam is not None else ())
+        mine = {"mean": (self.mean.w1, self.mean.b1, self.mean.w2, self.mean.b2), "sigma": self.sigma, "m1": self.m1, "m2": self.m2}
+        if not isinstance(state, dict) or any(k not in state for k in names + ("t",)):
+            raise ValueError("SeparableES.load_state: state must be a dict with %s and t" % ", ".join(names))
+        if isinstance(state["t"], bool) or not isinstance(state["t"], int) or state["t"] < 0:
+            raise ValueError("SeparableES.load_state: t must be an integer of at least 0, not %r" % (state["t"],))
+        for k in names:
+            got = state[k]
+            if (not isinstance(got, (list, tuple)) or len(got) != 4 or any(not isinstance(a, torch.Tensor) or a.dtype != torch.float32
+                                                                          or a.shape != b.shape for a, b in zip(got, mine[k]))):
+                raise ValueError("SeparableES.load_state: %s must be four float32 tensors of the mean's shapes" % k)
+        for k in names:
+            for a, b in zip(state[k], mine[k]):
+                b.copy_(a)
+        self.t = state["t"]
