@@ -112,6 +112,11 @@ ELITES_MAX_CELLS = 65536    # REM2D_ELITES_MAX_CELLS
 SNES_ABI_VERSION = 1        # include/rem2d_snes.h
 SNES_MAX_GROUP = 8192       # REM2D_SNES_MAX_GROUP
 SNES_ADAM, SNES_NATURAL = 1, 2   # REM2D_SNES_ADAM, REM2D_SNES_NATURAL
+PARETO_ABI_VERSION = 1      # include/rem2d_pareto.h
+PARETO_MAX_OBJ = 4          # REM2D_PARETO_MAX_OBJ
+PARETO_MAX_GROUP = 1024     # REM2D_PARETO_MAX_GROUP
+PARETO_MAX_WIDTH = 32       # REM2D_PARETO_MAX_WIDTH
+PARETO_MAX_K = 32           # REM2D_PARETO_MAX_K
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -226,6 +231,12 @@ class Snes(C.Structure):
                 + [(pre + k, C.c_void_p) for pre in ("", "sigma_", "m1_", "m2_", "child_", "new_", "new_sigma_", "new_m1_", "new_m2_")
                    for k in SNES_ARRAYS]
                 + [("scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)])
+
+
+class Pareto(C.Structure):
+    """rem2d_pareto (include/rem2d_pareto.h): device pointers the caller owns."""
+    _fields_ = ([(k, C.c_int32) for k in ("n_rows", "group_size", "n_obj", "width", "k", "reserved")]
+                + [(k, C.c_void_p) for k in ("obj", "front", "crowd", "util", "n_fronts", "desc", "fitness", "local", "neighbours")])
 
 
 class EpisodeOut(C.Structure):
@@ -499,6 +510,12 @@ def lib(wide=False):
         fn.argtypes = [C.POINTER(Snes), C.c_void_p]
     if L.rem2d_snes_abi_version() != SNES_ABI_VERSION:
         raise Rem2dError("%s: snes ABI version mismatch" % os.path.basename(path))
+    # Pareto ranking (include/rem2d_pareto.h)
+    L.rem2d_pareto_abi_version.restype = C.c_int
+    for fn in (L.rem2d_pareto_rank, L.rem2d_pareto_local):
+        fn.argtypes = [C.POINTER(Pareto), C.c_void_p]
+    if L.rem2d_pareto_abi_version() != PARETO_ABI_VERSION:
+        raise Rem2dError("%s: pareto ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

@@ -51,6 +51,7 @@
 #include <rem2d_novelty.h> // (likewise)
 #include <rem2d_elites.h>  // (likewise)
 #include <rem2d_snes.h>    // (likewise)
+#include <rem2d_pareto.h>  // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -115,6 +116,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_novelty.h"
 #include "rem2d_elites.h"
 #include "rem2d_snes.h"
+#include "rem2d_pareto.h"
 
 // =====================================================================================
 // host side: handle + C ABI
@@ -2469,6 +2471,92 @@ extern "C" int rem2d_elites_emit(const rem2d_elites *e, void *stream) {
     const int rc = el_ok("elites_emit", e, EL_SAMPLE | EL_VARY);
     if (rc != REM2D_OK) return rc;
     return el_launch(e, EL_SAMPLE | EL_VARY, (hipStream_t)stream);
+}
+
+// ---- Pareto ranking (include/rem2d_pareto.h, csrc/rem2d_pareto.h) ----
+extern "C" int rem2d_pareto_abi_version(void) { return REM2D_PARETO_ABI_VERSION; }
+static_assert(REM2D_PARETO_MAX_GROUP == PA_LONG, "a block of the rank fits one workgroup");
+static_assert(REM2D_PARETO_MAX_WIDTH == REM2D_NOVELTY_MAX_WIDTH && REM2D_PARETO_MAX_K <= 32, "the local kernel's register bounds and its 32-bit mask");
+// does [p, p + bytes) meet [q, q + qbytes)?
+static bool pa_meet(const void *p, size_t bytes, const void *q, size_t qbytes) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)bytes;
+}
+// The members both calls share.  Nothing the descriptor points to is read.
+static int pa_ok(const std::string &s, const rem2d_pareto *p, int max_group) {
+    if (!p) return fail(REM2D_E_INVALID, s + "NULL descriptor");
+    if (p->n_rows < 1) return fail(REM2D_E_INVALID, s + "n_rows must be at least 1, not " + std::to_string(p->n_rows));
+    if (p->group_size < 1 || (max_group && p->group_size > max_group) || p->n_rows % p->group_size != 0)
+        return fail(REM2D_E_INVALID, s + "group_size must be " + (max_group ? "1.." + std::to_string(max_group) : std::string("at least 1")) +
+                                         " and divide n_rows (" + std::to_string(p->n_rows) + "), not " + std::to_string(p->group_size));
+    return REM2D_OK;
+}
+template <int T> static void pa_launch_rank(const PaArgs &A, int K, dim3 grid, hipStream_t st) {
+    if (K == 1) hipLaunchKernelGGL((rem2d_pareto_rank_kernel<1, T>), grid, dim3(T), 0, st, A);
+    else if (K == 2) hipLaunchKernelGGL((rem2d_pareto_rank_kernel<2, T>), grid, dim3(T), 0, st, A);
+    else if (K == 3) hipLaunchKernelGGL((rem2d_pareto_rank_kernel<3, T>), grid, dim3(T), 0, st, A);
+    else hipLaunchKernelGGL((rem2d_pareto_rank_kernel<4, T>), grid, dim3(T), 0, st, A);
+}
+extern "C" int rem2d_pareto_rank(const rem2d_pareto *p, void *stream) {
+    const std::string s = "pareto_rank: ";
+    const int rc = pa_ok(s, p, REM2D_PARETO_MAX_GROUP);
+    if (rc != REM2D_OK) return rc;
+    if (p->n_obj < 1 || p->n_obj > REM2D_PARETO_MAX_OBJ)
+        return fail(REM2D_E_INVALID, s + "n_obj must be 1.." + std::to_string(REM2D_PARETO_MAX_OBJ) + ", not " + std::to_string(p->n_obj));
+    if (p->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0");
+    if (!p->obj) return fail(REM2D_E_INVALID, s + "NULL device pointer (obj)");
+    const size_t G = (size_t)p->n_rows, M = G / (size_t)p->group_size, in = G * (size_t)p->n_obj * sizeof(double);
+    if (p->front && pa_meet(p->front, G * sizeof(int32_t), p->obj, in)) return fail(REM2D_E_INVALID, s + "front overlaps obj");
+    if (p->crowd && pa_meet(p->crowd, G * sizeof(double), p->obj, in)) return fail(REM2D_E_INVALID, s + "crowd overlaps obj");
+    if (p->util && pa_meet(p->util, G * sizeof(int32_t), p->obj, in)) return fail(REM2D_E_INVALID, s + "util overlaps obj");
+    if (p->n_fronts && pa_meet(p->n_fronts, M * sizeof(int32_t), p->obj, in)) return fail(REM2D_E_INVALID, s + "n_fronts overlaps obj");
+    PaArgs A;
+    memset(&A, 0, sizeof(A));
+    A.obj = p->obj; A.front = p->front; A.crowd = p->crowd; A.util = p->util; A.nfronts = p->n_fronts;
+    A.G = p->n_rows; A.S = p->group_size;
+    const long long T = A.S <= PA_SHORT ? PA_SHORT : PA_LONG, P = T / A.S; // whole blocks per workgroup
+    const dim3 grid((unsigned)(((long long)M + P - 1) / P));
+    if (T == PA_SHORT) pa_launch_rank<PA_SHORT>(A, p->n_obj, grid, (hipStream_t)stream);
+    else pa_launch_rank<PA_LONG>(A, p->n_obj, grid, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
+}
+template <int BP> static void pa_launch_local(const PaArgs &A, dim3 grid, hipStream_t st) {
+    if (A.k <= 2) hipLaunchKernelGGL((rem2d_pareto_local_kernel<BP, 2>), grid, dim3(NV_TILE), 0, st, A);
+    else if (A.k <= 8) hipLaunchKernelGGL((rem2d_pareto_local_kernel<BP, 8>), grid, dim3(NV_TILE), 0, st, A);
+    else if (A.k <= 16) hipLaunchKernelGGL((rem2d_pareto_local_kernel<BP, 16>), grid, dim3(NV_TILE), 0, st, A);
+    else hipLaunchKernelGGL((rem2d_pareto_local_kernel<BP, 32>), grid, dim3(NV_TILE), 0, st, A);
+}
+extern "C" int rem2d_pareto_local(const rem2d_pareto *p, void *stream) {
+    const std::string s = "pareto_local: ";
+    const int rc = pa_ok(s, p, 0);
+    if (rc != REM2D_OK) return rc;
+    if (p->width < 1 || p->width > REM2D_PARETO_MAX_WIDTH)
+        return fail(REM2D_E_INVALID, s + "width must be 1.." + std::to_string(REM2D_PARETO_MAX_WIDTH) + ", not " + std::to_string(p->width));
+    if (p->k < 1 || p->k > REM2D_PARETO_MAX_K)
+        return fail(REM2D_E_INVALID, s + "k must be 1.." + std::to_string(REM2D_PARETO_MAX_K) + ", not " + std::to_string(p->k));
+    if (p->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0");
+    if (!p->desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (desc)");
+    if (!p->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
+    if (!p->local) return fail(REM2D_E_INVALID, s + "NULL device pointer (local)");
+    const size_t G = (size_t)p->n_rows, dn = G * (size_t)p->width * sizeof(float), fn = G * sizeof(double);
+    if (pa_meet(p->local, G * sizeof(double), p->desc, dn)) return fail(REM2D_E_INVALID, s + "local overlaps desc");
+    if (pa_meet(p->local, G * sizeof(double), p->fitness, fn)) return fail(REM2D_E_INVALID, s + "local overlaps fitness");
+    if (p->neighbours && pa_meet(p->neighbours, G * sizeof(int32_t), p->desc, dn)) return fail(REM2D_E_INVALID, s + "neighbours overlaps desc");
+    if (p->neighbours && pa_meet(p->neighbours, G * sizeof(int32_t), p->fitness, fn)) return fail(REM2D_E_INVALID, s + "neighbours overlaps fitness");
+    PaArgs A;
+    memset(&A, 0, sizeof(A));
+    A.desc = p->desc; A.fitness = p->fitness; A.local = p->local; A.neigh = p->neighbours;
+    A.G = p->n_rows; A.S = p->group_size; A.B = p->width; A.k = p->k;
+    const dim3 grid((unsigned)(((long long)A.G + NV_TILE - 1) / NV_TILE));
+    const hipStream_t st = (hipStream_t)stream;
+    if (A.B <= 2) pa_launch_local<2>(A, grid, st);
+    else if (A.B <= 4) pa_launch_local<4>(A, grid, st);
+    else if (A.B <= 8) pa_launch_local<8>(A, grid, st);
+    else if (A.B <= 16) pa_launch_local<16>(A, grid, st);
+    else pa_launch_local<32>(A, grid, st);
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

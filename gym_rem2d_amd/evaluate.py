@@ -486,6 +486,122 @@ def run_policy_nses(env, mean, n_generations, archive, k=15, rate=0.02, weights=
     return mean, fit, history
 
 
+def _pareto_loop_checks(what, env, n_sets, group_size, even, archive, samples, max_steps, period, on_error):
+    """What run_policy_pareto_es and run_policy_nslc refuse, before anything is allocated -> (n, S, samples, period, device)"""
+    if on_error not in ("raise", "warn", "ignore"):
+        raise ValueError("on_error must be 'raise', 'warn' or 'ignore', not %r" % (on_error,))
+    if not env.worlds:
+        raise ValueError("%s: no population in place (reset first)" % what)
+    if env._autoreset is not None or env._stream_rec is not None:
+        raise ValueError("%s: descriptors are not recorded under auto-reset or streaming" % what)
+    n = env.n_envs
+    S = n if group_size is None else int(group_size)
+    if S < 1 or n % S or S > _lib.PARETO_MAX_GROUP or (even and (S < 2 or S % 2)) or n_sets * (S if even else 1) != n:
+        raise ValueError("%s: %d creatures and %d weight sets are not blocks of %s group_size of at most %d (%r)"
+                         % (what, n, n_sets, "an even" if even else "one", _lib.PARETO_MAX_GROUP, group_size))
+    samples = int(samples)
+    period = -(-int(max_steps) // samples) if period is None else int(period)
+    if archive.n_blocks != n // S or archive.width != 2 * samples:
+        raise ValueError("%s: the archive must have %d blocks of width %d, not %d of %d"
+                         % (what, n // S, 2 * samples, archive.n_blocks, archive.width))
+    dev = env.worlds[0][0].device
+    if archive.device != dev:
+        raise ValueError("%s: the archive must be on %s, not %s" % (what, dev, archive.device))
+    return n, S, samples, period, dev
+
+
+def run_policy_pareto_es(env, mean, n_generations, archive, k=15, rate=0.02, period=None, samples=4, seed=0, sigma=0.1, lr=0.05,
+                         group_size=None, max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None):
+    """run_policy_nses with a Pareto ranking in place of the weighted sum of ranks: every generation is ``mean.es_sample``,
+    ``env.set_policy``, ``env.reset_where`` of everyone, ``run_behaviour_episode``, ``archive.step`` (the novelty of every child,
+    then a share ``rate`` of them joins the archive) and ``es_update(util = pareto.rank(stack(fitness, novelty)).util)``: within
+    each block the children are ordered by non-dominated front, then by crowding (include/rem2d_pareto.h), so a child that is the
+    most novel of its block counts as much as the fittest one, whatever the other objective says -- which no weights of
+    run_policy_nses give.  group_size is at most 1024.  One child policy, two sets of mean buffers and one each of novelty,
+    objective, rank and scratch tensors are reused throughout: nothing is allocated after the first generation; ``mean`` itself is
+    never written.  Returns ``(mean, fitness, history)`` as run_policy_es.  ``on_generation(gen, children, fitness, mean,
+    behaviour, novelty, util)``, if given, is called after every update with the tensors themselves and the NEW mean (clone what
+    must last).  Like ``describe`` it raises under auto-reset or streaming."""
+    from . import pareto
+    n, S, samples, period, dev = _pareto_loop_checks("run_policy_pareto_es", env, mean.n_sets, group_size, True, archive, samples,
+                                                     max_steps, period, on_error)
+    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
+    mean = mean.to(dev)
+    children, scratch, fit, history = None, None, None, []
+    need = mean.es_scratch_bytes(S)
+    if need:
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    # (the two sets of mean buffers, written in turn: the first mean's buffers are the caller's and never written)
+    turn = [mean._like(*(torch.empty_like(t) for t in (mean.w1, mean.b1, mean.w2, mean.b2)), None) for _ in range(2)]
+    nov = torch.empty(n, dtype=torch.float64, device=dev)
+    obj = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    ranks = (None, None, torch.empty(n, dtype=torch.int32, device=dev), None)
+    for gen in range(1, int(n_generations) + 1):
+        children = mean.es_sample(gen, seed=seed, sigma=sigma, group_size=S, out=children)
+        env.set_policy(children)
+        env.reset_where(mask=everyone)
+        fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+        archive.step(behaviour, gen, k=k, seed=seed, rate=rate, group_size=S, out=nov)
+        obj[:, 0].copy_(fit)
+        obj[:, 1].copy_(nov)
+        util = pareto.rank(obj, group_size=S, out=ranks).util
+        mean = mean.es_update(None, gen, seed=seed, sigma=sigma, lr=lr, group_size=S, out=turn[gen & 1], scratch=scratch, util=util)
+        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
+        history.append((gen,) + tuple(stats))
+        if on_generation:
+            on_generation(gen, children, fit, mean, behaviour, nov, util)
+        if log:
+            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+    return mean, fit, history
+
+
+def run_policy_nslc(env, policy, n_generations, archive, k=15, rate=0.02, period=None, samples=4, seed=0, mut_rate=0.05, sigma=0.1,
+                    tournsize=4, group_size=None, elite=0, max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None):
+    """Novelty search with local competition (Lehman and Stanley) for device policies: run_policy_generations' loop on
+    ``run_behaviour_episode``, selecting by a Pareto ranking of two objectives -- the novelty of a creature's behaviour
+    (``archive.step``: k nearest neighbours among its block's peers and archive; a share ``rate`` then joins the archive) and its
+    local competition (``pareto.local_competition``: how many of its k nearest peers it out-walks).  Generation 0's episode runs
+    first; every generation g = 1 .. is ``policy.evolve(fitness = util as float64, g, rate=mut_rate, ...)`` with ``util`` the rank
+    utility of the generation before (include/rem2d_pareto.h), ``env.set_policy``, ``env.reset_where`` of everyone and the
+    episode.  group_size (default: everyone) is at most 1024.  Two sets of weight buffers and one each of novelty, local, objective
+    and rank tensors are reused; ``policy`` itself is never written.  Returns ``(policy, fitness, history)`` as
+    run_policy_generations.  ``on_generation(gen, policy, fitness, behaviour, novelty, local, util)``, if given, is called after
+    every episode, generation 0's included, with the tensors themselves (clone what must last).  Like ``describe`` it raises under
+    auto-reset or streaming."""
+    from . import pareto
+    n, S, samples, period, dev = _pareto_loop_checks("run_policy_nslc", env, policy.n_sets, group_size, False, archive, samples,
+                                                     max_steps, period, on_error)
+    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
+    nov, loc = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2))
+    obj = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    sel = torch.empty(n, dtype=torch.float64, device=dev)
+    ranks = (None, None, torch.empty(n, dtype=torch.int32, device=dev), None)
+    spare, history, fit = None, [], None
+    env.set_policy(policy)
+    policy = env.policy
+    for gen in range(0, int(n_generations) + 1):
+        if gen:
+            child = policy.evolve(sel, gen, seed=seed, rate=mut_rate, sigma=sigma, tournsize=tournsize, group_size=S, elite=elite, out=spare)
+            spare, policy = (policy if gen > 1 else None), child    # (generation 0's buffers are the caller's: never written)
+            env.set_policy(policy)
+            env.reset_where(mask=everyone)
+        fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+        archive.step(behaviour, gen, k=k, seed=seed, rate=rate, group_size=S, out=nov)
+        pareto.local_competition(behaviour, fit, k=k, group_size=S, out=loc)
+        obj[:, 0].copy_(nov)
+        obj[:, 1].copy_(loc)
+        util = pareto.rank(obj, group_size=S, out=ranks).util
+        sel.copy_(util)
+        if gen:
+            stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
+            history.append((gen,) + tuple(stats))
+        if on_generation:
+            on_generation(gen, policy, fit, behaviour, nov, loc, util)
+        if log and gen:
+            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+    return policy, fit, history
+
+
 def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples=4, seed=0, rate=0.05, sigma=0.1, group_size=None,
                           max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None):
     """MAP-Elites for device policies: ``grid`` (an ``elites.EliteGrid`` of M = n_envs / ``group_size`` blocks over descriptor rows
