@@ -117,6 +117,8 @@ PARETO_MAX_OBJ = 4          # REM2D_PARETO_MAX_OBJ
 PARETO_MAX_GROUP = 1024     # REM2D_PARETO_MAX_GROUP
 PARETO_MAX_WIDTH = 32       # REM2D_PARETO_MAX_WIDTH
 PARETO_MAX_K = 32           # REM2D_PARETO_MAX_K
+RECURRENT_ABI_VERSION = 1   # include/rem2d_recurrent.h
+RECURRENT_MAX_INPUTS = SENSE_MAX_RAYS   # n_rays + context: what a feed-forward set may have as ray inputs
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -180,6 +182,11 @@ class Policy(C.Structure):
                 + [(k, C.c_int32) for k in ("n_sets", "reserved")]
                 + [(k, C.c_void_p) for k in ("w1", "b1", "w2", "b2", "index", "row_mask", "obs", "frac", "targets", "valid")]
                 + [("n_rows", C.c_int64)])
+
+
+class Recurrent(C.Structure):
+    """rem2d_recurrent (include/rem2d_recurrent.h): a rem2d_policy, the context width and the device memory the caller owns."""
+    _fields_ = [("p", Policy), ("context", C.c_int32), ("reserved", C.c_int32), ("memory", C.c_void_p), ("reset", C.c_void_p)]
 
 
 class Evolve(C.Structure):
@@ -516,6 +523,12 @@ def lib(wide=False):
         fn.argtypes = [C.POINTER(Pareto), C.c_void_p]
     if L.rem2d_pareto_abi_version() != PARETO_ABI_VERSION:
         raise Rem2dError("%s: pareto ABI version mismatch" % os.path.basename(path))
+    # recurrent device policies (include/rem2d_recurrent.h)
+    L.rem2d_recurrent_abi_version.restype = C.c_int
+    L.rem2d_recurrent_forward.argtypes = [C.POINTER(Recurrent), C.c_void_p]
+    L.rem2d_worlds_act_recurrent.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Recurrent), C.c_void_p, C.c_void_p]
+    if L.rem2d_recurrent_abi_version() != RECURRENT_ABI_VERSION:
+        raise Rem2dError("%s: recurrent ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

@@ -52,6 +52,7 @@
 #include <rem2d_elites.h>  // (likewise)
 #include <rem2d_snes.h>    // (likewise)
 #include <rem2d_pareto.h>  // (likewise)
+#include <rem2d_recurrent.h> // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -109,6 +110,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_control.h"
 #include "rem2d_sense.h"
 #include "rem2d_policy.h"
+#include "rem2d_recurrent.h"
 #include "rem2d_episode.h"
 #include "rem2d_stream.h"
 #include "rem2d_evolve.h"
@@ -1638,6 +1640,89 @@ extern "C" int rem2d_worlds_act(rem2d_world *const *worlds, int32_t n_worlds, co
         if (rc != REM2D_OK) return rc;
     }
     rc = policy_launch(p, (hipStream_t)stream);
+    if (rc != REM2D_OK) return rc;
+    return rem2d_worlds_control(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, stream);
+}
+
+// ---- recurrent device policies (include/rem2d_recurrent.h, csrc/rem2d_recurrent.h) ----
+extern "C" int rem2d_recurrent_abi_version(void) { return REM2D_RECURRENT_ABI_VERSION; }
+// Checks a recurrent descriptor; `what` prefixes the message.  Nothing it points to is read.  policy_ok checks everything of q->p
+// but d, whose rule here counts the context words.
+static int recurrent_ok(const char *what, const rem2d_recurrent *q) {
+    const std::string s = std::string(what) + ": ";
+    if (!q) return fail(REM2D_E_INVALID, s + "NULL recurrent policy");
+    rem2d_policy c = q->p;
+    c.d = REM2D_OBS_HEAD + REM2D_OBS_BODY * c.max_bodies + c.n_rays; // (what policy_ok wants of a feed-forward set: checked below instead)
+    const int rc = policy_ok(what, &c);
+    if (rc != REM2D_OK) return rc;
+    if (q->context < 1 || q->context > q->p.hidden)
+        return fail(REM2D_E_INVALID, s + "context must be 1..hidden (" + std::to_string(q->p.hidden) + "), not " + std::to_string(q->context));
+    if (q->p.n_rays + q->context > REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, s + "n_rays + context must be at most " + std::to_string(REM2D_SENSE_MAX_RAYS) + ", not " +
+                                         std::to_string(q->p.n_rays) + " + " + std::to_string(q->context));
+    if (q->p.d != c.d + q->context)
+        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + n_rays + context = " + std::to_string(c.d + q->context) + ", not " +
+                                         std::to_string(q->p.d));
+    if (q->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0, not " + std::to_string(q->reserved));
+    if (!q->memory) return fail(REM2D_E_INVALID, s + "NULL device pointer (memory)");
+    return REM2D_OK;
+}
+// The recurrent forward pass of a checked descriptor on `st`: policy_launch's launch shape.
+static int recurrent_launch(const rem2d_recurrent *q, hipStream_t st) {
+    const rem2d_policy *p = &q->p;
+    if (p->n_rows == 0) return REM2D_OK;
+    RecurrentArgs Q;
+    memset(&Q, 0, sizeof(Q));
+    PolicyArgs &A = Q.P;
+    A.w1 = p->w1; A.b1 = p->b1; A.w2 = p->w2; A.b2 = p->b2;
+    A.index = p->index; A.rowMask = p->row_mask;
+    A.obs = p->obs; A.frac = p->frac; A.targets = p->targets; A.valid = p->valid;
+    A.nRows = p->n_rows;
+    A.D = p->d; A.MB = p->max_bodies; A.R = p->n_rays; A.H = p->hidden; A.G = p->n_sets; A.act = p->activation;
+    A.scale = p->scale;
+    Q.memory = q->memory; Q.reset = q->reset; Q.K = q->context;
+    const bool v1 = p->hidden % 4 == 0 && (uintptr_t)p->w1 % 16 == 0;
+    const bool v2 = p->max_bodies % 4 == 0 && (uintptr_t)p->w2 % 16 == 0;
+    const unsigned need = std::max((unsigned)(p->hidden + (v1 ? 3 : 0)) / (v1 ? 4u : 1u), (unsigned)(p->max_bodies + (v2 ? 3 : 0)) / (v2 ? 4u : 1u));
+    const unsigned lpr = std::min((unsigned)WAVE, std::max((unsigned)POL_MIN_LPR, pow2_at_least(need)));
+    A.lpr = (int)lpr;
+    const unsigned rpw = WAVE / lpr;
+    const long long blocks = (p->n_rows + rpw - 1) / rpw;
+    if (blocks > 0x7fffffffLL) return fail(REM2D_E_INVALID, "recurrent: too many rows for one launch");
+    const size_t lds = (size_t)rpw * (size_t)(p->d + p->hidden) * sizeof(float);
+    void (*kernel)(RecurrentArgs) = v1 ? (v2 ? rem2d_recurrent_forward_kernel<4, 4> : rem2d_recurrent_forward_kernel<4, 1>)
+                                       : (v2 ? rem2d_recurrent_forward_kernel<1, 4> : rem2d_recurrent_forward_kernel<1, 1>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, Q);
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
+}
+extern "C" int rem2d_recurrent_forward(const rem2d_recurrent *q, void *stream) {
+    const int rc = recurrent_ok("recurrent", q);
+    if (rc != REM2D_OK) return rc;
+    return recurrent_launch(q, (hipStream_t)stream);
+}
+extern "C" int rem2d_worlds_act_recurrent(rem2d_world *const *worlds, int32_t n_worlds, const rem2d_recurrent *q,
+                                          const double *ray_offsets_dev, void *stream) {
+    // (rem2d_worlds_act's order: arguments first, worlds after, everything before the first launch)
+    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "act_recurrent: no worlds");
+    int rc = recurrent_ok("act_recurrent", q);
+    if (rc != REM2D_OK) return rc;
+    const rem2d_policy *p = &q->p;
+    if (p->n_rays > 0 && !ray_offsets_dev) return fail(REM2D_E_INVALID, "act_recurrent: NULL device pointer (ray offsets)");
+    for (int32_t i = 0; i < n_worlds; ++i)
+        if (!worlds[i]) return fail(REM2D_E_INVALID, "act_recurrent: world " + std::to_string(i) + " is NULL");
+    rc = control_worlds_ok("act_recurrent", worlds, n_worlds, p->max_bodies, p->n_rows, p->obs);
+    if (rc != REM2D_OK) return rc;
+    if (p->n_rays > 0)
+        for (int32_t i = 0; i < n_worlds; ++i)
+            if (!worlds[i]->haveTerrain) return fail(REM2D_E_STATE, "act_recurrent: rem2d_world_set_terrain must be called first");
+    rc = rem2d_worlds_observe(worlds, n_worlds, p->max_bodies, const_cast<float *>(p->obs), p->n_rows, stream);
+    if (rc != REM2D_OK) return rc;
+    if (p->n_rays > 0) {
+        rc = rem2d_worlds_sense(worlds, n_worlds, ray_offsets_dev, p->n_rays, const_cast<float *>(p->frac), nullptr, p->n_rows, stream);
+        if (rc != REM2D_OK) return rc;
+    }
+    rc = recurrent_launch(q, (hipStream_t)stream);
     if (rc != REM2D_OK) return rc;
     return rem2d_worlds_control(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, stream);
 }

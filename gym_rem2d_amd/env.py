@@ -185,6 +185,7 @@ class BatchedModular2D:
         self.robots = None
         self._reward = self._done = None
         self._policy = self._act_args = None   # set_policy()
+        self._context_reset = False            # reset_where() since the last act(): whom it restarted reads zero context (RecurrentPolicy)
         self._episodes = self._episode_args = self._autoreset = None   # episodes / reset_where() / set_autoreset()
         self._stream_rec = self._refill_args = None                    # reset_stream() / refill() / stream
         self._descriptor = None                                        # set_descriptor() / describe() / behaviour
@@ -284,6 +285,7 @@ class BatchedModular2D:
         self._sense_rays = {}                                  # ray tables on the device, by content
         self._policy = None                                    # set_policy(): the device policy and its persistent buffers
         self._act_args = None
+        self._context_reset = False
         self._episodes = None                                  # reset_where()'s harvest buffers: made (zeroed) on first use after a reset
         self._episode_args = None
         self._stream_rec = self._refill_args = None            # (a streamed evaluation ends with the upload that replaces it)
@@ -636,13 +638,24 @@ class BatchedModular2D:
         """Attach a ``policy.MLPPolicy`` to the population in place (after reset; a new upload drops it), or None to detach it.  The
         policy needs one weight set per creature, or an ``index`` with one entry per creature, and at most 64 bodies' worth of
         columns; it is moved to the env's device.  The buffers act() works in -- observation rows, ray fractions, targets, validity
-        bytes -- are allocated here, once.  step(), observe(), sense_terrain() and set_joint_targets() are not affected."""
+        bytes -- are allocated here, once.  step(), observe(), sense_terrain() and set_joint_targets() are not affected.
+
+        A ``policy.RecurrentPolicy`` also gets its context words here: ``policy_memory``, float32 ``[N, context]`` in population
+        order, zeroed -- attaching a policy again zeroes them again.  act() carries them from step to step and reads zeros for a
+        creature that reset_where() has just restarted.  Streaming under a recurrent policy is not built: a slot's next creature
+        would inherit its predecessor's context, so with a streamed evaluation in place this raises ValueError."""
+        from .policy import RecurrentPolicy
         self._act_args = None
+        self._context_reset = False
         if policy is None:
             self._policy = None
             return
         if not self.worlds:
             raise ValueError("set_policy: no population in place (reset first)")
+        recurrent = isinstance(policy, RecurrentPolicy)
+        if recurrent and self._stream_rec is not None:
+            raise ValueError("set_policy: a RecurrentPolicy cannot be attached to a streamed evaluation (reset_stream): refill() "
+                             "would hand a slot's context to the next creature -- streaming under recurrent policies is not built")
         have = policy.n_sets if policy.index is None else int(policy.index.shape[0])
         if have != self.n_envs:
             raise ValueError("set_policy: the policy has %d %s for %d creatures"
@@ -655,11 +668,18 @@ class BatchedModular2D:
             obs=torch.zeros((N, control.width(M)), dtype=torch.float32, device=dev),
             frac=torch.ones((N, R), dtype=torch.float32, device=dev) if R else None,
             targets=torch.zeros((N, M), dtype=torch.float64, device=dev),
-            valid=torch.zeros((N, M), dtype=torch.uint8, device=dev))
+            valid=torch.zeros((N, M), dtype=torch.uint8, device=dev),
+            memory=policy.new_memory(N) if recurrent else None)
 
     @property
     def policy(self):
         return None if self._policy is None else self._policy["policy"]
+
+    @property
+    def policy_memory(self):
+        """The context words of the attached ``policy.RecurrentPolicy``: float32 ``[N, context]`` on the device, population order,
+        read and rewritten in place by every act() (clone what must last); None without one."""
+        return None if self._policy is None else self._policy["memory"]
 
     def act(self):
         """One control step by the attached policy: every creature is observed (and its rays cast), the policy's forward pass turns
@@ -667,7 +687,12 @@ class BatchedModular2D:
         (rem2d_worlds_act), four launches queued on the current stream, nothing synchronises.  Returns the persistent ``(targets
         float64 [N, max_bodies], valid uint8 [N, max_bodies])`` buffers the call writes (clone what must last); ``valid`` 0 = the
         target is not finite and that joint was left as it is.  After compact(), rows no live world holds are masked out of the
-        forward pass and keep their last values."""
+        forward pass and keep their last values.
+
+        Under a ``policy.RecurrentPolicy`` the call is rem2d_worlds_act_recurrent -- as many launches -- which also carries
+        ``policy_memory`` forward.  The first act() after a reset_where() (under set_autoreset: every act()) hands that call's
+        ``episodes.ended`` to the kernel as its reset mask: a creature that has just restarted reads zero context, everybody else
+        their own; no extra launch, nothing synchronises."""
         P = self._policy
         if P is None:
             raise ValueError("act: no policy attached (set_policy first)")
@@ -679,13 +704,24 @@ class BatchedModular2D:
                 for wi, (w, idx) in enumerate(self.worlds):
                     if wi not in self._inactive and getattr(w, "h", None):
                         mask[idx] = 1
-            desc = P["policy"].descriptor(P["obs"], P["frac"], P["targets"], P["valid"], mask)
+            if P["memory"] is None:
+                desc = P["policy"].descriptor(P["obs"], P["frac"], P["targets"], P["valid"], mask)
+            else:
+                desc = P["policy"].descriptor(P["obs"], P["frac"], P["targets"], P["valid"], P["memory"], None, mask)
             self._act_args = (worlds, _lib.world_array(worlds) if worlds else None, desc, mask)
         worlds, arr, desc, _ = self._act_args
         if worlds:
             w0 = worlds[0]
-            _lib.check(w0.L.rem2d_worlds_act(arr, len(worlds), C.byref(desc), None if P["rays"] is None else P["rays"].data_ptr(),
-                                             w0._stream()), w0.wide)
+            rays = None if P["rays"] is None else P["rays"].data_ptr()
+            if P["memory"] is None:
+                _lib.check(w0.L.rem2d_worlds_act(arr, len(worlds), C.byref(desc), rays, w0._stream()), w0.wide)
+            else:   # (the reset mask is this one call's: the cached descriptor points at it now and at nothing afterwards)
+                desc.reset = self._episodes.ended.data_ptr() if self._context_reset else None
+                self._context_reset = False
+                try:
+                    _lib.check(w0.L.rem2d_worlds_act_recurrent(arr, len(worlds), C.byref(desc), rays, w0._stream()), w0.wide)
+                finally:
+                    desc.reset = None
         return P["targets"], P["valid"]
 
     def step_policy(self, n_steps=1):
@@ -810,6 +846,7 @@ class BatchedModular2D:
         w0 = worlds[0]
         _lib.check(w0.L.rem2d_worlds_reset_where(arr, morphs, len(worlds), None if mask is None else mask.data_ptr(), bits, steps,
                                                  C.byref(out), self.n_envs, w0._stream()), w0.wide)
+        self._context_reset = True   # (the next act() of a RecurrentPolicy reads `ended` as its reset mask; then never again)
         return self._episodes.ended
 
     def set_autoreset(self, when=("done", "steps"), max_steps=4800):
@@ -899,6 +936,9 @@ class BatchedModular2D:
         rec = self._stream_rec
         if rec is None:
             raise ValueError("refill: no streamed evaluation in place (reset_stream first)")
+        if self._policy is not None and self._policy["memory"] is not None:
+            raise ValueError("refill: a RecurrentPolicy is attached: a slot's next creature would inherit its predecessor's context "
+                             "-- streaming under recurrent policies is not built")
         bits = when_bits(when)
         steps = 0 if max_steps is None else int(max_steps)
         if bits == 0:
@@ -955,7 +995,8 @@ class Modular2D(gymshim.Env):
         follow the ``8 + 6 * max_bodies`` words; ``observation_space`` is that much wider.  The reference advertises them
         (24 = 14 + 10 floats) and never fills them.
         policy (closed loop only): a ``policy.MLPPolicy`` with one weight set and ``max_bodies`` columns; step(None) then acts by it
-        (BatchedModular2D.act) instead of leaving the joints as they are.  An explicit action still wins."""
+        (BatchedModular2D.act) instead of leaving the joints as they are.  An explicit action still wins.  A
+        ``policy.RecurrentPolicy`` works the same way: its context words are the batch env's ``policy_memory``, zero after reset()."""
         self._device = device
         self._policy = policy
         if policy is not None:

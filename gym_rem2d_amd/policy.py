@@ -8,6 +8,9 @@ target per body column, ``scale * softsign(.)``, and a validity byte per target 
 
 The arithmetic is binary32, one separately rounded operation after the other in a fixed order (the header states it), the same in
 every build of the library: what a policy computes is as reproducible as a step.
+
+``RecurrentPolicy`` is the same controller with memory (include/rem2d_recurrent.h): K of its hidden activations are
+input words of the next step, carried per creature in device memory that its own kernel reads and rewrites in place.
 """
 import ctypes as C
 import math
@@ -63,10 +66,7 @@ class MLPPolicy:
             raise ValueError("max_bodies (w2's last axis) must be 1..%d, not %d" % (control.MAX_BODIES, MB))
         if not 1 <= H <= MAX_HIDDEN:
             raise ValueError("the hidden width must be 1..%d, not %d" % (MAX_HIDDEN, H))
-        R = D - control.width(MB)
-        if not 0 <= R <= sense.MAX_RAYS:
-            raise ValueError("w1 has %d input rows: with max_bodies = %d that must be %d + R, R in 0..%d"
-                             % (D, MB, control.width(MB), sense.MAX_RAYS))
+        R = self._ray_inputs(D, MB)
         if activation not in ACTIVATIONS:
             raise ValueError("activation must be one of %r, not %r" % (ACTIVATIONS, activation))
         if len({t.device for t in (w1, b1, w2, b2)}) != 1:
@@ -96,6 +96,14 @@ class MLPPolicy:
         self.util = None        # int32 [M S] on a mean that es_update() made: the utilities of the children it was moved by
 
     # ---- construction ----
+    def _ray_inputs(self, D, MB):
+        """R: how many of w1's D input rows are ray fractions (checked)."""
+        R = D - control.width(MB)
+        if not 0 <= R <= sense.MAX_RAYS:
+            raise ValueError("w1 has %d input rows: with max_bodies = %d that must be %d + R, R in 0..%d"
+                             % (D, MB, control.width(MB), sense.MAX_RAYS))
+        return R
+
     @classmethod
     def random(cls, n_sets, max_bodies, hidden, n_rays=10, seed=0, std=(0.3, 0.3, 0.5, 0.3), **kw):
         """n_sets controllers with normal weights: w1, b1, w2, b2 drawn in that order from ``numpy.random.default_rng(seed)``, scaled
@@ -391,6 +399,86 @@ class MLPPolicy:
         with torch.cuda.device(dev):
             _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
         return new
+
+
+class RecurrentPolicy(MLPPolicy):
+    """G Elman-style partially recurrent controllers (include/rem2d_recurrent.h): an ``MLPPolicy`` whose first
+    ``context`` = K hidden activations of one control step are K extra input words of the next.  The weights have the shapes of an
+    ``MLPPolicy`` with ``D = 8 + 6 * max_bodies + R + K`` input rows -- the K last rows of w1 are the recurrent weights -- so
+    ``R = D - 8 - 6 * max_bodies - K`` and ``1 <= K <= min(H, 64 - R)``.  The context words are not part of the policy: they are a
+    float32 ``[N, K]`` tensor per population (``new_memory``; ``BatchedModular2D.set_policy`` keeps one as ``env.policy_memory``),
+    which ``forward`` reads and rewrites in place.  To everything that only moves weights about -- ``take``, ``to``, ``evolve``,
+    ``es_sample`` / ``es_update``, ``SeparableES``, ``EliteGrid`` -- it is an ordinary weight set of R + K ray inputs, and what those
+    return stays a ``RecurrentPolicy`` of the same K."""
+
+    def __init__(self, w1, b1, w2, b2, context, activation="softsign", scale=None, index=None, rays=None):
+        if isinstance(context, bool) or not isinstance(context, (int, np.integer)) or int(context) < 1:
+            raise ValueError("context (K, the hidden units fed back) must be an integer of at least 1, not %r" % (context,))
+        self.context = int(context)
+        super().__init__(w1, b1, w2, b2, activation, scale, index, rays)
+        if self.context > self.hidden:
+            raise ValueError("context = %d is more than the %d hidden units there are to feed back" % (self.context, self.hidden))
+
+    def _ray_inputs(self, D, MB):
+        K = self.context
+        R = D - control.width(MB) - K
+        if R < 0 or R + K > _lib.RECURRENT_MAX_INPUTS:
+            raise ValueError("w1 has %d input rows: with max_bodies = %d and context = %d that must be %d + R + %d, R in 0..%d"
+                             % (D, MB, K, control.width(MB), K, _lib.RECURRENT_MAX_INPUTS - K))
+        return R
+
+    @classmethod
+    def random(cls, n_sets, max_bodies, hidden, context, n_rays=10, seed=0, std=(0.3, 0.3, 0.5, 0.3), **kw):
+        """As ``MLPPolicy.random``, with ``context`` more input rows in w1: the same draw as an ``MLPPolicy`` of
+        ``n_rays + context`` rays."""
+        std = (float(std),) * 4 if np.isscalar(std) else tuple(float(s) for s in std)
+        rng = np.random.default_rng(seed)
+        D = input_width(max_bodies, n_rays) + int(context)
+        shapes = ((n_sets, D, hidden), (n_sets, hidden), (n_sets, hidden, max_bodies), (n_sets, max_bodies))
+        arrays = [torch.from_numpy((rng.standard_normal(s) * sd).astype(np.float32)) for s, sd in zip(shapes, std)]
+        if n_rays not in (0, 10) and "rays" not in kw:
+            kw["rays"] = sense.bipedal_rays(n_rays)
+        return cls(*arrays, context, **kw)
+
+    def _like(self, w1, b1, w2, b2, index):
+        return RecurrentPolicy(w1, b1, w2, b2, self.context, self.activation, self.scale, index, self.rays)
+
+    def new_memory(self, n_rows):
+        """Zeroed context words for ``n_rows`` population rows: float32 ``[n_rows, context]`` on the policy's device."""
+        return torch.zeros((int(n_rows), self.context), dtype=torch.float32, device=self.device)
+
+    # ---- the library's descriptor ----
+    def descriptor(self, obs, frac, targets, valid, memory, reset=None, row_mask=None):
+        """rem2d_recurrent over these buffers (checked as ``MLPPolicy.descriptor`` checks its own; ``memory`` float32 ``[N, K]``,
+        ``reset`` uint8 or bool ``[N]`` or None)."""
+        p = super().descriptor(obs, frac, targets, valid, row_mask)
+        dev, N = self.device, int(obs.shape[0])
+        if (not isinstance(memory, torch.Tensor) or memory.dtype != torch.float32 or not memory.is_contiguous() or memory.device != dev
+                or tuple(memory.shape) != (N, self.context)):
+            raise ValueError("policy: memory must be a contiguous torch.float32 %r tensor on %s" % ((N, self.context), dev))
+        if reset is not None and (not isinstance(reset, torch.Tensor) or reset.dtype not in (torch.uint8, torch.bool)
+                                  or not reset.is_contiguous() or reset.device != dev or tuple(reset.shape) != (N,)):
+            raise ValueError("policy: reset must be a contiguous torch.uint8 or torch.bool %r tensor on %s" % ((N,), dev))
+        q = _lib.Recurrent()
+        q.p, q.context, q.reserved = p, self.context, 0
+        q.memory, q.reset = memory.data_ptr(), (None if reset is None else reset.data_ptr())
+        return q
+
+    def forward(self, obs, frac, memory, reset=None, out=None, row_mask=None, wide=False):
+        """The recurrent forward pass alone (rem2d_recurrent_forward) on the current stream: ``obs``, ``frac``, ``out``, ``row_mask``
+        and ``wide`` as ``MLPPolicy.forward`` takes them; ``memory`` float32 ``[N, context]`` is the rows' context, read and then
+        overwritten IN PLACE with this step's first ``context`` hidden activations; ``reset`` uint8 / bool ``[N]``: a row whose
+        entry is set reads +0 for its context whatever memory holds (a new episode).  A row that is skipped keeps its memory too.
+        Returns ``(targets, valid)``."""
+        N = int(obs.shape[0])
+        if out is None:
+            out = (torch.zeros((N, self.max_bodies), dtype=torch.float64, device=self.device),
+                   torch.zeros((N, self.max_bodies), dtype=torch.uint8, device=self.device))
+        q = self.descriptor(obs, frac, out[0], out[1], memory, reset, row_mask)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib(wide).rem2d_recurrent_forward(C.byref(q), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                       wide)
+        return out
 
 
 class SeparableES:
