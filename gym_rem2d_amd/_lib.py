@@ -109,6 +109,10 @@ ELITES_ABI_VERSION = 1      # include/rem2d_elites.h
 ELITES_MAX_WIDTH = 32       # REM2D_ELITES_MAX_WIDTH
 ELITES_MAX_DIMS = 4         # REM2D_ELITES_MAX_DIMS
 ELITES_MAX_CELLS = 65536    # REM2D_ELITES_MAX_CELLS
+CVT_ABI_VERSION = 1         # include/rem2d_cvt.h
+CVT_MAX_WIDTH = 32          # REM2D_CVT_MAX_WIDTH
+CVT_MAX_CELLS = 65536       # REM2D_CVT_MAX_CELLS
+CVT_MAX_SPLITS = 4096       # REM2D_CVT_MAX_SPLITS
 SNES_ABI_VERSION = 1        # include/rem2d_snes.h
 SNES_MAX_GROUP = 8192       # REM2D_SNES_MAX_GROUP
 SNES_ADAM, SNES_NATURAL = 1, 2   # REM2D_SNES_ADAM, REM2D_SNES_NATURAL
@@ -224,6 +228,19 @@ class Elites(C.Structure):
                                              "elite_w1", "elite_b1", "elite_w2", "elite_b2", "count", "cell", "winner", "child_w1",
                                              "child_b1", "child_w2", "child_b2", "parent", "n_filled", "scratch")]
                 + [("scratch_bytes", C.c_uint64), ("reserved", C.c_int32)])
+
+
+class Cvt(C.Structure):
+    """rem2d_cvt (include/rem2d_cvt.h): device pointers the caller owns, and the stream the calls queue on."""
+    _fields_ = ([(k, C.c_int32) for k in ("d", "hidden", "max_bodies", "width", "n_cells", "n_blocks", "group_size", "n_children",
+                                          "n_rows", "splits")]
+                + [("generation", C.c_uint32), ("sigma_iso", C.c_float), ("sigma_line", C.c_float), ("reserved", C.c_int32),
+                   ("seed", C.c_uint64)]
+                + [(k, C.c_void_p) for k in ("centroids", "desc", "fitness", "mask", "w1", "b1", "w2", "b2", "elite_fitness",
+                                             "elite_desc", "elite_w1", "elite_b1", "elite_w2", "elite_b2", "count", "cell", "dist",
+                                             "winner", "child_w1", "child_b1", "child_w2", "child_b2", "parent", "parent2", "n_filled",
+                                             "scratch")]
+                + [("scratch_bytes", C.c_uint64), ("stream", C.c_void_p)])
 
 
 SNES_ARRAYS = ("w1", "b1", "w2", "b2")
@@ -509,6 +526,14 @@ def lib(wide=False):
         fn.argtypes = [C.POINTER(Elites), C.c_void_p]
     if L.rem2d_elites_abi_version() != ELITES_ABI_VERSION:
         raise Rem2dError("%s: elites ABI version mismatch" % os.path.basename(path))
+    # centroid archives and the line emitter (include/rem2d_cvt.h): the stream is a member of the descriptor
+    L.rem2d_cvt_abi_version.restype = C.c_int
+    L.rem2d_cvt_scratch_bytes.restype = C.c_int64
+    L.rem2d_cvt_scratch_bytes.argtypes = [C.POINTER(Cvt)]
+    for fn in (L.rem2d_cvt_assign, L.rem2d_cvt_insert, L.rem2d_cvt_emit_line):
+        fn.argtypes = [C.POINTER(Cvt)]
+    if L.rem2d_cvt_abi_version() != CVT_ABI_VERSION:
+        raise Rem2dError("%s: cvt ABI version mismatch" % os.path.basename(path))
     # an adaptive evolution strategy for device policies (include/rem2d_snes.h)
     L.rem2d_snes_abi_version.restype = C.c_int
     L.rem2d_snes_scratch_bytes.restype = C.c_int64

@@ -50,6 +50,7 @@
 #include <rem2d_es.h>      // (as rem2d_evolve.h: the quoted name below is the kernels' file)
 #include <rem2d_novelty.h> // (likewise)
 #include <rem2d_elites.h>  // (likewise)
+#include <rem2d_cvt.h>     // (likewise)
 #include <rem2d_snes.h>    // (likewise)
 #include <rem2d_pareto.h>  // (likewise)
 #include <rem2d_recurrent.h> // (likewise)
@@ -117,6 +118,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_es.h"
 #include "rem2d_novelty.h"
 #include "rem2d_elites.h"
+#include "rem2d_cvt.h"
 #include "rem2d_snes.h"
 #include "rem2d_pareto.h"
 
@@ -2556,6 +2558,237 @@ extern "C" int rem2d_elites_emit(const rem2d_elites *e, void *stream) {
     const int rc = el_ok("elites_emit", e, EL_SAMPLE | EL_VARY);
     if (rc != REM2D_OK) return rc;
     return el_launch(e, EL_SAMPLE | EL_VARY, (hipStream_t)stream);
+}
+
+// ---- Centroid archives and the line emitter (include/rem2d_cvt.h, csrc/rem2d_cvt.h) ----
+extern "C" int rem2d_cvt_abi_version(void) { return REM2D_CVT_ABI_VERSION; }
+static_assert(REM2D_CVT_MAX_WIDTH == REM2D_ELITES_MAX_WIDTH && REM2D_CVT_MAX_CELLS == REM2D_ELITES_MAX_CELLS, "a centroid archive is an elite grid of one dimension");
+static_assert(CV_TILE == EL_TILE, "the insertion mixes the two tiers' launches");
+enum { CV_ASSIGN = 1, CV_INSERT = 2, CV_LINE = 4 };
+// Checks what the assignment looks at of the shapes; `s` prefixes the message.  No pointer is looked at.
+static int cv_assign_shapes_ok(const std::string &s, const rem2d_cvt *v) {
+    if (!v) return fail(REM2D_E_INVALID, s + "NULL descriptor");
+    if (v->width < 1 || v->width > REM2D_CVT_MAX_WIDTH)
+        return fail(REM2D_E_INVALID, s + "width must be 1.." + std::to_string(REM2D_CVT_MAX_WIDTH) + ", not " + std::to_string(v->width));
+    if (v->n_cells < 1 || v->n_cells > REM2D_CVT_MAX_CELLS)
+        return fail(REM2D_E_INVALID, s + "n_cells must be 1.." + std::to_string(REM2D_CVT_MAX_CELLS) + ", not " + std::to_string(v->n_cells));
+    if (v->splits < 0 || v->splits > REM2D_CVT_MAX_SPLITS)
+        return fail(REM2D_E_INVALID, s + "splits must be 0.." + std::to_string(REM2D_CVT_MAX_SPLITS) + ", not " + std::to_string(v->splits));
+    if (v->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0");
+    return REM2D_OK;
+}
+// Checks the shapes and parameters of a centroid descriptor.  No pointer is looked at.
+static int cv_shapes_ok(const std::string &s, const rem2d_cvt *v) {
+    const int rc = cv_assign_shapes_ok(s, v);
+    if (rc != REM2D_OK) return rc;
+    if (v->max_bodies < 1 || v->max_bodies > REM2D_CONTROL_MAX_BODIES)
+        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(v->max_bodies));
+    if (v->hidden < 1 || v->hidden > REM2D_POLICY_MAX_HIDDEN)
+        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(v->hidden));
+    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * v->max_bodies;
+    if (v->d < d0 || v->d > d0 + REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
+                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(v->d));
+    if (v->n_blocks < 1) return fail(REM2D_E_INVALID, s + "n_blocks must be at least 1, not " + std::to_string(v->n_blocks));
+    if ((long long)v->n_blocks * (long long)v->n_cells > 2147483647ll) return fail(REM2D_E_INVALID, s + "n_blocks times n_cells must be at most 2^31 - 1");
+    if (v->group_size > 0 && (long long)v->n_blocks * (long long)v->group_size > 2147483647ll)
+        return fail(REM2D_E_INVALID, s + "n_blocks * group_size must be at most 2^31 - 1");
+    if (!el_finite(v->sigma_iso) || !el_finite(v->sigma_line)) return fail(REM2D_E_INVALID, s + "sigma_iso and sigma_line must be finite");
+    return REM2D_OK;
+}
+static size_t cv_slots(const rem2d_cvt *v) { return (size_t)v->n_blocks * (size_t)v->n_cells; }
+// Checks a centroid descriptor for the call `stage`.  Nothing it points to is read.
+static int cv_ok(const char *what, const rem2d_cvt *v, int stage) {
+    const std::string s = std::string(what) + ": ";
+    const int rc = stage == CV_ASSIGN ? cv_assign_shapes_ok(s, v) : cv_shapes_ok(s, v);
+    if (rc != REM2D_OK) return rc;
+    size_t need = 0;
+    if (stage == CV_ASSIGN) {
+        if (v->n_rows < 1) return fail(REM2D_E_INVALID, s + "n_rows must be at least 1, not " + std::to_string(v->n_rows));
+        need = (size_t)v->n_rows * sizeof(unsigned long long);
+    } else {
+        need = cv_slots(v) * (sizeof(unsigned long long) + sizeof(int));
+    }
+    const size_t slots = stage == CV_ASSIGN ? 0 : cv_slots(v);
+    const size_t len[4] = {(size_t)v->d * (size_t)v->hidden, (size_t)v->hidden, (size_t)v->hidden * (size_t)v->max_bodies, (size_t)v->max_bodies};
+    const char *const name[4] = {"w1", "b1", "w2", "b2"};
+    const float *elite[4] = {v->elite_w1, v->elite_b1, v->elite_w2, v->elite_b2};
+    if (stage == CV_INSERT) {
+        if (v->group_size < 1) return fail(REM2D_E_INVALID, s + "group_size must be at least 1, not " + std::to_string(v->group_size));
+        need += (size_t)v->n_blocks * (size_t)v->group_size * sizeof(unsigned long long);
+    }
+    if (stage == CV_LINE) {
+        if (v->n_children < 1 || v->n_children % v->n_blocks != 0)
+            return fail(REM2D_E_INVALID, s + "n_children must be a positive multiple of n_blocks (" + std::to_string(v->n_blocks) + "), not " + std::to_string(v->n_children));
+    }
+    if (stage & (CV_ASSIGN | CV_INSERT)) {
+        const size_t rows = stage == CV_ASSIGN ? (size_t)v->n_rows : (size_t)v->n_blocks * (size_t)v->group_size;
+        if (!v->centroids) return fail(REM2D_E_INVALID, s + "NULL device pointer (centroids)");
+        if (!v->desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (desc)");
+        if (!v->cell) return fail(REM2D_E_INVALID, s + "NULL device pointer (cell)");
+        const struct { const char *name; const void *p; size_t bytes; } in[2] = {
+            {"desc", v->desc, rows * (size_t)v->width * sizeof(float)}, {"centroids", v->centroids, (size_t)v->n_cells * (size_t)v->width * sizeof(float)}};
+        for (int i = 0; i < 2; ++i) {
+            if (el_overlap(in[i].p, in[i].bytes, v->cell, rows * sizeof(int))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps cell");
+            if (v->dist && el_overlap(in[i].p, in[i].bytes, v->dist, rows * sizeof(float))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps dist");
+        }
+        if (stage == CV_INSERT) {
+            if (!v->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
+            if (!v->elite_fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (elite_fitness)");
+            if (!v->elite_desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (elite_desc)");
+            if (!v->count) return fail(REM2D_E_INVALID, s + "NULL device pointer (count)");
+            if (!v->winner) return fail(REM2D_E_INVALID, s + "NULL device pointer (winner)");
+            const float *src[4] = {v->w1, v->b1, v->w2, v->b2};
+            for (int k = 0; k < 4; ++k)
+                if (!src[k] || !elite[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+            for (int i = 0; i < 2; ++i) {
+                if (el_overlap(in[i].p, in[i].bytes, v->elite_fitness, slots * sizeof(double))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps elite_fitness");
+                if (el_overlap(in[i].p, in[i].bytes, v->elite_desc, slots * (size_t)v->width * sizeof(float))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps elite_desc");
+                if (el_overlap(in[i].p, in[i].bytes, v->count, slots * sizeof(int))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps count");
+                for (int k = 0; k < 4; ++k)
+                    if (el_overlap(in[i].p, in[i].bytes, elite[k], slots * len[k] * sizeof(float))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps elite_" + name[k]);
+            }
+            for (int k = 0; k < 4; ++k)
+                for (int j = 0; j < 4; ++j)
+                    if (el_overlap(src[j], rows * len[j] * sizeof(float), elite[k], slots * len[k] * sizeof(float)))
+                        return fail(REM2D_E_INVALID, s + "elite_" + name[k] + " overlaps the evaluated sets' " + name[j]);
+        }
+    }
+    if (stage == CV_LINE) {
+        if (!v->count) return fail(REM2D_E_INVALID, s + "NULL device pointer (count)");
+        if (!v->parent) return fail(REM2D_E_INVALID, s + "NULL device pointer (parent)");
+        if (!v->parent2) return fail(REM2D_E_INVALID, s + "NULL device pointer (parent2)");
+        if (!v->n_filled) return fail(REM2D_E_INVALID, s + "NULL device pointer (n_filled)");
+        const float *dst[4] = {v->child_w1, v->child_b1, v->child_w2, v->child_b2};
+        for (int k = 0; k < 4; ++k)
+            if (!dst[k] || !elite[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        for (int k = 0; k < 4; ++k)
+            for (int j = 0; j < 4; ++j)
+                if (el_overlap(dst[k], (size_t)v->n_children * len[k] * sizeof(float), elite[j], slots * len[j] * sizeof(float)))
+                    return fail(REM2D_E_INVALID, s + "child_" + name[k] + " overlaps elite_" + name[j]);
+    }
+    if (!v->scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
+    if ((uintptr_t)v->scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
+    if (v->scratch_bytes < (uint64_t)need)
+        return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(v->scratch_bytes) + " bytes, " + std::to_string(need) + " are needed");
+    return REM2D_OK;
+}
+// The assignment of `rows` rows on `st`: A.best is set.  One launch, or clear + split assign + read-out.
+static int cv_assign_launch(CvArgs &A, long long rows, int splits, hipStream_t st) {
+    const unsigned tiles = (unsigned)((rows + CV_TILE - 1) / CV_TILE);
+    const int chunks = (A.C + CV_TILE - 1) / CV_TILE; // a split below one LDS tile of centroids gains nothing
+    if (splits == 0) // the library's choice: about 1024 workgroups where the rows alone give fewer than 512
+        splits = tiles >= 512u ? 1 : std::min(chunks, (int)((1024u + tiles - 1u) / tiles));
+    A.rows = rows;
+    A.splits = splits;
+    A.per = (A.C + splits - 1) / splits;
+    if (splits > 1) {
+        hipLaunchKernelGGL(rem2d_cvt_clear_kernel, dim3(tiles), dim3(CV_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    const dim3 grid(tiles, (unsigned)splits);
+    if (A.B <= 4) hipLaunchKernelGGL(rem2d_cvt_assign_kernel<4>, grid, dim3(CV_TILE), 0, st, A);
+    else if (A.B <= 8) hipLaunchKernelGGL(rem2d_cvt_assign_kernel<8>, grid, dim3(CV_TILE), 0, st, A);
+    else if (A.B <= 16) hipLaunchKernelGGL(rem2d_cvt_assign_kernel<16>, grid, dim3(CV_TILE), 0, st, A);
+    else hipLaunchKernelGGL(rem2d_cvt_assign_kernel<32>, grid, dim3(CV_TILE), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    if (splits > 1) {
+        hipLaunchKernelGGL(rem2d_cvt_finish_kernel, dim3(tiles), dim3(CV_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+// The call `stage` of a checked descriptor on its stream.
+static int cv_launch(const rem2d_cvt *v, int stage) {
+    const hipStream_t st = (hipStream_t)v->stream;
+    CvArgs A;
+    memset(&A, 0, sizeof(A));
+    A.desc = v->desc; A.centroids = v->centroids; A.cell = v->cell; A.dist = v->dist;
+    A.B = v->width; A.C = v->n_cells;
+    A.best = (unsigned long long *)v->scratch;
+    if (stage == CV_ASSIGN) return cv_assign_launch(A, (long long)v->n_rows, v->splits, st);
+    const long long slots = (long long)cv_slots(v);
+    A.fitness = v->fitness; A.mask = v->mask; A.count = v->count;
+    A.parent = v->parent; A.parent2 = v->parent2; A.nFilled = v->n_filled;
+    A.key0 = (unsigned)(v->seed & 0xffffffffull); A.key1 = (unsigned)(v->seed >> 32); A.generation = v->generation;
+    A.M = v->n_blocks; A.S = v->group_size;
+    const int len[4] = {v->d * v->hidden, v->hidden, v->hidden * v->max_bodies, v->max_bodies};
+    float *const elite[4] = {v->elite_w1, v->elite_b1, v->elite_w2, v->elite_b2};
+    if (stage == CV_INSERT) {
+        // scratch: best[G] | key[M C] | row[M C]; the elites' kernels see the last two as they see their own scratch
+        const long long G = (long long)A.M * (long long)A.S;
+        A.key = A.best + G;
+        const int rc = cv_assign_launch(A, G, v->splits, st);
+        if (rc != REM2D_OK) return rc;
+        ElArgs L;
+        EvolveArgs E;
+        memset(&L, 0, sizeof(L));
+        memset(&E, 0, sizeof(E));
+        L.desc = v->desc; L.fitness = v->fitness; L.mask = v->mask;
+        L.eliteFitness = v->elite_fitness; L.eliteDesc = v->elite_desc;
+        L.count = v->count; L.cell = v->cell; L.winner = v->winner;
+        L.key = A.key; L.row = (int *)(A.key + slots);
+        L.B = A.B; L.M = A.M; L.S = A.S; L.C = A.C;
+        const float *src[4] = {v->w1, v->b1, v->w2, v->b2};
+        for (int k = 0; k < 4; ++k) {
+            E.len[k] = len[k];
+            E.src[k] = src[k];
+            E.dst[k] = elite[k];
+            E.vec[k] = E.len[k] % 4 == 0 && (uintptr_t)E.src[k] % 16 == 0 && (uintptr_t)E.dst[k] % 16 == 0;
+        }
+        hipLaunchKernelGGL(rem2d_elites_clear_kernel, dim3((unsigned)((slots + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, L);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rem2d_cvt_key_kernel, dim3((unsigned)((G + CV_TILE - 1) / CV_TILE)), dim3(CV_TILE), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rem2d_elites_row_kernel, dim3((unsigned)((G + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, L);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rem2d_elites_commit_kernel, dim3((unsigned)slots), dim3(WAVE), 0, st, L, E);
+        HIP_TRY(hipGetLastError());
+        return REM2D_OK;
+    }
+    // CV_LINE: the draw (its list in the scratch's last M C words, where the elites' sample keeps it), then the variation
+    A.list = (int *)((unsigned long long *)v->scratch + slots);
+    A.perBlock = v->n_children / v->n_blocks;
+    hipLaunchKernelGGL(rem2d_cvt_draw_kernel, dim3((unsigned)A.M), dim3(CV_TILE), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    CvLine Ln;
+    memset(&Ln, 0, sizeof(Ln));
+    float *const dst[4] = {v->child_w1, v->child_b1, v->child_w2, v->child_b2};
+    for (int k = 0; k < 4; ++k) {
+        Ln.len[k] = len[k];
+        Ln.src[k] = elite[k];
+        Ln.dst[k] = dst[k];
+        Ln.vec[k] = len[k] % 4 == 0 && (uintptr_t)elite[k] % 16 == 0 && (uintptr_t)dst[k] % 16 == 0;
+    }
+    Ln.parent = v->parent; Ln.parent2 = v->parent2;
+    Ln.key0 = A.key0; Ln.key1 = A.key1; Ln.generation = v->generation;
+    Ln.slots = (int)slots;
+    Ln.sigmaIso = v->sigma_iso; Ln.sigmaLine = v->sigma_line;
+    hipLaunchKernelGGL(rem2d_cvt_line_kernel, dim3((unsigned)v->n_children), dim3(WAVE), 0, st, Ln);
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
+}
+extern "C" int64_t rem2d_cvt_scratch_bytes(const rem2d_cvt *v) {
+    const int rc = cv_shapes_ok("cvt_scratch_bytes: ", v);
+    if (rc != REM2D_OK) return rc;
+    const long long G = v->group_size > 0 ? (long long)v->n_blocks * (long long)v->group_size : 0;
+    const long long R = std::max((long long)(v->n_rows > 0 ? v->n_rows : 0), G);
+    return (int64_t)(cv_slots(v) * 12) + (int64_t)(8 * R);
+}
+extern "C" int rem2d_cvt_assign(const rem2d_cvt *v) {
+    const int rc = cv_ok("cvt_assign", v, CV_ASSIGN);
+    if (rc != REM2D_OK) return rc;
+    return cv_launch(v, CV_ASSIGN);
+}
+extern "C" int rem2d_cvt_insert(const rem2d_cvt *v) {
+    const int rc = cv_ok("cvt_insert", v, CV_INSERT);
+    if (rc != REM2D_OK) return rc;
+    return cv_launch(v, CV_INSERT);
+}
+extern "C" int rem2d_cvt_emit_line(const rem2d_cvt *v) {
+    const int rc = cv_ok("cvt_emit_line", v, CV_LINE);
+    if (rc != REM2D_OK) return rc;
+    return cv_launch(v, CV_LINE);
 }
 
 // ---- Pareto ranking (include/rem2d_pareto.h, csrc/rem2d_pareto.h) ----

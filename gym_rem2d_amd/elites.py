@@ -5,6 +5,10 @@ whose every cell keeps the best controller ever seen there, with its fitness and
 ``evaluate.run_behaviour_episode`` returns them) into the grids; ``EliteGrid.emit`` makes the next children, mutated copies of
 uniformly drawn elites, with the mutation of ``MLPPolicy.evolve``; ``evaluate.run_policy_map_elites`` is the loop.
 
+``CentroidArchive`` (include/rem2d_cvt.h) is the same state over C centroids instead of a regular cell map -- CVT-MAP-Elites: a row
+belongs to its nearest centroid, over the whole descriptor row --, ``cvt_centroids`` makes the centroids, and ``EliteGrid.emit_line``
+is the directional iso+line variation between two elites, on grids and centroid archives alike.  tests/cvt_model.py restates those.
+
 Nothing here allocates after the grid was made and ``out=`` is given; every call is one library call queued on the current stream;
 nothing synchronises.  tests/elites_model.py restates every output bit in numpy."""
 import ctypes as C
@@ -271,3 +275,262 @@ class EliteGrid:
         e.child_w1, e.child_b1, e.child_w2, e.child_b2 = (t.data_ptr() for t in (out.w1, out.b1, out.w2, out.b2))
         self._call("rem2d_elites_emit", e, wide)
         return out
+
+    def _line_descriptor(self, generation, seed, sigma_iso, sigma_line):
+        v = _lib.Cvt()
+        v.d, v.hidden, v.max_bodies, v.width, v.n_cells, v.n_blocks = self.d, self.hidden, self.max_bodies, self.width, self.n_cells, self.n_blocks
+        v.generation, v.seed, v.sigma_iso, v.sigma_line, v.splits, v.reserved = int(generation), int(seed), float(sigma_iso), float(sigma_line), 0, 0
+        v.elite_fitness, v.elite_desc, v.count = self.fitness.data_ptr(), self.desc.data_ptr(), self.count.data_ptr()
+        v.elite_w1, v.elite_b1, v.elite_w2, v.elite_b2 = (t.data_ptr() for t in (self.w1, self.b1, self.w2, self.b2))
+        v.winner, v.n_filled = self.winner.data_ptr(), self.filled.data_ptr()
+        v.scratch, v.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel() * 8
+        return v
+
+    def _call_cvt(self, name, v, wide):
+        _call_cvt(name, v, self.device, wide)
+
+    def emit_line(self, generation, seed=0, sigma_iso=0.01, sigma_line=0.2, n_children=None, out=None, wide=False):
+        """The next children by the iso+line variation (rem2d_cvt_emit_line; Vassiliades & Mouret 2018): child c descends from TWO
+        uniformly drawn elites of its block, ``x1`` (the draw of ``sample`` / ``emit``) and ``x2`` (a draw of its own), as
+        ``(x1 + sigma_iso * z) + a * (x2 - x1)``: ``z`` a unit-variance draw per element, ``a = sigma_line * zl`` one draw per child.
+        Every element moves; there is no rate.  ``sigma_line = 0`` is ``emit(rate=1.0, sigma=sigma_iso)`` bit for bit.  A child of a
+        block whose grid is empty keeps the words its buffer holds.  ``n_children``, ``out``: as ``emit``.
+
+        Returns the child ``MLPPolicy`` with ``.parents`` and ``.parents2`` int32 ``[n_children]`` (slots of the grid, or -1)."""
+        if out is not None:
+            self._fits("emit_line", out, None if n_children is None else int(n_children))
+            if n_children is None:
+                n_children = out.n_sets
+        n = self._draw("emit_line", generation, seed, n_children, None)
+        if not math.isfinite(float(sigma_iso)) or not math.isfinite(float(sigma_line)):
+            raise ValueError("emit_line: sigma_iso and sigma_line must be finite, not %r, %r" % (sigma_iso, sigma_line))
+        if self.device.type != "cuda":
+            raise ValueError("emit_line: the grid is on %s; make it on the GPU (device=...)" % self.device)
+        dev = self.device
+        if out is None:
+            out = self.like._like(*(torch.zeros((n,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+                                     for t in (self.w1, self.b1, self.w2, self.b2)), None)
+        else:
+            out.activation, out.scale, out.rays = self.like.activation, self.like.scale, self.like.rays
+        for attr in ("parents", "parents2"):
+            have = getattr(out, attr, None)
+            if have is None or have.dtype != torch.int32 or tuple(have.shape) != (n,) or have.device != dev or not have.is_contiguous():
+                setattr(out, attr, torch.empty(n, dtype=torch.int32, device=dev))
+        v = self._line_descriptor(generation, seed, sigma_iso, sigma_line)
+        v.n_children, v.parent, v.parent2 = n, out.parents.data_ptr(), out.parents2.data_ptr()
+        v.child_w1, v.child_b1, v.child_w2, v.child_b2 = (t.data_ptr() for t in (out.w1, out.b1, out.w2, out.b2))
+        self._call_cvt("rem2d_cvt_emit_line", v, wide)
+        return out
+
+
+def _call_cvt(name, v, device, wide):
+    """a call of include/rem2d_cvt.h: the stream is a member of the descriptor, not a parameter"""
+    L = _lib.lib(wide)
+    with torch.cuda.device(device):
+        v.stream = torch.cuda.current_stream(device).cuda_stream
+        _lib.check(getattr(L, name)(C.byref(v)), wide)
+
+
+def assign_host(desc, centroids, chunk=None):
+    """The nearest centroid of every row as include/rem2d_cvt.h defines it, in numpy on the host: ``d2 = d2 + (t * t)`` with
+    ``t = x_i - y_i`` for ascending i, every operation a binary32 one; the lowest centroid of the least finite d2
+    -> (cell int32 [n], dist float32 [n]); cell -1 and dist +inf for a row with no finite candidate."""
+    x, y = np.ascontiguousarray(desc, np.float32), np.ascontiguousarray(centroids, np.float32)
+    n, B = x.shape
+    C_ = y.shape[0]
+    cell, dist = np.full(n, -1, np.int32), np.full(n, np.inf, np.float32)
+    step = max(1, (1 << 22) // max(C_, 1)) if chunk is None else int(chunk)
+    with np.errstate(all="ignore"):
+        for r0 in range(0, n, step):
+            xs = x[r0:r0 + step]
+            d2 = np.zeros((xs.shape[0], C_), np.float32)
+            for i in range(B):
+                t = xs[:, i, None] - y[None, :, i]
+                d2 = d2 + t * t
+            assert d2.dtype == np.float32
+            d2 = np.where(np.isfinite(d2), d2, np.float32(np.inf))
+            q = np.argmin(d2, axis=1)                          # (the first of equal minima: the lowest centroid)
+            best = d2[np.arange(xs.shape[0]), q]
+            cell[r0:r0 + step] = np.where(best < np.inf, q, -1)
+            dist[r0:r0 + step] = best
+    return cell, dist
+
+
+def _check_rows(what, desc, width, dev):
+    if not isinstance(desc, torch.Tensor) or desc.dtype != torch.float32:
+        raise ValueError("%s: desc must be a torch.float32 tensor" % what)
+    if desc.dim() != 2 or desc.shape[1] != width or desc.shape[0] < 1 or not desc.is_contiguous() or desc.device != dev:
+        raise ValueError("%s: desc must be a contiguous tensor [n, %d] on %s, not %s on %s" % (what, width, dev, list(desc.shape), desc.device))
+    if desc.shape[0] > 2 ** 31 - 1:
+        raise ValueError("%s: at most 2^31 - 1 rows" % what)
+
+
+def _assign(what, desc, centroids, out, dist, scratch, wide=False, splits=0):
+    """rem2d_cvt_assign (a GPU device) or assign_host (the CPU) -> (cell, the scratch tensor to keep)"""
+    dev = centroids.device
+    _check_rows(what, desc, centroids.shape[1], dev)
+    n = desc.shape[0]
+    for name, t, dt in (("out", out, torch.int32), ("dist", dist, torch.float32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != dev):
+            raise ValueError("%s: %s must be a contiguous %s [%d] tensor on %s" % (what, name, dt, n, dev))
+    if not 0 <= int(splits) <= _lib.CVT_MAX_SPLITS:
+        raise ValueError("%s: splits must be 0 .. %d, not %r" % (what, _lib.CVT_MAX_SPLITS, splits))
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    if dev.type != "cuda":
+        cell, d = assign_host(desc.numpy(), centroids.numpy())
+        out.copy_(torch.from_numpy(cell))
+        if dist is not None:
+            dist.copy_(torch.from_numpy(d))
+        return out, scratch
+    if scratch is None or scratch.numel() < n:
+        scratch = torch.empty(n, dtype=torch.int64, device=dev)
+    v = _lib.Cvt()
+    v.width, v.n_cells, v.n_rows, v.splits, v.reserved = centroids.shape[1], centroids.shape[0], n, int(splits), 0
+    v.centroids, v.desc, v.cell, v.dist = centroids.data_ptr(), desc.data_ptr(), out.data_ptr(), None if dist is None else dist.data_ptr()
+    v.scratch, v.scratch_bytes = scratch.data_ptr(), scratch.numel() * 8
+    _call_cvt("rem2d_cvt_assign", v, dev, wide)
+    return out, scratch
+
+
+def _check_centroids(what, centroids, dev):
+    if isinstance(centroids, np.ndarray):
+        if centroids.dtype != np.float32:
+            raise ValueError("%s: centroids must be float32, not %s" % (what, centroids.dtype))
+        centroids = torch.from_numpy(np.ascontiguousarray(centroids))
+    if not isinstance(centroids, torch.Tensor) or centroids.dtype != torch.float32 or centroids.dim() != 2:
+        raise ValueError("%s: centroids must be a float32 [C, width] array or tensor" % what)
+    C_, width = int(centroids.shape[0]), int(centroids.shape[1])
+    if not 1 <= C_ <= _lib.CVT_MAX_CELLS:
+        raise ValueError("%s: 1 .. %d centroids, not %d" % (what, _lib.CVT_MAX_CELLS, C_))
+    if not 1 <= width <= _lib.CVT_MAX_WIDTH:
+        raise ValueError("%s: width must be 1 .. %d, not %d" % (what, _lib.CVT_MAX_WIDTH, width))
+    return centroids.detach().to(dev).contiguous().clone()
+
+
+class CentroidArchive(EliteGrid):
+    """``n_blocks`` archives of C cells over descriptor rows of ``width`` words, CVT-MAP-Elites (include/rem2d_cvt.h):
+    ``centroids`` float32 ``[C, width]`` (1 <= C <= 65536, width <= 32; ``cvt_centroids`` makes them), shared by all blocks; the
+    cell of a row is its NEAREST centroid -- squared distance summed word by word in binary32, ties to the lowest centroid, a
+    non-finite distance never chosen, no finite one: not admitted.  The tensors are ``EliteGrid``'s, plus ``centroids`` (a copy on
+    ``device``) and, after an ``insert``, ``dist`` float32 ``[G]``: every row's squared distance to its centroid.  ``sample``,
+    ``emit``, ``emit_line`` and the readings are inherited: to them the archive is a grid of one dimension of C bins."""
+
+    def __init__(self, n_blocks, centroids, like, device=None):
+        dev = torch.zeros(0, device="cpu" if device is None else device).device
+        cen = _check_centroids("CentroidArchive", centroids, dev)
+        C_, width = int(cen.shape[0]), int(cen.shape[1])
+        super().__init__(n_blocks, [(0, 0.0, float(C_), C_)], width, like, device=dev)
+        self.centroids = cen
+        self.dist = None
+        self._vscratch = None
+
+    _STATE = EliteGrid._STATE + ("centroids",)
+
+    def assign(self, desc, out=None, dist=None, wide=False, splits=0):
+        """The nearest centroid of every row of ``desc`` float32 ``[n, width]`` (rem2d_cvt_assign; on a CPU archive ``assign_host``,
+        the same definition in numpy): returns ``out`` int32 ``[n]`` (made if None), -1 for a row with no finite distance;
+        ``dist`` float32 ``[n]``, if given, receives the squared distances (+inf beside -1).  ``splits``: the launch shape (0: the
+        library's choice); no result depends on it."""
+        out, self._vscratch = _assign("assign", desc, self.centroids, out, dist, self._vscratch, wide, splits)
+        return out
+
+    def insert(self, policy, fitness, desc, mask=None, group_size=None, wide=False):
+        """``EliteGrid.insert`` with the nearest centroid as the cell (rem2d_cvt_insert): the same arguments, checks and return.
+        A row is admitted iff it has a finite distance to some centroid, its fitness is not a NaN and the mask admits it;
+        ``self.cell`` int32 ``[G]`` holds the cells (-1: not admitted), ``self.dist`` float32 ``[G]`` every row's squared distance."""
+        dev = self.device
+        self._fits("insert", policy)
+        G = policy.n_sets
+        if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
+            raise ValueError("insert: fitness must be a torch.float64 tensor")
+        if tuple(fitness.shape) != (G,) or not fitness.is_contiguous() or fitness.device != dev:
+            raise ValueError("insert: fitness must be a contiguous tensor of one entry per weight set [%d] on %s, not %s" % (G, dev, list(fitness.shape)))
+        if not isinstance(desc, torch.Tensor) or desc.dtype != torch.float32:
+            raise ValueError("insert: desc must be a torch.float32 tensor")
+        if tuple(desc.shape) != (G, self.width) or not desc.is_contiguous() or desc.device != dev:
+            raise ValueError("insert: desc must be a contiguous tensor [%d, %d] on %s, not %s" % (G, self.width, dev, list(desc.shape)))
+        if group_size is None:
+            if G % self.n_blocks:
+                raise ValueError("insert: %d rows are not %d blocks of one group_size" % (G, self.n_blocks))
+            group_size = G // self.n_blocks
+        S = int(group_size)
+        if S < 1 or S * self.n_blocks != G:
+            raise ValueError("insert: %d rows in groups of %r are not the archive's %d blocks" % (G, group_size, self.n_blocks))
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("insert: mask must be a torch.bool or torch.uint8 tensor")
+            if tuple(mask.shape) != (G,) or not mask.is_contiguous() or mask.device != dev:
+                raise ValueError("insert: mask must be a contiguous tensor of one entry per row [%d] on %s, not %s" % (G, dev, list(mask.shape)))
+        for name, other in (("fitness", self.fitness), ("desc", self.desc), ("count", self.count), ("w1", self.w1), ("b1", self.b1),
+                            ("w2", self.w2), ("b2", self.b2), ("centroids", self.centroids)):
+            a, an = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
+            b, bn = desc.data_ptr(), desc.data_ptr() + desc.numel() * 4
+            if a < bn and b < an:
+                raise ValueError("insert: desc shares memory with the archive's %s" % name)
+        if dev.type != "cuda":
+            raise ValueError("insert: the archive is on %s; make it on the GPU (device=...)" % dev)
+        if self.cell is None or tuple(self.cell.shape) != (G,):
+            self.cell = torch.empty(G, dtype=torch.int32, device=dev)
+        if self.dist is None or tuple(self.dist.shape) != (G,):
+            self.dist = torch.empty(G, dtype=torch.float32, device=dev)
+        need = (12 * self.n_blocks * self.n_cells + 8 * G + 7) // 8
+        if self._vscratch is None or self._vscratch.numel() < need:
+            self._vscratch = torch.empty(need, dtype=torch.int64, device=dev)
+        v = self._line_descriptor(0, 0, 0.0, 0.0)
+        v.group_size = S
+        v.centroids, v.desc, v.fitness, v.mask = self.centroids.data_ptr(), desc.data_ptr(), fitness.data_ptr(), None if mask is None else mask.data_ptr()
+        v.w1, v.b1, v.w2, v.b2 = (t.data_ptr() for t in (policy.w1, policy.b1, policy.w2, policy.b2))
+        v.cell, v.dist = self.cell.data_ptr(), self.dist.data_ptr()
+        v.scratch, v.scratch_bytes = self._vscratch.data_ptr(), self._vscratch.numel() * 8
+        self._keep = (policy, fitness, desc, mask)          # (the tensors the queued kernels read)
+        self._call_cvt("rem2d_cvt_insert", v, wide)
+        return self.winner
+
+
+def cvt_centroids(n_cells, lo, hi, n_samples=None, iterations=10, seed=0, device=None, wide=False):
+    """Centroids of a centroidal Voronoi tessellation of the box ``[lo, hi)`` (one pair per descriptor word), by Lloyd's algorithm
+    (Vassiliades et al. 2018): ``n_samples`` points (default 64 per cell) drawn uniformly in the box from
+    ``numpy.random.Generator(PCG64(seed))`` as binary32; the start is the first ``n_cells`` points; each of ``iterations`` rounds
+    assigns every point to its nearest centroid -- ``rem2d_cvt_assign`` where ``device`` is a GPU, ``assign_host`` otherwise: one
+    definition, the same bits -- and moves every centroid to the mean of its points, accumulated on the host in binary64 in
+    ascending point order and rounded to binary32; a centroid without points stays.  Returns float32 ``[n_cells, width]`` on
+    ``device`` (default: the CPU), a function of the arguments alone, the same on both routes."""
+    C_ = int(n_cells)
+    lo32, hi32 = np.atleast_1d(np.asarray(lo, np.float32)), np.atleast_1d(np.asarray(hi, np.float32))
+    if lo32.ndim != 1 or lo32.shape != hi32.shape or not 1 <= lo32.shape[0] <= _lib.CVT_MAX_WIDTH:
+        raise ValueError("cvt_centroids: lo and hi must be two sequences of 1 .. %d words" % _lib.CVT_MAX_WIDTH)
+    if not np.isfinite(lo32).all() or not np.isfinite(hi32).all() or not (hi32 > lo32).all() or not np.isfinite(hi32 - lo32).all():
+        raise ValueError("cvt_centroids: lo and hi must be finite binary32 values with lo < hi")
+    if not 1 <= C_ <= _lib.CVT_MAX_CELLS:
+        raise ValueError("cvt_centroids: n_cells must be 1 .. %d, not %r" % (_lib.CVT_MAX_CELLS, n_cells))
+    n = 64 * C_ if n_samples is None else int(n_samples)
+    if n < C_ or n > 2 ** 31 - 1:
+        raise ValueError("cvt_centroids: n_samples must be n_cells .. 2^31 - 1, not %r" % (n_samples,))
+    if int(iterations) < 0:
+        raise ValueError("cvt_centroids: iterations must not be negative")
+    B = lo32.shape[0]
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    pts = (lo32 + rng.random((n, B), dtype=np.float32) * (hi32 - lo32)).astype(np.float32)
+    pts = np.where(pts >= hi32, np.nextafter(hi32, lo32), pts).astype(np.float32)      # (a product rounded up to hi: still inside)
+    cen = pts[:C_].copy()
+    dev = torch.zeros(0, device="cpu" if device is None else device).device
+    on_gpu = dev.type == "cuda"
+    if on_gpu:
+        pts_d, cen_d = torch.from_numpy(pts).to(dev), torch.empty((C_, B), dtype=torch.float32, device=dev)
+        cell_d, scratch = torch.empty(n, dtype=torch.int32, device=dev), None
+    pts64 = pts.astype(np.float64)
+    for _ in range(int(iterations)):
+        if on_gpu:
+            cen_d.copy_(torch.from_numpy(cen))
+            cell_d, scratch = _assign("cvt_centroids", pts_d, cen_d, cell_d, None, scratch, wide)
+            cell = cell_d.cpu().numpy()
+        else:
+            cell = assign_host(pts, cen)[0]
+        ok = cell >= 0
+        members = np.bincount(cell[ok], minlength=C_)
+        for i in range(B):                                     # (bincount adds in ascending point order, in binary64)
+            total = np.bincount(cell[ok], weights=pts64[ok, i], minlength=C_)
+            with np.errstate(all="ignore"):
+                cen[:, i] = np.where(members > 0, (total / members).astype(np.float32), cen[:, i])
+    return torch.from_numpy(cen).to(dev)

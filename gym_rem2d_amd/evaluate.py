@@ -603,7 +603,7 @@ def run_policy_nslc(env, policy, n_generations, archive, k=15, rate=0.02, period
 
 
 def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples=4, seed=0, rate=0.05, sigma=0.1, group_size=None,
-                          max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None):
+                          max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None, sigma_line=None):
     """MAP-Elites for device policies: ``grid`` (an ``elites.EliteGrid`` of M = n_envs / ``group_size`` blocks over descriptor rows
     of ``2 * samples`` words on the env's device) keeps, per block of consecutive creatures -- a morphology -- and per cell of
     behaviour space, the best controller seen so far.  Generation 0 evaluates ``policy`` (one weight set per creature of ``env``,
@@ -615,7 +615,11 @@ def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples
     ``policy`` itself is never written.  Returns ``(grid, fitness, history)``: the last generation's fitness (float64 [N] on the
     device) and rows ``(gen, min, max, mean, filled cells, qd_score)``, generation 0's included, the only numbers that leave the
     device.  ``on_generation(gen, children, fitness, behaviour, grid)``, if given, is called after every insert with the tensors
-    themselves (clone what must last).  Like ``describe`` it raises under auto-reset or streaming."""
+    themselves (clone what must last).  Like ``describe`` it raises under auto-reset or streaming.
+
+    ``grid`` may be an ``elites.CentroidArchive`` over rows of ``2 * samples`` words: insertion is then by nearest centroid.
+    ``sigma_line``: None is the emission above; a float switches it to ``grid.emit_line(sigma_iso=sigma, sigma_line=sigma_line)``,
+    the iso+line variation between two elites, which moves every element: ``rate`` is then unused."""
     from .elites import EliteGrid
     if not isinstance(grid, EliteGrid):
         raise ValueError("run_policy_map_elites: grid must be an elites.EliteGrid")
@@ -643,7 +647,10 @@ def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples
         if gen > 0:
             if children is policy:      # the one child buffer, made of the caller's sets: what a still empty block runs again
                 children = policy._like(policy.w1.clone(), policy.b1.clone(), policy.w2.clone(), policy.b2.clone(), None)
-            grid.emit(gen, seed=seed, rate=rate, sigma=sigma, n_children=n, out=children)
+            if sigma_line is None:
+                grid.emit(gen, seed=seed, rate=rate, sigma=sigma, n_children=n, out=children)
+            else:
+                grid.emit_line(gen, seed=seed, sigma_iso=sigma, sigma_line=float(sigma_line), n_children=n, out=children)
             env.reset_where(mask=everyone)
         env.set_policy(children)
         fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
