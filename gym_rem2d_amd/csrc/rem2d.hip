@@ -1863,6 +1863,122 @@ extern "C" int rem2d_worlds_refill(rem2d_world *const *worlds, const rem2d_morph
     return REM2D_OK;
 }
 
+// ---- what the search tiers below share on the host: net shapes, buffer spans, scratch, launches ----
+#define OK_TRY(expr) \
+    do { const int rc_ = (expr); if (rc_ != REM2D_OK) return rc_; } while (0)
+// The w1 / b1 / w2 / b2 members of a descriptor whose names begin with `pre` (which may be empty): the initialiser of an array of four.
+#define QUAD(e, pre) {(e)->pre##w1, (e)->pre##b1, (e)->pre##w2, (e)->pre##b2}
+static const char *const kNet[4] = {"w1", "b1", "w2", "b2"};
+// The three refusals of a net's shape; `s` prefixes the message.
+static int net_ok(const std::string &s, int d, int hidden, int max_bodies) {
+    if (max_bodies < 1 || max_bodies > REM2D_CONTROL_MAX_BODIES)
+        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(max_bodies));
+    if (hidden < 1 || hidden > REM2D_POLICY_MAX_HIDDEN)
+        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(hidden));
+    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * max_bodies;
+    if (d < d0 || d > d0 + REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
+                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(d));
+    return REM2D_OK;
+}
+// Words of one set of w1, b1, w2, b2 of a net whose shape is good.
+struct Net {
+    size_t len[4];
+    Net(int d, int hidden, int max_bodies) : len{(size_t)d * (size_t)hidden, (size_t)hidden, (size_t)hidden * (size_t)max_bodies, (size_t)max_bodies} {}
+};
+// A buffer as a validator sees it; a message names it `pre` `name`.
+struct Span {
+    uintptr_t at;
+    size_t bytes;
+    const char *pre, *name;
+};
+static Span span(const void *p, size_t bytes, const char *name) { return {(uintptr_t)p, bytes, "", name}; }
+// The four arrays of a family, `sets` sets each, into to[0 .. 3]; false where one of them is NULL.
+static bool add4(Span *to, const float *const (&p)[4], const char *pre, size_t sets, const Net &N) {
+    for (int k = 0; k < 4; ++k) {
+        if (!p[k]) return false;
+        to[k] = {(uintptr_t)p[k], sets * N.len[k] * sizeof(float), pre, kNet[k]};
+    }
+    return true;
+}
+static bool meet(const Span &a, const Span &b) { return a.at < b.at + b.bytes && b.at < a.at + a.bytes; }
+// Refuses the first of a[0] with b[0], a[0] with b[1], ..., a[1] with b[0], ... that meet.  Which pairs a tier hands in is the tier's rule.
+static int apart(const std::string &s, const Span *a, int na, const Span *b, int nb) {
+    for (int i = 0; i < na; ++i)
+        for (int j = 0; j < nb; ++j)
+            if (meet(a[i], b[j])) {
+                std::string m;
+                m.reserve(s.size() + 64); // the whole message in one allocation
+                m.append(s);
+                if (*a[i].pre) m.append(a[i].pre);
+                m.append(a[i].name).append(" overlaps ");
+                if (*b[j].pre) m.append(b[j].pre);
+                return fail(REM2D_E_INVALID, m.append(b[j].name));
+            }
+    return REM2D_OK;
+}
+static int scratch_ok(const std::string &s, const void *scratch, uint64_t have, size_t need) {
+    if (!scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
+    if ((uintptr_t)scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
+    if (have < (uint64_t)need) return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(have) + " bytes, " + std::to_string(need) + " are needed");
+    return REM2D_OK;
+}
+// 16-byte accesses where a set of the array is whole float4s and both bases are aligned (every set's base then is too)
+static int vec_ok(size_t len, const void *a, const void *b) { return len % 4 == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0; }
+static void seed_keys(uint64_t seed, unsigned &key0, unsigned &key1) {
+    key0 = (unsigned)(seed & 0xffffffffull);
+    key1 = (unsigned)(seed >> 32);
+}
+template <typename T, typename U> static void set4(T (&to)[4], U *const (&from)[4]) {
+    for (int k = 0; k < 4; ++k) to[k] = from[k];
+}
+// len, src, dst and vec of a kernel that copies or varies sets of `src` into `dst` (EvolveArgs, CvLine).
+template <typename A> static void quads(A &X, const Net &N, const float *const (&src)[4], float *const (&dst)[4]) {
+    for (int k = 0; k < 4; ++k) {
+        X.len[k] = (int)N.len[k];
+        X.src[k] = src[k];
+        X.dst[k] = dst[k];
+        X.vec[k] = vec_ok(N.len[k], src[k], dst[k]);
+    }
+}
+enum { ES_MAX_GRID = 1 << 24 }; // workgroups of one launch; what lies beyond goes into further launches
+// `items` workgroups of one wavefront of one kernel, ES_MAX_GRID of them per launch, each launch told its first item in `itemBase`
+// (a member of `args`).
+template <typename K, typename A> static int launch_items(K kernel, long long items, A &args, long long &itemBase, hipStream_t st) {
+    for (long long base = 0; base < items; base += ES_MAX_GRID) {
+        const long long n = items - base < (long long)ES_MAX_GRID ? items - base : (long long)ES_MAX_GRID;
+        itemBase = base;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(WAVE), 0, st, args);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+// An insertion into an elite grid on `st`: clear, the tier's key kernel on its own arguments, row, commit.  L holds the rows, the grid
+// and the scratch's key | row; the sets of `src` go to `elite`.  (The key kernel's grid is sized by EL_TILE whichever tier's it
+// is: the cvt section's static_assert(CV_TILE == EL_TILE) is what allows that.)
+template <typename K, typename KA>
+static int insert_launch(K key_kernel, const KA &key_args, const ElArgs &L, const Net &N, const float *const (&src)[4], float *const (&elite)[4], hipStream_t st) {
+    const long long G = (long long)L.M * (long long)L.S, slots = (long long)L.M * (long long)L.C;
+    EvolveArgs E;
+    memset(&E, 0, sizeof(E));
+    quads(E, N, src, elite);
+    hipLaunchKernelGGL(rem2d_elites_clear_kernel, dim3((unsigned)((slots + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, L);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(key_kernel, dim3((unsigned)((G + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, key_args);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rem2d_elites_row_kernel, dim3((unsigned)((G + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, L);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rem2d_elites_commit_kernel, dim3((unsigned)slots), dim3(WAVE), 0, st, L, E);
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
+}
+// An entry point: the tier's check of the descriptor for `stages`, then its launch of them.
+template <typename D>
+static int run(int (*ok)(const char *, const D *, int), int (*launch)(const D *, int, hipStream_t), const char *what, const D *e, int stages, void *stream) {
+    OK_TRY(ok(what, e, stages));
+    return launch(e, stages, (hipStream_t)stream);
+}
+
 // ---- evolving device policies (include/rem2d_evolve.h, csrc/rem2d_evolve.h) ----
 extern "C" int rem2d_evolve_abi_version(void) { return REM2D_EVOLVE_ABI_VERSION; }
 enum { EVOLVE_SELECT = 1, EVOLVE_VARY = 2 };
@@ -1870,14 +1986,7 @@ enum { EVOLVE_SELECT = 1, EVOLVE_VARY = 2 };
 static int evolve_ok(const char *what, const rem2d_evolve *e, int stages) {
     const std::string s = std::string(what) + ": ";
     if (!e) return fail(REM2D_E_INVALID, s + "NULL descriptor");
-    if (e->max_bodies < 1 || e->max_bodies > REM2D_CONTROL_MAX_BODIES)
-        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(e->max_bodies));
-    if (e->hidden < 1 || e->hidden > REM2D_POLICY_MAX_HIDDEN)
-        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(e->hidden));
-    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * e->max_bodies;
-    if (e->d < d0 || e->d > d0 + REM2D_SENSE_MAX_RAYS)
-        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
-                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(e->d));
+    OK_TRY(net_ok(s, e->d, e->hidden, e->max_bodies));
     if (e->n_sets < 1) return fail(REM2D_E_INVALID, s + "n_sets must be at least 1");
     if (e->group_size < 1 || e->n_sets % e->group_size != 0)
         return fail(REM2D_E_INVALID, s + "group_size must be a divisor of n_sets (" + std::to_string(e->n_sets) + "), not " + std::to_string(e->group_size));
@@ -1888,32 +1997,21 @@ static int evolve_ok(const char *what, const rem2d_evolve *e, int stages) {
     if (!e->parent) return fail(REM2D_E_INVALID, s + "NULL device pointer (parent)");
     if ((stages & EVOLVE_SELECT) && !e->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
     if (stages & EVOLVE_VARY) {
-        const float *src[4] = {e->w1, e->b1, e->w2, e->b2};
-        const float *dst[4] = {e->child_w1, e->child_b1, e->child_w2, e->child_b2};
-        const char *const name[4] = {"w1", "b1", "w2", "b2"};
-        const size_t len[4] = {(size_t)e->d * (size_t)e->hidden, (size_t)e->hidden, (size_t)e->hidden * (size_t)e->max_bodies, (size_t)e->max_bodies};
-        for (int k = 0; k < 4; ++k)
-            if (!src[k] || !dst[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
-        for (int k = 0; k < 4; ++k)
-            for (int j = 0; j < 4; ++j) {
-                const uintptr_t a = (uintptr_t)dst[k], an = a + (uintptr_t)e->n_sets * len[k] * sizeof(float);
-                const uintptr_t b = (uintptr_t)src[j], bn = b + (uintptr_t)e->n_sets * len[j] * sizeof(float);
-                if (a < bn && b < an) return fail(REM2D_E_INVALID, s + "child_" + name[k] + " overlaps the parents' " + name[j]);
-            }
+        const Net N(e->d, e->hidden, e->max_bodies);
+        Span src[4], dst[4];
+        if (!add4(src, QUAD(e, ), "the parents' ", (size_t)e->n_sets, N) || !add4(dst, QUAD(e, child_), "child_", (size_t)e->n_sets, N))
+            return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        OK_TRY(apart(s, dst, 4, src, 4));
     }
     return REM2D_OK;
 }
 static void evolve_args(EvolveArgs &A, const rem2d_evolve *e) {
     memset(&A, 0, sizeof(A));
     A.fitness = e->fitness;
-    A.src[0] = e->w1; A.src[1] = e->b1; A.src[2] = e->w2; A.src[3] = e->b2;
-    A.dst[0] = e->child_w1; A.dst[1] = e->child_b1; A.dst[2] = e->child_w2; A.dst[3] = e->child_b2;
+    quads(A, Net(e->d, e->hidden, e->max_bodies), QUAD(e, ), QUAD(e, child_));
     A.parent = e->parent;
     A.rateThreshold = e->rate_threshold;
-    A.key0 = (unsigned)(e->seed & 0xffffffffull); A.key1 = (unsigned)(e->seed >> 32); A.generation = e->generation;
-    A.len[0] = e->d * e->hidden; A.len[1] = e->hidden; A.len[2] = e->hidden * e->max_bodies; A.len[3] = e->max_bodies;
-    // 16-byte accesses where a set of the array is whole float4s and both bases are aligned (every set's base then is too)
-    for (int k = 0; k < 4; ++k) A.vec[k] = A.len[k] % 4 == 0 && (uintptr_t)A.src[k] % 16 == 0 && (uintptr_t)A.dst[k] % 16 == 0;
+    seed_keys(e->seed, A.key0, A.key1); A.generation = e->generation;
     A.G = e->n_sets; A.S = e->group_size; A.T = e->tournsize; A.elite = e->elite;
     A.sigma = e->sigma;
 }
@@ -1931,37 +2029,29 @@ static int evolve_launch(const rem2d_evolve *e, int stages, hipStream_t st) {
     }
     return REM2D_OK;
 }
-extern "C" int rem2d_policy_select(const rem2d_evolve *e, void *stream) {
-    const int rc = evolve_ok("select", e, EVOLVE_SELECT);
-    if (rc != REM2D_OK) return rc;
-    return evolve_launch(e, EVOLVE_SELECT, (hipStream_t)stream);
-}
-extern "C" int rem2d_policy_vary(const rem2d_evolve *e, void *stream) {
-    const int rc = evolve_ok("vary", e, EVOLVE_VARY);
-    if (rc != REM2D_OK) return rc;
-    return evolve_launch(e, EVOLVE_VARY, (hipStream_t)stream);
-}
-extern "C" int rem2d_policy_evolve(const rem2d_evolve *e, void *stream) {
-    const int rc = evolve_ok("evolve", e, EVOLVE_SELECT | EVOLVE_VARY);
-    if (rc != REM2D_OK) return rc;
-    return evolve_launch(e, EVOLVE_SELECT | EVOLVE_VARY, (hipStream_t)stream);
-}
+extern "C" int rem2d_policy_select(const rem2d_evolve *e, void *stream) { return run(evolve_ok, evolve_launch, "select", e, EVOLVE_SELECT, stream); }
+extern "C" int rem2d_policy_vary(const rem2d_evolve *e, void *stream) { return run(evolve_ok, evolve_launch, "vary", e, EVOLVE_VARY, stream); }
+extern "C" int rem2d_policy_evolve(const rem2d_evolve *e, void *stream) { return run(evolve_ok, evolve_launch, "evolve", e, EVOLVE_SELECT | EVOLVE_VARY, stream); }
 
 // ---- an evolution strategy for device policies (include/rem2d_es.h, csrc/rem2d_es.h) ----
 extern "C" int rem2d_es_abi_version(void) { return REM2D_ES_ABI_VERSION; }
 enum { ES_SAMPLE = 1, ES_SHAPE = 2, ES_UPDATE = 4 };
-enum { ES_MAX_GRID = 1 << 24 }; // workgroups of one launch; what lies beyond goes into further launches
-// The split of a block's pairs for a descriptor whose shapes are good: pairs per wavefront and chunks per block.
-static void es_split(const rem2d_es *e, int &pairChunk, int &nChunks) {
-    const long long P = e->group_size / 2;
-    long long chunk = e->pair_chunk;
+// The shapes of an es or an snes descriptor: what their checks, the split and the scratch's size read.
+struct EsShape {
+    int d, hidden, max_bodies, n_means, group_size, pair_chunk;
+};
+template <typename D> static EsShape es_shape(const D *e) { return {e->d, e->hidden, e->max_bodies, e->n_means, e->group_size, e->pair_chunk}; }
+// The split of a block's pairs for shapes that are good: pairs per wavefront and chunks per block.
+static void es_split(const EsShape &X, int &pairChunk, int &nChunks) {
+    const long long P = X.group_size / 2;
+    long long chunk = X.pair_chunk;
     if (chunk == 0) {
         // the library's choice: no split while the blocks alone fill the machine or a block is short; otherwise chunks of at
         // least 64 pairs, as many as bring the launch to about 4096 wavefronts
-        const long long lens[4] = {(long long)e->d * e->hidden, e->hidden, (long long)e->hidden * e->max_bodies, e->max_bodies};
+        const Net N(X.d, X.hidden, X.max_bodies);
         long long W = 0;
-        for (int k = 0; k < 4; ++k) W += (lens[k] + WAVE - 1) / WAVE;
-        const long long waves = W * (long long)e->n_means;
+        for (int k = 0; k < 4; ++k) W += ((long long)N.len[k] + WAVE - 1) / WAVE;
+        const long long waves = W * (long long)X.n_means;
         chunk = P;
         if (waves < 1024 && P > 64) {
             const long long want = (4096 + waves - 1) / waves;
@@ -1973,300 +2063,193 @@ static void es_split(const rem2d_es *e, int &pairChunk, int &nChunks) {
     pairChunk = (int)chunk;
     nChunks = (int)((P + chunk - 1) / chunk);
 }
-// Checks the shapes and parameters of an es descriptor; `what` prefixes the message.  No pointer is looked at.
+// Checks the shapes es and snes share; `s` prefixes the message.
+static int es_shape_ok(const std::string &s, const EsShape &X) {
+    OK_TRY(net_ok(s, X.d, X.hidden, X.max_bodies));
+    if (X.n_means < 1) return fail(REM2D_E_INVALID, s + "n_means must be at least 1");
+    if (X.group_size < 2 || X.group_size % 2 != 0)
+        return fail(REM2D_E_INVALID, s + "group_size must be even and at least 2, not " + std::to_string(X.group_size));
+    if ((long long)X.n_means * (long long)X.group_size > 2147483647ll)
+        return fail(REM2D_E_INVALID, s + "n_means * group_size must be at most 2^31 - 1");
+    if (X.pair_chunk < 0) return fail(REM2D_E_INVALID, s + "pair_chunk must be at least 0, not " + std::to_string(X.pair_chunk));
+    return REM2D_OK;
+}
+// Checks the shapes and parameters of an es descriptor; `s` prefixes the message.  No pointer is looked at.
 static int es_shapes_ok(const std::string &s, const rem2d_es *e) {
     if (!e) return fail(REM2D_E_INVALID, s + "NULL descriptor");
-    if (e->max_bodies < 1 || e->max_bodies > REM2D_CONTROL_MAX_BODIES)
-        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(e->max_bodies));
-    if (e->hidden < 1 || e->hidden > REM2D_POLICY_MAX_HIDDEN)
-        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(e->hidden));
-    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * e->max_bodies;
-    if (e->d < d0 || e->d > d0 + REM2D_SENSE_MAX_RAYS)
-        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
-                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(e->d));
-    if (e->n_means < 1) return fail(REM2D_E_INVALID, s + "n_means must be at least 1");
-    if (e->group_size < 2 || e->group_size % 2 != 0)
-        return fail(REM2D_E_INVALID, s + "group_size must be even and at least 2, not " + std::to_string(e->group_size));
-    if ((long long)e->n_means * (long long)e->group_size > 2147483647ll)
-        return fail(REM2D_E_INVALID, s + "n_means * group_size must be at most 2^31 - 1");
-    if (e->pair_chunk < 0) return fail(REM2D_E_INVALID, s + "pair_chunk must be at least 0, not " + std::to_string(e->pair_chunk));
+    OK_TRY(es_shape_ok(s, es_shape(e)));
     if (e->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0");
     return REM2D_OK;
 }
-static size_t es_scratch_need(const rem2d_es *e) {
+static size_t es_scratch_need(const EsShape &X) {
     int pairChunk, nChunks;
-    es_split(e, pairChunk, nChunks);
+    es_split(X, pairChunk, nChunks);
     if (nChunks == 1) return 0;
-    const size_t E = (size_t)e->d * e->hidden + (size_t)e->hidden + (size_t)e->hidden * e->max_bodies + (size_t)e->max_bodies;
-    return (size_t)e->n_means * (size_t)nChunks * E * sizeof(long long);
+    const Net N(X.d, X.hidden, X.max_bodies);
+    return (size_t)X.n_means * (size_t)nChunks * (N.len[0] + N.len[1] + N.len[2] + N.len[3]) * sizeof(long long);
 }
 // Checks an es descriptor for the calls in `stages`.  Nothing it points to is read.
 static int es_ok(const char *what, const rem2d_es *e, int stages) {
     const std::string s = std::string(what) + ": ";
-    const int rc = es_shapes_ok(s, e);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(es_shapes_ok(s, e));
     if ((stages & ES_SHAPE) && !e->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
     if ((stages & (ES_SHAPE | ES_UPDATE)) && !e->util) return fail(REM2D_E_INVALID, s + "NULL device pointer (util)");
-    const float *mean[4] = {e->w1, e->b1, e->w2, e->b2};
-    const char *const name[4] = {"w1", "b1", "w2", "b2"};
-    const size_t len[4] = {(size_t)e->d * (size_t)e->hidden, (size_t)e->hidden, (size_t)e->hidden * (size_t)e->max_bodies, (size_t)e->max_bodies};
-    for (int pass = 0; pass < 2; ++pass) {
-        if (!(stages & (pass == 0 ? ES_SAMPLE : ES_UPDATE))) continue;
-        const float *dst[4] = {pass == 0 ? e->child_w1 : e->new_w1, pass == 0 ? e->child_b1 : e->new_b1,
-                               pass == 0 ? e->child_w2 : e->new_w2, pass == 0 ? e->child_b2 : e->new_b2};
-        const size_t sets = pass == 0 ? (size_t)e->n_means * (size_t)e->group_size : (size_t)e->n_means;
-        for (int k = 0; k < 4; ++k)
-            if (!mean[k] || !dst[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
-        for (int k = 0; k < 4; ++k)
-            for (int j = 0; j < 4; ++j) {
-                const uintptr_t a = (uintptr_t)dst[k], an = a + (uintptr_t)(sets * len[k] * sizeof(float));
-                const uintptr_t b = (uintptr_t)mean[j], bn = b + (uintptr_t)((size_t)e->n_means * len[j] * sizeof(float));
-                if (a < bn && b < an) return fail(REM2D_E_INVALID, s + (pass == 0 ? "child_" : "new_") + name[k] + " overlaps the mean's " + name[j]);
-            }
+    const Net N(e->d, e->hidden, e->max_bodies);
+    const size_t M = (size_t)e->n_means, G = M * (size_t)e->group_size;
+    // each destination against the mean, and against nothing else
+    const struct { int stage; const float *p[4]; const char *pre; size_t sets; } outs[2] = {
+        {ES_SAMPLE, QUAD(e, child_), "child_", G}, {ES_UPDATE, QUAD(e, new_), "new_", M}};
+    Span mean[4], dst[4];
+    const bool have = add4(mean, QUAD(e, ), "the mean's ", M, N);
+    for (const auto &o : outs) {
+        if (!(stages & o.stage)) continue;
+        if (!have || !add4(dst, o.p, o.pre, o.sets, N)) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        OK_TRY(apart(s, dst, 4, mean, 4));
     }
     if (stages & ES_UPDATE) {
-        const size_t need = es_scratch_need(e);
-        if (need != 0) {
-            if (!e->scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
-            if ((uintptr_t)e->scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
-            if (e->scratch_bytes < (uint64_t)need)
-                return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(e->scratch_bytes) + " bytes, " + std::to_string(need) + " are needed");
-        }
+        const size_t need = es_scratch_need(es_shape(e));
+        if (need != 0) OK_TRY(scratch_ok(s, e->scratch, e->scratch_bytes, need));
     }
     return REM2D_OK;
 }
-static void es_args(EsArgs &A, const rem2d_es *e) {
+// What es and snes hand their kernels alike, from either descriptor: all of EsArgs but sigma and step.
+template <typename D> static void es_args(EsArgs &A, const D *e) {
     memset(&A, 0, sizeof(A));
     A.fitness = e->fitness;
     A.util = e->util;
-    A.mean[0] = e->w1; A.mean[1] = e->b1; A.mean[2] = e->w2; A.mean[3] = e->b2;
-    A.child[0] = e->child_w1; A.child[1] = e->child_b1; A.child[2] = e->child_w2; A.child[3] = e->child_b2;
-    A.next[0] = e->new_w1; A.next[1] = e->new_b1; A.next[2] = e->new_w2; A.next[3] = e->new_b2;
+    set4(A.mean, QUAD(e, )); set4(A.child, QUAD(e, child_)); set4(A.next, QUAD(e, new_));
     A.scratch = (long long *)e->scratch;
-    A.key0 = (unsigned)(e->seed & 0xffffffffull); A.key1 = (unsigned)(e->seed >> 32); A.generation = e->generation;
-    A.len[0] = e->d * e->hidden; A.len[1] = e->hidden; A.len[2] = e->hidden * e->max_bodies; A.len[3] = e->max_bodies;
+    seed_keys(e->seed, A.key0, A.key1); A.generation = e->generation;
+    const Net N(e->d, e->hidden, e->max_bodies);
     for (int k = 0; k < 4; ++k) {
-        // 16-byte accesses where a set of the array is whole float4s and both bases are aligned (every set's base then is too)
-        A.vec[k] = A.len[k] % 4 == 0 && (uintptr_t)A.mean[k] % 16 == 0 && (uintptr_t)A.child[k] % 16 == 0;
+        A.len[k] = (int)N.len[k];
+        A.vec[k] = vec_ok(N.len[k], A.mean[k], A.child[k]);
         A.slots[k] = (A.len[k] + WAVE - 1) / WAVE;
         A.off[k] = A.E;
         A.W += A.slots[k];
         A.E += A.len[k];
     }
     A.M = e->n_means; A.S = e->group_size;
-    es_split(e, A.pairChunk, A.nChunks);
-    A.sigma = e->sigma; A.step = e->step;
-}
-// `items` workgroups of `threads` threads of one kernel, ES_MAX_GRID of them per launch, each launch told its first item.
-template <typename K> static int es_launch_items(K kernel, long long items, int threads, EsArgs &A, hipStream_t st) {
-    for (long long base = 0; base < items; base += ES_MAX_GRID) {
-        const long long n = items - base < (long long)ES_MAX_GRID ? items - base : (long long)ES_MAX_GRID;
-        A.itemBase = base;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3((unsigned)threads), 0, st, A);
-        HIP_TRY(hipGetLastError());
-    }
-    return REM2D_OK;
+    es_split(es_shape(e), A.pairChunk, A.nChunks);
 }
 // The stages of a checked descriptor on `st`.
 static int es_launch(const rem2d_es *e, int stages, hipStream_t st) {
     EsArgs A;
     es_args(A, e);
+    A.sigma = e->sigma; A.step = e->step;
     const long long G = (long long)A.M * (long long)A.S;
-    int rc = REM2D_OK;
-    if (stages & ES_SAMPLE) rc = es_launch_items(rem2d_es_sample_kernel, G / 2, WAVE, A, st);
-    if (rc == REM2D_OK && (stages & ES_SHAPE)) {
+    if (stages & ES_SAMPLE) OK_TRY(launch_items(rem2d_es_sample_kernel, G / 2, A, A.itemBase, st));
+    if (stages & ES_SHAPE) {
         A.itemBase = 0; // (ceil(G / ES_TILE) < 2^23 workgroups: one launch)
         hipLaunchKernelGGL(rem2d_es_shape_kernel, dim3((unsigned)((G + ES_TILE - 1) / ES_TILE)), dim3(ES_TILE), 0, st, A);
         HIP_TRY(hipGetLastError());
     }
-    if (rc == REM2D_OK && (stages & ES_UPDATE)) {
-        rc = es_launch_items(rem2d_es_update_kernel, (long long)A.M * (long long)A.nChunks * (long long)A.W, WAVE, A, st);
-        if (rc == REM2D_OK && A.nChunks > 1) rc = es_launch_items(rem2d_es_finish_kernel, (long long)A.M * (long long)A.W, WAVE, A, st);
+    if (stages & ES_UPDATE) {
+        OK_TRY(launch_items(rem2d_es_update_kernel, (long long)A.M * (long long)A.nChunks * (long long)A.W, A, A.itemBase, st));
+        if (A.nChunks > 1) OK_TRY(launch_items(rem2d_es_finish_kernel, (long long)A.M * (long long)A.W, A, A.itemBase, st));
     }
-    return rc;
+    return REM2D_OK;
 }
 extern "C" int64_t rem2d_es_scratch_bytes(const rem2d_es *e) {
-    const int rc = es_shapes_ok("es_scratch_bytes: ", e);
-    if (rc != REM2D_OK) return rc;
-    return (int64_t)es_scratch_need(e);
+    OK_TRY(es_shapes_ok("es_scratch_bytes: ", e));
+    return (int64_t)es_scratch_need(es_shape(e));
 }
-extern "C" int rem2d_es_sample(const rem2d_es *e, void *stream) {
-    const int rc = es_ok("es_sample", e, ES_SAMPLE);
-    if (rc != REM2D_OK) return rc;
-    return es_launch(e, ES_SAMPLE, (hipStream_t)stream);
-}
-extern "C" int rem2d_es_shape(const rem2d_es *e, void *stream) {
-    const int rc = es_ok("es_shape", e, ES_SHAPE);
-    if (rc != REM2D_OK) return rc;
-    return es_launch(e, ES_SHAPE, (hipStream_t)stream);
-}
-extern "C" int rem2d_es_update(const rem2d_es *e, void *stream) {
-    const int rc = es_ok("es_update", e, ES_UPDATE);
-    if (rc != REM2D_OK) return rc;
-    return es_launch(e, ES_UPDATE, (hipStream_t)stream);
-}
-extern "C" int rem2d_es_step(const rem2d_es *e, void *stream) {
-    const int rc = es_ok("es_step", e, ES_SHAPE | ES_UPDATE);
-    if (rc != REM2D_OK) return rc;
-    return es_launch(e, ES_SHAPE | ES_UPDATE, (hipStream_t)stream);
-}
+extern "C" int rem2d_es_sample(const rem2d_es *e, void *stream) { return run(es_ok, es_launch, "es_sample", e, ES_SAMPLE, stream); }
+extern "C" int rem2d_es_shape(const rem2d_es *e, void *stream) { return run(es_ok, es_launch, "es_shape", e, ES_SHAPE, stream); }
+extern "C" int rem2d_es_update(const rem2d_es *e, void *stream) { return run(es_ok, es_launch, "es_update", e, ES_UPDATE, stream); }
+extern "C" int rem2d_es_step(const rem2d_es *e, void *stream) { return run(es_ok, es_launch, "es_step", e, ES_SHAPE | ES_UPDATE, stream); }
 
 // ---- an adaptive evolution strategy for device policies (include/rem2d_snes.h, csrc/rem2d_snes.h) ----
 extern "C" int rem2d_snes_abi_version(void) { return REM2D_SNES_ABI_VERSION; }
 enum { SN_SAMPLE = 1, SN_SHAPE = 2, SN_UPDATE = 4 };
-// The shapes of an snes descriptor as an es descriptor: what es_shapes_ok, es_split and es_args read.  No pointer is set.
-static rem2d_es sn_as_es(const rem2d_snes *e) {
-    rem2d_es x;
-    memset(&x, 0, sizeof(x));
-    x.d = e->d; x.hidden = e->hidden; x.max_bodies = e->max_bodies; x.n_means = e->n_means; x.group_size = e->group_size;
-    x.pair_chunk = e->pair_chunk; x.generation = e->generation; x.seed = e->seed;
-    return x;
-}
-// Checks the shapes and parameters of an snes descriptor; `what` prefixes the message.  No pointer is looked at.
+// Checks the shapes and parameters of an snes descriptor; `s` prefixes the message.  No pointer is looked at.
 static int sn_shapes_ok(const std::string &s, const rem2d_snes *e) {
     if (!e) return fail(REM2D_E_INVALID, s + "NULL descriptor");
-    const rem2d_es x = sn_as_es(e);
-    const int rc = es_shapes_ok(s, &x);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(es_shape_ok(s, es_shape(e)));
     if (e->group_size > REM2D_SNES_MAX_GROUP)
         return fail(REM2D_E_INVALID, s + "group_size must be at most " + std::to_string(REM2D_SNES_MAX_GROUP) + ", not " + std::to_string(e->group_size));
     if (e->flags & ~(REM2D_SNES_ADAM | REM2D_SNES_NATURAL)) return fail(REM2D_E_INVALID, s + "unknown bits in flags: " + std::to_string(e->flags));
     return REM2D_OK;
 }
-static size_t sn_scratch_need(const rem2d_snes *e) {
-    const rem2d_es x = sn_as_es(e);
-    return 2 * es_scratch_need(&x); // two int64 per element per chunk
-}
-struct SnBuf {
-    uintptr_t at;
-    size_t bytes;
-    std::string name;
-};
+static size_t sn_scratch_need(const rem2d_snes *e) { return 2 * es_scratch_need(es_shape(e)); } // two int64 per element per chunk
 // Checks an snes descriptor for the calls in `stages`.  Nothing it points to is read.
 static int sn_ok(const char *what, const rem2d_snes *e, int stages) {
     const std::string s = std::string(what) + ": ";
-    const int rc = sn_shapes_ok(s, e);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(sn_shapes_ok(s, e));
     const bool adam = (e->flags & REM2D_SNES_ADAM) != 0;
     if ((stages & SN_SHAPE) && !e->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
     if ((stages & (SN_SHAPE | SN_UPDATE)) && !e->util) return fail(REM2D_E_INVALID, s + "NULL device pointer (util)");
-    const char *const name[4] = {"w1", "b1", "w2", "b2"};
-    const size_t len[4] = {(size_t)e->d * (size_t)e->hidden, (size_t)e->hidden, (size_t)e->hidden * (size_t)e->max_bodies, (size_t)e->max_bodies};
+    const Net N(e->d, e->hidden, e->max_bodies);
     const size_t M = (size_t)e->n_means, G = M * (size_t)e->group_size;
-    const float *mean[4] = {e->w1, e->b1, e->w2, e->b2}, *sigma[4] = {e->sigma_w1, e->sigma_b1, e->sigma_w2, e->sigma_b2};
-    const float *m1[4] = {e->m1_w1, e->m1_b1, e->m1_w2, e->m1_b2}, *m2[4] = {e->m2_w1, e->m2_b1, e->m2_w2, e->m2_b2};
-    const float *child[4] = {e->child_w1, e->child_b1, e->child_w2, e->child_b2}, *next[4] = {e->new_w1, e->new_b1, e->new_w2, e->new_b2};
-    const float *nsig[4] = {e->new_sigma_w1, e->new_sigma_b1, e->new_sigma_w2, e->new_sigma_b2};
-    const float *nm1[4] = {e->new_m1_w1, e->new_m1_b1, e->new_m1_w2, e->new_m1_b2}, *nm2[4] = {e->new_m2_w1, e->new_m2_b1, e->new_m2_w2, e->new_m2_b2};
-    std::vector<SnBuf> in, out;
-    auto add = [&](std::vector<SnBuf> &to, const float *const *p, const char *prefix, size_t sets) {
-        for (int k = 0; k < 4; ++k) {
-            if (!p[k]) return false;
-            to.push_back({(uintptr_t)p[k], sets * len[k] * sizeof(float), std::string(prefix) + name[k]});
-        }
-        return true;
-    };
-    bool all = add(in, mean, "the mean's ", M) && add(in, sigma, "sigma_", M);
-    if (stages & SN_SAMPLE) all = all && add(out, child, "child_", G);
+    // what the calls read and what they write, in the order the overlaps are looked for
+    Span in[4 * 4 + 2], out[5 * 4 + 1];
+    int ni = 8, no = 0;
+    bool all = add4(in, QUAD(e, ), "the mean's ", M, N) && add4(in + 4, QUAD(e, sigma_), "sigma_", M, N);
+    if (stages & SN_SAMPLE) {
+        all = all && add4(out, QUAD(e, child_), "child_", G, N);
+        no = 4;
+    }
     if (stages & SN_UPDATE) {
-        all = all && add(out, next, "new_", M) && add(out, nsig, "new_sigma_", M);
-        if (adam) all = all && add(in, m1, "m1_", M) && add(in, m2, "m2_", M) && add(out, nm1, "new_m1_", M) && add(out, nm2, "new_m2_", M);
+        all = all && add4(out + no, QUAD(e, new_), "new_", M, N) && add4(out + no + 4, QUAD(e, new_sigma_), "new_sigma_", M, N);
+        no += 8;
+        if (adam) {
+            all = all && add4(in + 8, QUAD(e, m1_), "m1_", M, N) && add4(in + 12, QUAD(e, m2_), "m2_", M, N) &&
+                  add4(out + no, QUAD(e, new_m1_), "new_m1_", M, N) && add4(out + no + 4, QUAD(e, new_m2_), "new_m2_", M, N);
+            ni = 16;
+            no += 8;
+        }
     }
     if (!all) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights or state)");
-    size_t need = 0;
     if (stages & SN_UPDATE) {
         if (!(e->sigma_min > 0.0f) || !(e->sigma_min <= e->sigma_max) || !std::isfinite(e->sigma_min) || !std::isfinite(e->sigma_max))
             return fail(REM2D_E_INVALID, s + "sigma_min and sigma_max must be finite with 0 < sigma_min <= sigma_max");
-        in.push_back({(uintptr_t)e->util, G * sizeof(int32_t), "util"});
-        need = sn_scratch_need(e);
+        in[ni++] = span(e->util, G * sizeof(int32_t), "util");
+        const size_t need = sn_scratch_need(e);
         if (need != 0) {
-            if (!e->scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
-            if ((uintptr_t)e->scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
-            if (e->scratch_bytes < (uint64_t)need)
-                return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(e->scratch_bytes) + " bytes, " + std::to_string(need) + " are needed");
-            out.push_back({(uintptr_t)e->scratch, need, "scratch"});
+            OK_TRY(scratch_ok(s, e->scratch, e->scratch_bytes, need));
+            out[no++] = span(e->scratch, need, "scratch");
         }
     }
-    if ((stages & SN_SHAPE)) in.push_back({(uintptr_t)e->fitness, G * sizeof(double), "fitness"});
-    for (size_t i = 0; i < out.size(); ++i) {
-        for (size_t j = 0; j < in.size(); ++j)
-            if (out[i].at < in[j].at + in[j].bytes && in[j].at < out[i].at + out[i].bytes)
-                return fail(REM2D_E_INVALID, s + out[i].name + " overlaps " + in[j].name);
-        for (size_t j = 0; j < i; ++j)
-            if (out[i].at < out[j].at + out[j].bytes && out[j].at < out[i].at + out[i].bytes)
-                return fail(REM2D_E_INVALID, s + out[i].name + " overlaps " + out[j].name);
-    }
-    return REM2D_OK;
-}
-static void sn_args(SnArgs &B, const rem2d_snes *e) {
-    memset(&B, 0, sizeof(B));
-    rem2d_es x = sn_as_es(e);
-    x.fitness = e->fitness; x.util = e->util;
-    x.w1 = e->w1; x.b1 = e->b1; x.w2 = e->w2; x.b2 = e->b2;
-    x.child_w1 = e->child_w1; x.child_b1 = e->child_b1; x.child_w2 = e->child_w2; x.child_b2 = e->child_b2;
-    x.new_w1 = e->new_w1; x.new_b1 = e->new_b1; x.new_w2 = e->new_w2; x.new_b2 = e->new_b2;
-    x.scratch = e->scratch;
-    es_args(B.es, &x);
-    B.sigma[0] = e->sigma_w1; B.sigma[1] = e->sigma_b1; B.sigma[2] = e->sigma_w2; B.sigma[3] = e->sigma_b2;
-    B.m1[0] = e->m1_w1; B.m1[1] = e->m1_b1; B.m1[2] = e->m1_w2; B.m1[3] = e->m1_b2;
-    B.m2[0] = e->m2_w1; B.m2[1] = e->m2_b1; B.m2[2] = e->m2_w2; B.m2[3] = e->m2_b2;
-    B.nextSigma[0] = e->new_sigma_w1; B.nextSigma[1] = e->new_sigma_b1; B.nextSigma[2] = e->new_sigma_w2; B.nextSigma[3] = e->new_sigma_b2;
-    B.nextM1[0] = e->new_m1_w1; B.nextM1[1] = e->new_m1_b1; B.nextM1[2] = e->new_m1_w2; B.nextM1[3] = e->new_m1_b2;
-    B.nextM2[0] = e->new_m2_w1; B.nextM2[1] = e->new_m2_b1; B.nextM2[2] = e->new_m2_w2; B.nextM2[3] = e->new_m2_b2;
-    for (int k = 0; k < 4; ++k) B.es.vec[k] = B.es.vec[k] && (uintptr_t)B.sigma[k] % 16 == 0; // the third base of the sample
-    B.flags = e->flags;
-    B.mstep = e->mstep; B.sstep = e->sstep; B.beta1 = e->beta1; B.omb1 = e->omb1; B.beta2 = e->beta2; B.omb2 = e->omb2;
-    B.alpha = e->alpha; B.eps = e->eps; B.sigmaMin = e->sigma_min; B.sigmaMax = e->sigma_max;
-}
-// `items` workgroups of one wavefront of one kernel, ES_MAX_GRID of them per launch, each launch told its first item.
-template <typename K> static int sn_launch_items(K kernel, long long items, SnArgs &B, hipStream_t st) {
-    for (long long base = 0; base < items; base += ES_MAX_GRID) {
-        const long long n = items - base < (long long)ES_MAX_GRID ? items - base : (long long)ES_MAX_GRID;
-        B.es.itemBase = base;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(WAVE), 0, st, B);
-        HIP_TRY(hipGetLastError());
+    if (stages & SN_SHAPE) in[ni++] = span(e->fitness, G * sizeof(double), "fitness");
+    // each output against every input, then against the outputs before it
+    for (int i = 0; i < no; ++i) {
+        OK_TRY(apart(s, out + i, 1, in, ni));
+        OK_TRY(apart(s, out + i, 1, out, i));
     }
     return REM2D_OK;
 }
 // The stages of a checked descriptor on `st`.
 static int sn_launch(const rem2d_snes *e, int stages, hipStream_t st) {
     SnArgs B;
-    sn_args(B, e);
+    memset(&B, 0, sizeof(B));
+    es_args(B.es, e);
+    set4(B.sigma, QUAD(e, sigma_)); set4(B.m1, QUAD(e, m1_)); set4(B.m2, QUAD(e, m2_));
+    set4(B.nextSigma, QUAD(e, new_sigma_)); set4(B.nextM1, QUAD(e, new_m1_)); set4(B.nextM2, QUAD(e, new_m2_));
+    for (int k = 0; k < 4; ++k) B.es.vec[k] = B.es.vec[k] && (uintptr_t)B.sigma[k] % 16 == 0; // the third base of the sample
+    B.flags = e->flags;
+    B.mstep = e->mstep; B.sstep = e->sstep; B.beta1 = e->beta1; B.omb1 = e->omb1; B.beta2 = e->beta2; B.omb2 = e->omb2;
+    B.alpha = e->alpha; B.eps = e->eps; B.sigmaMin = e->sigma_min; B.sigmaMax = e->sigma_max;
     const EsArgs &A = B.es;
     const long long G = (long long)A.M * (long long)A.S;
-    int rc = REM2D_OK;
-    if (stages & SN_SAMPLE) rc = sn_launch_items(rem2d_snes_sample_kernel, G / 2, B, st);
-    if (rc == REM2D_OK && (stages & SN_SHAPE)) {
+    if (stages & SN_SAMPLE) OK_TRY(launch_items(rem2d_snes_sample_kernel, G / 2, B, B.es.itemBase, st));
+    if (stages & SN_SHAPE) {
         B.es.itemBase = 0;
         hipLaunchKernelGGL(rem2d_es_shape_kernel, dim3((unsigned)((G + ES_TILE - 1) / ES_TILE)), dim3(ES_TILE), 0, st, B.es);
         HIP_TRY(hipGetLastError());
     }
-    if (rc == REM2D_OK && (stages & SN_UPDATE)) {
-        rc = sn_launch_items(rem2d_snes_update_kernel, (long long)A.M * (long long)A.nChunks * (long long)A.W, B, st);
-        if (rc == REM2D_OK && A.nChunks > 1) rc = sn_launch_items(rem2d_snes_finish_kernel, (long long)A.M * (long long)A.W, B, st);
+    if (stages & SN_UPDATE) {
+        OK_TRY(launch_items(rem2d_snes_update_kernel, (long long)A.M * (long long)A.nChunks * (long long)A.W, B, B.es.itemBase, st));
+        if (A.nChunks > 1) OK_TRY(launch_items(rem2d_snes_finish_kernel, (long long)A.M * (long long)A.W, B, B.es.itemBase, st));
     }
-    return rc;
+    return REM2D_OK;
 }
 extern "C" int64_t rem2d_snes_scratch_bytes(const rem2d_snes *e) {
-    const int rc = sn_shapes_ok("snes_scratch_bytes: ", e);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(sn_shapes_ok("snes_scratch_bytes: ", e));
     return (int64_t)sn_scratch_need(e);
 }
-extern "C" int rem2d_snes_sample(const rem2d_snes *e, void *stream) {
-    const int rc = sn_ok("snes_sample", e, SN_SAMPLE);
-    if (rc != REM2D_OK) return rc;
-    return sn_launch(e, SN_SAMPLE, (hipStream_t)stream);
-}
-extern "C" int rem2d_snes_update(const rem2d_snes *e, void *stream) {
-    const int rc = sn_ok("snes_update", e, SN_UPDATE);
-    if (rc != REM2D_OK) return rc;
-    return sn_launch(e, SN_UPDATE, (hipStream_t)stream);
-}
-extern "C" int rem2d_snes_step(const rem2d_snes *e, void *stream) {
-    const int rc = sn_ok("snes_step", e, SN_SHAPE | SN_UPDATE);
-    if (rc != REM2D_OK) return rc;
-    return sn_launch(e, SN_SHAPE | SN_UPDATE, (hipStream_t)stream);
-}
+extern "C" int rem2d_snes_sample(const rem2d_snes *e, void *stream) { return run(sn_ok, sn_launch, "snes_sample", e, SN_SAMPLE, stream); }
+extern "C" int rem2d_snes_update(const rem2d_snes *e, void *stream) { return run(sn_ok, sn_launch, "snes_update", e, SN_UPDATE, stream); }
+extern "C" int rem2d_snes_step(const rem2d_snes *e, void *stream) { return run(sn_ok, sn_launch, "snes_step", e, SN_SHAPE | SN_UPDATE, stream); }
 
 // ---- behavioural novelty (include/rem2d_novelty.h, csrc/rem2d_novelty.h) ----
 extern "C" int rem2d_novelty_abi_version(void) { return REM2D_NOVELTY_ABI_VERSION; }
@@ -2313,17 +2296,13 @@ static int nv_ok(const char *what, const rem2d_novelty *n, int stages) {
     if (!n->total) return fail(REM2D_E_INVALID, s + "NULL device pointer (total)");
     if (n->capacity > 0 && !n->archive) return fail(REM2D_E_INVALID, s + "NULL device pointer (archive)");
     if ((stages & NV_SCORE) && !n->novelty) return fail(REM2D_E_INVALID, s + "NULL device pointer (novelty)");
-    const uintptr_t d = (uintptr_t)n->desc, dn = d + (uintptr_t)((size_t)n->n_rows * (size_t)n->width * sizeof(float));
-    if (n->capacity > 0) {
-        const size_t M = (size_t)(n->n_rows / n->group_size);
-        const uintptr_t a = (uintptr_t)n->archive, an = a + (uintptr_t)(M * (size_t)n->capacity * (size_t)n->width * sizeof(float));
-        if (a < dn && d < an) return fail(REM2D_E_INVALID, s + "archive overlaps desc");
-    }
-    if (stages & NV_SCORE) {
-        const uintptr_t a = (uintptr_t)n->novelty, an = a + (uintptr_t)((size_t)n->n_rows * sizeof(double));
-        if (a < dn && d < an) return fail(REM2D_E_INVALID, s + "novelty overlaps desc");
-    }
-    return REM2D_OK;
+    const size_t G = (size_t)n->n_rows, M = (size_t)(n->n_rows / n->group_size);
+    const Span desc = span(n->desc, G * (size_t)n->width * sizeof(float), "desc");
+    Span out[2];
+    int no = 0;
+    if (n->capacity > 0) out[no++] = span(n->archive, M * (size_t)n->capacity * (size_t)n->width * sizeof(float), "archive");
+    if (stages & NV_SCORE) out[no++] = span(n->novelty, G * sizeof(double), "novelty");
+    return apart(s, out, no, &desc, 1);
 }
 template <int BP> static void nv_launch_score(const NvArgs &A, int kp, dim3 grid, hipStream_t st) {
     if (kp <= 2) hipLaunchKernelGGL((rem2d_novelty_score_kernel<BP, 2>), grid, dim3(NV_TILE), 0, st, A);
@@ -2337,7 +2316,7 @@ static int nv_launch(const rem2d_novelty *n, int stages, hipStream_t st) {
     memset(&A, 0, sizeof(A));
     A.desc = n->desc; A.archive = n->archive; A.total = (long long *)n->total; A.novelty = n->novelty; A.mask = n->add_mask;
     A.threshold = n->add_threshold;
-    A.key0 = (unsigned)(n->seed & 0xffffffffull); A.key1 = (unsigned)(n->seed >> 32); A.generation = n->generation;
+    seed_keys(n->seed, A.key0, A.key1); A.generation = n->generation;
     A.B = n->width; A.G = n->n_rows; A.S = n->group_size; A.k = n->k; A.cap = n->capacity;
     if (stages & NV_SCORE) {
         const dim3 grid((unsigned)(((long long)A.G + NV_TILE - 1) / NV_TILE));
@@ -2354,21 +2333,9 @@ static int nv_launch(const rem2d_novelty *n, int stages, hipStream_t st) {
     }
     return REM2D_OK;
 }
-extern "C" int rem2d_novelty_score(const rem2d_novelty *n, void *stream) {
-    const int rc = nv_ok("novelty_score", n, NV_SCORE);
-    if (rc != REM2D_OK) return rc;
-    return nv_launch(n, NV_SCORE, (hipStream_t)stream);
-}
-extern "C" int rem2d_novelty_add(const rem2d_novelty *n, void *stream) {
-    const int rc = nv_ok("novelty_add", n, NV_ADD);
-    if (rc != REM2D_OK) return rc;
-    return nv_launch(n, NV_ADD, (hipStream_t)stream);
-}
-extern "C" int rem2d_novelty_step(const rem2d_novelty *n, void *stream) {
-    const int rc = nv_ok("novelty_step", n, NV_SCORE | NV_ADD);
-    if (rc != REM2D_OK) return rc;
-    return nv_launch(n, NV_SCORE | NV_ADD, (hipStream_t)stream);
-}
+extern "C" int rem2d_novelty_score(const rem2d_novelty *n, void *stream) { return run(nv_ok, nv_launch, "novelty_score", n, NV_SCORE, stream); }
+extern "C" int rem2d_novelty_add(const rem2d_novelty *n, void *stream) { return run(nv_ok, nv_launch, "novelty_add", n, NV_ADD, stream); }
+extern "C" int rem2d_novelty_step(const rem2d_novelty *n, void *stream) { return run(nv_ok, nv_launch, "novelty_step", n, NV_SCORE | NV_ADD, stream); }
 
 // ---- MAP-Elites for device policies (include/rem2d_elites.h, csrc/rem2d_elites.h) ----
 extern "C" int rem2d_elites_abi_version(void) { return REM2D_ELITES_ABI_VERSION; }
@@ -2379,14 +2346,7 @@ static bool el_finite(float v) { return std::isfinite(v); }
 // Checks the shapes and parameters of an elites descriptor; `s` prefixes the message.  No pointer is looked at.
 static int el_shapes_ok(const std::string &s, const rem2d_elites *e) {
     if (!e) return fail(REM2D_E_INVALID, s + "NULL descriptor");
-    if (e->max_bodies < 1 || e->max_bodies > REM2D_CONTROL_MAX_BODIES)
-        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(e->max_bodies));
-    if (e->hidden < 1 || e->hidden > REM2D_POLICY_MAX_HIDDEN)
-        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(e->hidden));
-    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * e->max_bodies;
-    if (e->d < d0 || e->d > d0 + REM2D_SENSE_MAX_RAYS)
-        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
-                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(e->d));
+    OK_TRY(net_ok(s, e->d, e->hidden, e->max_bodies));
     if (e->width < 1 || e->width > REM2D_ELITES_MAX_WIDTH)
         return fail(REM2D_E_INVALID, s + "width must be 1.." + std::to_string(REM2D_ELITES_MAX_WIDTH) + ", not " + std::to_string(e->width));
     if (e->n_blocks < 1) return fail(REM2D_E_INVALID, s + "n_blocks must be at least 1, not " + std::to_string(e->n_blocks));
@@ -2417,19 +2377,22 @@ static long long el_cells(const rem2d_elites *e) {
 static size_t el_scratch_need(const rem2d_elites *e) {
     return (size_t)e->n_blocks * (size_t)el_cells(e) * (sizeof(unsigned long long) + sizeof(int));
 }
-static bool el_overlap(const void *a, size_t an, const void *b, size_t bn) {
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p < q + (uintptr_t)bn && q < p + (uintptr_t)an;
+// The buffers of a grid of `slots` cells (an elites or a cvt descriptor's) in the order both tiers test them: elite_fitness,
+// elite_desc, count, then the elite arrays in to[3 .. 6]; false where one of those is NULL.
+template <typename D> static bool grid_spans(Span (&to)[7], const D *e, size_t slots, const Net &N) {
+    to[0] = span(e->elite_fitness, slots * sizeof(double), "elite_fitness");
+    to[1] = span(e->elite_desc, slots * (size_t)e->width * sizeof(float), "elite_desc");
+    to[2] = span(e->count, slots * sizeof(int), "count");
+    return add4(to + 3, QUAD(e, elite_), "elite_", slots, N);
 }
 // Checks an elites descriptor for the calls in `stages`.  Nothing it points to is read.
 static int el_ok(const char *what, const rem2d_elites *e, int stages) {
     const std::string s = std::string(what) + ": ";
-    const int rc = el_shapes_ok(s, e);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(el_shapes_ok(s, e));
     const size_t slots = (size_t)e->n_blocks * (size_t)el_cells(e);
-    const size_t len[4] = {(size_t)e->d * (size_t)e->hidden, (size_t)e->hidden, (size_t)e->hidden * (size_t)e->max_bodies, (size_t)e->max_bodies};
-    const char *const name[4] = {"w1", "b1", "w2", "b2"};
-    const float *elite[4] = {e->elite_w1, e->elite_b1, e->elite_w2, e->elite_b2};
+    const Net N(e->d, e->hidden, e->max_bodies);
+    Span grid[7], *const elite = grid + 3;
+    const bool elites = grid_spans(grid, e, slots, N);
     if (stages & EL_INSERT) {
         if (e->group_size < 1) return fail(REM2D_E_INVALID, s + "group_size must be at least 1, not " + std::to_string(e->group_size));
         if ((long long)e->n_blocks * (long long)e->group_size > 2147483647ll)
@@ -2448,74 +2411,38 @@ static int el_ok(const char *what, const rem2d_elites *e, int stages) {
         if (!e->elite_desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (elite_desc)");
         if (!e->cell) return fail(REM2D_E_INVALID, s + "NULL device pointer (cell)");
         if (!e->winner) return fail(REM2D_E_INVALID, s + "NULL device pointer (winner)");
-        const float *src[4] = {e->w1, e->b1, e->w2, e->b2};
-        for (int k = 0; k < 4; ++k)
-            if (!src[k] || !elite[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
-        const size_t dn = G * (size_t)e->width * sizeof(float);
-        if (el_overlap(e->desc, dn, e->elite_fitness, slots * sizeof(double))) return fail(REM2D_E_INVALID, s + "desc overlaps elite_fitness");
-        if (el_overlap(e->desc, dn, e->elite_desc, slots * (size_t)e->width * sizeof(float))) return fail(REM2D_E_INVALID, s + "desc overlaps elite_desc");
-        if (el_overlap(e->desc, dn, e->count, slots * sizeof(int))) return fail(REM2D_E_INVALID, s + "desc overlaps count");
-        for (int k = 0; k < 4; ++k)
-            if (el_overlap(e->desc, dn, elite[k], slots * len[k] * sizeof(float))) return fail(REM2D_E_INVALID, s + "desc overlaps elite_" + name[k]);
-        for (int k = 0; k < 4; ++k)
-            for (int j = 0; j < 4; ++j)
-                if (el_overlap(src[j], G * len[j] * sizeof(float), elite[k], slots * len[k] * sizeof(float)))
-                    return fail(REM2D_E_INVALID, s + "elite_" + name[k] + " overlaps the evaluated sets' " + name[j]);
+        Span src[4];
+        if (!add4(src, QUAD(e, ), "the evaluated sets' ", G, N) || !elites) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        const Span desc = span(e->desc, G * (size_t)e->width * sizeof(float), "desc");
+        OK_TRY(apart(s, &desc, 1, grid, 7));
+        OK_TRY(apart(s, elite, 4, src, 4));
     }
     if (stages & (EL_SAMPLE | EL_VARY)) {
         if (!e->parent) return fail(REM2D_E_INVALID, s + "NULL device pointer (parent)");
         if (!e->n_filled) return fail(REM2D_E_INVALID, s + "NULL device pointer (n_filled)");
     }
     if (stages & EL_VARY) {
-        const float *dst[4] = {e->child_w1, e->child_b1, e->child_w2, e->child_b2};
-        for (int k = 0; k < 4; ++k)
-            if (!dst[k] || !elite[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
-        for (int k = 0; k < 4; ++k)
-            for (int j = 0; j < 4; ++j)
-                if (el_overlap(dst[k], (size_t)e->n_children * len[k] * sizeof(float), elite[j], slots * len[j] * sizeof(float)))
-                    return fail(REM2D_E_INVALID, s + "child_" + name[k] + " overlaps elite_" + name[j]);
+        Span dst[4];
+        if (!add4(dst, QUAD(e, child_), "child_", (size_t)e->n_children, N) || !elites) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        OK_TRY(apart(s, dst, 4, elite, 4));
     }
-    const size_t need = el_scratch_need(e);
-    if (!e->scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
-    if ((uintptr_t)e->scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
-    if (e->scratch_bytes < (uint64_t)need)
-        return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(e->scratch_bytes) + " bytes, " + std::to_string(need) + " are needed");
-    return REM2D_OK;
+    return scratch_ok(s, e->scratch, e->scratch_bytes, el_scratch_need(e));
 }
 // The stages of a checked descriptor on `st`.
 static int el_launch(const rem2d_elites *e, int stages, hipStream_t st) {
     ElArgs A;
-    EvolveArgs E;
     memset(&A, 0, sizeof(A));
-    memset(&E, 0, sizeof(E));
     const long long C = el_cells(e), slots = (long long)e->n_blocks * C;
+    const Net N(e->d, e->hidden, e->max_bodies);
     A.desc = e->desc; A.fitness = e->fitness; A.mask = e->mask;
     A.eliteFitness = e->elite_fitness; A.eliteDesc = e->elite_desc;
     A.count = e->count; A.cell = e->cell; A.winner = e->winner; A.parent = e->parent; A.nFilled = e->n_filled;
     A.key = (unsigned long long *)e->scratch;
     A.row = (int *)(A.key + slots);
     for (int i = 0; i < e->n_dims; ++i) { A.lo[i] = e->lo[i]; A.inv[i] = e->inv[i]; A.word[i] = e->word[i]; A.bins[i] = e->bins[i]; }
-    A.key0 = (unsigned)(e->seed & 0xffffffffull); A.key1 = (unsigned)(e->seed >> 32); A.generation = e->generation;
+    seed_keys(e->seed, A.key0, A.key1); A.generation = e->generation;
     A.nDims = e->n_dims; A.B = e->width; A.M = e->n_blocks; A.S = e->group_size; A.C = (int)C;
-    E.len[0] = e->d * e->hidden; E.len[1] = e->hidden; E.len[2] = e->hidden * e->max_bodies; E.len[3] = e->max_bodies;
-    float *const elite[4] = {e->elite_w1, e->elite_b1, e->elite_w2, e->elite_b2};
-    if (stages & EL_INSERT) {
-        const long long G = (long long)A.M * (long long)A.S;
-        const float *src[4] = {e->w1, e->b1, e->w2, e->b2};
-        for (int k = 0; k < 4; ++k) {
-            E.src[k] = src[k];
-            E.dst[k] = elite[k];
-            E.vec[k] = E.len[k] % 4 == 0 && (uintptr_t)E.src[k] % 16 == 0 && (uintptr_t)E.dst[k] % 16 == 0;
-        }
-        hipLaunchKernelGGL(rem2d_elites_clear_kernel, dim3((unsigned)((slots + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rem2d_elites_key_kernel, dim3((unsigned)((G + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rem2d_elites_row_kernel, dim3((unsigned)((G + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rem2d_elites_commit_kernel, dim3((unsigned)slots), dim3(WAVE), 0, st, A, E);
-        HIP_TRY(hipGetLastError());
-    }
+    if (stages & EL_INSERT) OK_TRY(insert_launch(rem2d_elites_key_kernel, A, A, N, QUAD(e, ), QUAD(e, elite_), st));
     if (stages & EL_SAMPLE) {
         A.perBlock = e->n_children / e->n_blocks;
         hipLaunchKernelGGL(rem2d_elites_sample_kernel, dim3((unsigned)A.M), dim3(EL_TILE), 0, st, A);
@@ -2523,12 +2450,9 @@ static int el_launch(const rem2d_elites *e, int stages, hipStream_t st) {
     }
     if (stages & EL_VARY) {
         // rem2d_evolve_vary_kernel as it is: the elite arrays are the "parents", M C bounds p, a workgroup per child
-        float *const dst[4] = {e->child_w1, e->child_b1, e->child_w2, e->child_b2};
-        for (int k = 0; k < 4; ++k) {
-            E.src[k] = elite[k];
-            E.dst[k] = dst[k];
-            E.vec[k] = E.len[k] % 4 == 0 && (uintptr_t)E.src[k] % 16 == 0 && (uintptr_t)E.dst[k] % 16 == 0;
-        }
+        EvolveArgs E;
+        memset(&E, 0, sizeof(E));
+        quads(E, N, QUAD(e, elite_), QUAD(e, child_));
         E.parent = e->parent;
         E.rateThreshold = e->rate_threshold;
         E.key0 = A.key0; E.key1 = A.key1; E.generation = e->generation;
@@ -2540,25 +2464,12 @@ static int el_launch(const rem2d_elites *e, int stages, hipStream_t st) {
     return REM2D_OK;
 }
 extern "C" int64_t rem2d_elites_scratch_bytes(const rem2d_elites *e) {
-    const int rc = el_shapes_ok("elites_scratch_bytes: ", e);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(el_shapes_ok("elites_scratch_bytes: ", e));
     return (int64_t)el_scratch_need(e);
 }
-extern "C" int rem2d_elites_insert(const rem2d_elites *e, void *stream) {
-    const int rc = el_ok("elites_insert", e, EL_INSERT);
-    if (rc != REM2D_OK) return rc;
-    return el_launch(e, EL_INSERT, (hipStream_t)stream);
-}
-extern "C" int rem2d_elites_sample(const rem2d_elites *e, void *stream) {
-    const int rc = el_ok("elites_sample", e, EL_SAMPLE);
-    if (rc != REM2D_OK) return rc;
-    return el_launch(e, EL_SAMPLE, (hipStream_t)stream);
-}
-extern "C" int rem2d_elites_emit(const rem2d_elites *e, void *stream) {
-    const int rc = el_ok("elites_emit", e, EL_SAMPLE | EL_VARY);
-    if (rc != REM2D_OK) return rc;
-    return el_launch(e, EL_SAMPLE | EL_VARY, (hipStream_t)stream);
-}
+extern "C" int rem2d_elites_insert(const rem2d_elites *e, void *stream) { return run(el_ok, el_launch, "elites_insert", e, EL_INSERT, stream); }
+extern "C" int rem2d_elites_sample(const rem2d_elites *e, void *stream) { return run(el_ok, el_launch, "elites_sample", e, EL_SAMPLE, stream); }
+extern "C" int rem2d_elites_emit(const rem2d_elites *e, void *stream) { return run(el_ok, el_launch, "elites_emit", e, EL_SAMPLE | EL_VARY, stream); }
 
 // ---- Centroid archives and the line emitter (include/rem2d_cvt.h, csrc/rem2d_cvt.h) ----
 extern "C" int rem2d_cvt_abi_version(void) { return REM2D_CVT_ABI_VERSION; }
@@ -2579,16 +2490,8 @@ static int cv_assign_shapes_ok(const std::string &s, const rem2d_cvt *v) {
 }
 // Checks the shapes and parameters of a centroid descriptor.  No pointer is looked at.
 static int cv_shapes_ok(const std::string &s, const rem2d_cvt *v) {
-    const int rc = cv_assign_shapes_ok(s, v);
-    if (rc != REM2D_OK) return rc;
-    if (v->max_bodies < 1 || v->max_bodies > REM2D_CONTROL_MAX_BODIES)
-        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(v->max_bodies));
-    if (v->hidden < 1 || v->hidden > REM2D_POLICY_MAX_HIDDEN)
-        return fail(REM2D_E_INVALID, s + "hidden must be 1.." + std::to_string(REM2D_POLICY_MAX_HIDDEN) + ", not " + std::to_string(v->hidden));
-    const int d0 = REM2D_OBS_HEAD + REM2D_OBS_BODY * v->max_bodies;
-    if (v->d < d0 || v->d > d0 + REM2D_SENSE_MAX_RAYS)
-        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 max_bodies + R with R in 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + " (" +
-                                         std::to_string(d0) + ".." + std::to_string(d0 + REM2D_SENSE_MAX_RAYS) + "), not " + std::to_string(v->d));
+    OK_TRY(cv_assign_shapes_ok(s, v));
+    OK_TRY(net_ok(s, v->d, v->hidden, v->max_bodies));
     if (v->n_blocks < 1) return fail(REM2D_E_INVALID, s + "n_blocks must be at least 1, not " + std::to_string(v->n_blocks));
     if ((long long)v->n_blocks * (long long)v->n_cells > 2147483647ll) return fail(REM2D_E_INVALID, s + "n_blocks times n_cells must be at most 2^31 - 1");
     if (v->group_size > 0 && (long long)v->n_blocks * (long long)v->group_size > 2147483647ll)
@@ -2600,8 +2503,7 @@ static size_t cv_slots(const rem2d_cvt *v) { return (size_t)v->n_blocks * (size_
 // Checks a centroid descriptor for the call `stage`.  Nothing it points to is read.
 static int cv_ok(const char *what, const rem2d_cvt *v, int stage) {
     const std::string s = std::string(what) + ": ";
-    const int rc = stage == CV_ASSIGN ? cv_assign_shapes_ok(s, v) : cv_shapes_ok(s, v);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(stage == CV_ASSIGN ? cv_assign_shapes_ok(s, v) : cv_shapes_ok(s, v));
     size_t need = 0;
     if (stage == CV_ASSIGN) {
         if (v->n_rows < 1) return fail(REM2D_E_INVALID, s + "n_rows must be at least 1, not " + std::to_string(v->n_rows));
@@ -2610,9 +2512,9 @@ static int cv_ok(const char *what, const rem2d_cvt *v, int stage) {
         need = cv_slots(v) * (sizeof(unsigned long long) + sizeof(int));
     }
     const size_t slots = stage == CV_ASSIGN ? 0 : cv_slots(v);
-    const size_t len[4] = {(size_t)v->d * (size_t)v->hidden, (size_t)v->hidden, (size_t)v->hidden * (size_t)v->max_bodies, (size_t)v->max_bodies};
-    const char *const name[4] = {"w1", "b1", "w2", "b2"};
-    const float *elite[4] = {v->elite_w1, v->elite_b1, v->elite_w2, v->elite_b2};
+    const Net N(v->d, v->hidden, v->max_bodies); // (the assignment, which does not check them, reads none of it)
+    Span grid[7], *const elite = grid + 3;
+    const bool elites = grid_spans(grid, v, slots, N);
     if (stage == CV_INSERT) {
         if (v->group_size < 1) return fail(REM2D_E_INVALID, s + "group_size must be at least 1, not " + std::to_string(v->group_size));
         need += (size_t)v->n_blocks * (size_t)v->group_size * sizeof(unsigned long long);
@@ -2626,32 +2528,20 @@ static int cv_ok(const char *what, const rem2d_cvt *v, int stage) {
         if (!v->centroids) return fail(REM2D_E_INVALID, s + "NULL device pointer (centroids)");
         if (!v->desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (desc)");
         if (!v->cell) return fail(REM2D_E_INVALID, s + "NULL device pointer (cell)");
-        const struct { const char *name; const void *p; size_t bytes; } in[2] = {
-            {"desc", v->desc, rows * (size_t)v->width * sizeof(float)}, {"centroids", v->centroids, (size_t)v->n_cells * (size_t)v->width * sizeof(float)}};
-        for (int i = 0; i < 2; ++i) {
-            if (el_overlap(in[i].p, in[i].bytes, v->cell, rows * sizeof(int))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps cell");
-            if (v->dist && el_overlap(in[i].p, in[i].bytes, v->dist, rows * sizeof(float))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps dist");
-        }
+        const Span in[2] = {span(v->desc, rows * (size_t)v->width * sizeof(float), "desc"),
+                            span(v->centroids, (size_t)v->n_cells * (size_t)v->width * sizeof(float), "centroids")};
+        const Span out[2] = {span(v->cell, rows * sizeof(int), "cell"), span(v->dist, rows * sizeof(float), "dist")};
+        OK_TRY(apart(s, in, 2, out, v->dist ? 2 : 1));
         if (stage == CV_INSERT) {
             if (!v->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
             if (!v->elite_fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (elite_fitness)");
             if (!v->elite_desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (elite_desc)");
             if (!v->count) return fail(REM2D_E_INVALID, s + "NULL device pointer (count)");
             if (!v->winner) return fail(REM2D_E_INVALID, s + "NULL device pointer (winner)");
-            const float *src[4] = {v->w1, v->b1, v->w2, v->b2};
-            for (int k = 0; k < 4; ++k)
-                if (!src[k] || !elite[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
-            for (int i = 0; i < 2; ++i) {
-                if (el_overlap(in[i].p, in[i].bytes, v->elite_fitness, slots * sizeof(double))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps elite_fitness");
-                if (el_overlap(in[i].p, in[i].bytes, v->elite_desc, slots * (size_t)v->width * sizeof(float))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps elite_desc");
-                if (el_overlap(in[i].p, in[i].bytes, v->count, slots * sizeof(int))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps count");
-                for (int k = 0; k < 4; ++k)
-                    if (el_overlap(in[i].p, in[i].bytes, elite[k], slots * len[k] * sizeof(float))) return fail(REM2D_E_INVALID, s + in[i].name + " overlaps elite_" + name[k]);
-            }
-            for (int k = 0; k < 4; ++k)
-                for (int j = 0; j < 4; ++j)
-                    if (el_overlap(src[j], rows * len[j] * sizeof(float), elite[k], slots * len[k] * sizeof(float)))
-                        return fail(REM2D_E_INVALID, s + "elite_" + name[k] + " overlaps the evaluated sets' " + name[j]);
+            Span src[4];
+            if (!add4(src, QUAD(v, ), "the evaluated sets' ", rows, N) || !elites) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+            OK_TRY(apart(s, in, 2, grid, 7));
+            OK_TRY(apart(s, elite, 4, src, 4));
         }
     }
     if (stage == CV_LINE) {
@@ -2659,19 +2549,11 @@ static int cv_ok(const char *what, const rem2d_cvt *v, int stage) {
         if (!v->parent) return fail(REM2D_E_INVALID, s + "NULL device pointer (parent)");
         if (!v->parent2) return fail(REM2D_E_INVALID, s + "NULL device pointer (parent2)");
         if (!v->n_filled) return fail(REM2D_E_INVALID, s + "NULL device pointer (n_filled)");
-        const float *dst[4] = {v->child_w1, v->child_b1, v->child_w2, v->child_b2};
-        for (int k = 0; k < 4; ++k)
-            if (!dst[k] || !elite[k]) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
-        for (int k = 0; k < 4; ++k)
-            for (int j = 0; j < 4; ++j)
-                if (el_overlap(dst[k], (size_t)v->n_children * len[k] * sizeof(float), elite[j], slots * len[j] * sizeof(float)))
-                    return fail(REM2D_E_INVALID, s + "child_" + name[k] + " overlaps elite_" + name[j]);
+        Span dst[4];
+        if (!add4(dst, QUAD(v, child_), "child_", (size_t)v->n_children, N) || !elites) return fail(REM2D_E_INVALID, s + "NULL device pointer (weights)");
+        OK_TRY(apart(s, dst, 4, elite, 4));
     }
-    if (!v->scratch) return fail(REM2D_E_INVALID, s + "NULL device pointer (scratch): " + std::to_string(need) + " bytes are needed");
-    if ((uintptr_t)v->scratch % 8 != 0) return fail(REM2D_E_INVALID, s + "scratch must be 8-byte aligned");
-    if (v->scratch_bytes < (uint64_t)need)
-        return fail(REM2D_E_INVALID, s + "scratch holds " + std::to_string(v->scratch_bytes) + " bytes, " + std::to_string(need) + " are needed");
-    return REM2D_OK;
+    return scratch_ok(s, v->scratch, v->scratch_bytes, need);
 }
 // The assignment of `rows` rows on `st`: A.best is set.  One launch, or clear + split assign + read-out.
 static int cv_assign_launch(CvArgs &A, long long rows, int splits, hipStream_t st) {
@@ -2698,9 +2580,8 @@ static int cv_assign_launch(CvArgs &A, long long rows, int splits, hipStream_t s
     }
     return REM2D_OK;
 }
-// The call `stage` of a checked descriptor on its stream.
-static int cv_launch(const rem2d_cvt *v, int stage) {
-    const hipStream_t st = (hipStream_t)v->stream;
+// The call `stage` of a checked descriptor on `st`, its stream.
+static int cv_launch(const rem2d_cvt *v, int stage, hipStream_t st) {
     CvArgs A;
     memset(&A, 0, sizeof(A));
     A.desc = v->desc; A.centroids = v->centroids; A.cell = v->cell; A.dist = v->dist;
@@ -2710,41 +2591,22 @@ static int cv_launch(const rem2d_cvt *v, int stage) {
     const long long slots = (long long)cv_slots(v);
     A.fitness = v->fitness; A.mask = v->mask; A.count = v->count;
     A.parent = v->parent; A.parent2 = v->parent2; A.nFilled = v->n_filled;
-    A.key0 = (unsigned)(v->seed & 0xffffffffull); A.key1 = (unsigned)(v->seed >> 32); A.generation = v->generation;
+    seed_keys(v->seed, A.key0, A.key1); A.generation = v->generation;
     A.M = v->n_blocks; A.S = v->group_size;
-    const int len[4] = {v->d * v->hidden, v->hidden, v->hidden * v->max_bodies, v->max_bodies};
-    float *const elite[4] = {v->elite_w1, v->elite_b1, v->elite_w2, v->elite_b2};
+    const Net N(v->d, v->hidden, v->max_bodies);
     if (stage == CV_INSERT) {
         // scratch: best[G] | key[M C] | row[M C]; the elites' kernels see the last two as they see their own scratch
         const long long G = (long long)A.M * (long long)A.S;
         A.key = A.best + G;
-        const int rc = cv_assign_launch(A, G, v->splits, st);
-        if (rc != REM2D_OK) return rc;
+        OK_TRY(cv_assign_launch(A, G, v->splits, st));
         ElArgs L;
-        EvolveArgs E;
         memset(&L, 0, sizeof(L));
-        memset(&E, 0, sizeof(E));
         L.desc = v->desc; L.fitness = v->fitness; L.mask = v->mask;
         L.eliteFitness = v->elite_fitness; L.eliteDesc = v->elite_desc;
         L.count = v->count; L.cell = v->cell; L.winner = v->winner;
         L.key = A.key; L.row = (int *)(A.key + slots);
         L.B = A.B; L.M = A.M; L.S = A.S; L.C = A.C;
-        const float *src[4] = {v->w1, v->b1, v->w2, v->b2};
-        for (int k = 0; k < 4; ++k) {
-            E.len[k] = len[k];
-            E.src[k] = src[k];
-            E.dst[k] = elite[k];
-            E.vec[k] = E.len[k] % 4 == 0 && (uintptr_t)E.src[k] % 16 == 0 && (uintptr_t)E.dst[k] % 16 == 0;
-        }
-        hipLaunchKernelGGL(rem2d_elites_clear_kernel, dim3((unsigned)((slots + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, L);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rem2d_cvt_key_kernel, dim3((unsigned)((G + CV_TILE - 1) / CV_TILE)), dim3(CV_TILE), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rem2d_elites_row_kernel, dim3((unsigned)((G + EL_TILE - 1) / EL_TILE)), dim3(EL_TILE), 0, st, L);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rem2d_elites_commit_kernel, dim3((unsigned)slots), dim3(WAVE), 0, st, L, E);
-        HIP_TRY(hipGetLastError());
-        return REM2D_OK;
+        return insert_launch(rem2d_cvt_key_kernel, A, L, N, QUAD(v, ), QUAD(v, elite_), st);
     }
     // CV_LINE: the draw (its list in the scratch's last M C words, where the elites' sample keeps it), then the variation
     A.list = (int *)((unsigned long long *)v->scratch + slots);
@@ -2753,13 +2615,7 @@ static int cv_launch(const rem2d_cvt *v, int stage) {
     HIP_TRY(hipGetLastError());
     CvLine Ln;
     memset(&Ln, 0, sizeof(Ln));
-    float *const dst[4] = {v->child_w1, v->child_b1, v->child_w2, v->child_b2};
-    for (int k = 0; k < 4; ++k) {
-        Ln.len[k] = len[k];
-        Ln.src[k] = elite[k];
-        Ln.dst[k] = dst[k];
-        Ln.vec[k] = len[k] % 4 == 0 && (uintptr_t)elite[k] % 16 == 0 && (uintptr_t)dst[k] % 16 == 0;
-    }
+    quads(Ln, N, QUAD(v, elite_), QUAD(v, child_));
     Ln.parent = v->parent; Ln.parent2 = v->parent2;
     Ln.key0 = A.key0; Ln.key1 = A.key1; Ln.generation = v->generation;
     Ln.slots = (int)slots;
@@ -2769,37 +2625,20 @@ static int cv_launch(const rem2d_cvt *v, int stage) {
     return REM2D_OK;
 }
 extern "C" int64_t rem2d_cvt_scratch_bytes(const rem2d_cvt *v) {
-    const int rc = cv_shapes_ok("cvt_scratch_bytes: ", v);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(cv_shapes_ok("cvt_scratch_bytes: ", v));
     const long long G = v->group_size > 0 ? (long long)v->n_blocks * (long long)v->group_size : 0;
     const long long R = std::max((long long)(v->n_rows > 0 ? v->n_rows : 0), G);
     return (int64_t)(cv_slots(v) * 12) + (int64_t)(8 * R);
 }
-extern "C" int rem2d_cvt_assign(const rem2d_cvt *v) {
-    const int rc = cv_ok("cvt_assign", v, CV_ASSIGN);
-    if (rc != REM2D_OK) return rc;
-    return cv_launch(v, CV_ASSIGN);
-}
-extern "C" int rem2d_cvt_insert(const rem2d_cvt *v) {
-    const int rc = cv_ok("cvt_insert", v, CV_INSERT);
-    if (rc != REM2D_OK) return rc;
-    return cv_launch(v, CV_INSERT);
-}
-extern "C" int rem2d_cvt_emit_line(const rem2d_cvt *v) {
-    const int rc = cv_ok("cvt_emit_line", v, CV_LINE);
-    if (rc != REM2D_OK) return rc;
-    return cv_launch(v, CV_LINE);
-}
+// (the stream is a member of the descriptor, which may be NULL)
+extern "C" int rem2d_cvt_assign(const rem2d_cvt *v) { return run(cv_ok, cv_launch, "cvt_assign", v, CV_ASSIGN, v ? v->stream : nullptr); }
+extern "C" int rem2d_cvt_insert(const rem2d_cvt *v) { return run(cv_ok, cv_launch, "cvt_insert", v, CV_INSERT, v ? v->stream : nullptr); }
+extern "C" int rem2d_cvt_emit_line(const rem2d_cvt *v) { return run(cv_ok, cv_launch, "cvt_emit_line", v, CV_LINE, v ? v->stream : nullptr); }
 
 // ---- Pareto ranking (include/rem2d_pareto.h, csrc/rem2d_pareto.h) ----
 extern "C" int rem2d_pareto_abi_version(void) { return REM2D_PARETO_ABI_VERSION; }
 static_assert(REM2D_PARETO_MAX_GROUP == PA_LONG, "a block of the rank fits one workgroup");
 static_assert(REM2D_PARETO_MAX_WIDTH == REM2D_NOVELTY_MAX_WIDTH && REM2D_PARETO_MAX_K <= 32, "the local kernel's register bounds and its 32-bit mask");
-// does [p, p + bytes) meet [q, q + qbytes)?
-static bool pa_meet(const void *p, size_t bytes, const void *q, size_t qbytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)bytes;
-}
 // The members both calls share.  Nothing the descriptor points to is read.
 static int pa_ok(const std::string &s, const rem2d_pareto *p, int max_group) {
     if (!p) return fail(REM2D_E_INVALID, s + "NULL descriptor");
@@ -2817,17 +2656,17 @@ template <int T> static void pa_launch_rank(const PaArgs &A, int K, dim3 grid, h
 }
 extern "C" int rem2d_pareto_rank(const rem2d_pareto *p, void *stream) {
     const std::string s = "pareto_rank: ";
-    const int rc = pa_ok(s, p, REM2D_PARETO_MAX_GROUP);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(pa_ok(s, p, REM2D_PARETO_MAX_GROUP));
     if (p->n_obj < 1 || p->n_obj > REM2D_PARETO_MAX_OBJ)
         return fail(REM2D_E_INVALID, s + "n_obj must be 1.." + std::to_string(REM2D_PARETO_MAX_OBJ) + ", not " + std::to_string(p->n_obj));
     if (p->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0");
     if (!p->obj) return fail(REM2D_E_INVALID, s + "NULL device pointer (obj)");
-    const size_t G = (size_t)p->n_rows, M = G / (size_t)p->group_size, in = G * (size_t)p->n_obj * sizeof(double);
-    if (p->front && pa_meet(p->front, G * sizeof(int32_t), p->obj, in)) return fail(REM2D_E_INVALID, s + "front overlaps obj");
-    if (p->crowd && pa_meet(p->crowd, G * sizeof(double), p->obj, in)) return fail(REM2D_E_INVALID, s + "crowd overlaps obj");
-    if (p->util && pa_meet(p->util, G * sizeof(int32_t), p->obj, in)) return fail(REM2D_E_INVALID, s + "util overlaps obj");
-    if (p->n_fronts && pa_meet(p->n_fronts, M * sizeof(int32_t), p->obj, in)) return fail(REM2D_E_INVALID, s + "n_fronts overlaps obj");
+    const size_t G = (size_t)p->n_rows, M = G / (size_t)p->group_size;
+    const Span obj = span(p->obj, G * (size_t)p->n_obj * sizeof(double), "obj");
+    const Span out[4] = {span(p->front, G * sizeof(int32_t), "front"), span(p->crowd, G * sizeof(double), "crowd"),
+                         span(p->util, G * sizeof(int32_t), "util"), span(p->n_fronts, M * sizeof(int32_t), "n_fronts")};
+    for (const Span &o : out) // (each of them may be NULL)
+        if (o.at) OK_TRY(apart(s, &o, 1, &obj, 1));
     PaArgs A;
     memset(&A, 0, sizeof(A));
     A.obj = p->obj; A.front = p->front; A.crowd = p->crowd; A.util = p->util; A.nfronts = p->n_fronts;
@@ -2847,8 +2686,7 @@ template <int BP> static void pa_launch_local(const PaArgs &A, dim3 grid, hipStr
 }
 extern "C" int rem2d_pareto_local(const rem2d_pareto *p, void *stream) {
     const std::string s = "pareto_local: ";
-    const int rc = pa_ok(s, p, 0);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(pa_ok(s, p, 0));
     if (p->width < 1 || p->width > REM2D_PARETO_MAX_WIDTH)
         return fail(REM2D_E_INVALID, s + "width must be 1.." + std::to_string(REM2D_PARETO_MAX_WIDTH) + ", not " + std::to_string(p->width));
     if (p->k < 1 || p->k > REM2D_PARETO_MAX_K)
@@ -2857,11 +2695,10 @@ extern "C" int rem2d_pareto_local(const rem2d_pareto *p, void *stream) {
     if (!p->desc) return fail(REM2D_E_INVALID, s + "NULL device pointer (desc)");
     if (!p->fitness) return fail(REM2D_E_INVALID, s + "NULL device pointer (fitness)");
     if (!p->local) return fail(REM2D_E_INVALID, s + "NULL device pointer (local)");
-    const size_t G = (size_t)p->n_rows, dn = G * (size_t)p->width * sizeof(float), fn = G * sizeof(double);
-    if (pa_meet(p->local, G * sizeof(double), p->desc, dn)) return fail(REM2D_E_INVALID, s + "local overlaps desc");
-    if (pa_meet(p->local, G * sizeof(double), p->fitness, fn)) return fail(REM2D_E_INVALID, s + "local overlaps fitness");
-    if (p->neighbours && pa_meet(p->neighbours, G * sizeof(int32_t), p->desc, dn)) return fail(REM2D_E_INVALID, s + "neighbours overlaps desc");
-    if (p->neighbours && pa_meet(p->neighbours, G * sizeof(int32_t), p->fitness, fn)) return fail(REM2D_E_INVALID, s + "neighbours overlaps fitness");
+    const size_t G = (size_t)p->n_rows;
+    const Span in[2] = {span(p->desc, G * (size_t)p->width * sizeof(float), "desc"), span(p->fitness, G * sizeof(double), "fitness")};
+    const Span out[2] = {span(p->local, G * sizeof(double), "local"), span(p->neighbours, G * sizeof(int32_t), "neighbours")};
+    OK_TRY(apart(s, out, p->neighbours ? 2 : 1, in, 2));
     PaArgs A;
     memset(&A, 0, sizeof(A));
     A.desc = p->desc; A.fitness = p->fitness; A.local = p->local; A.neigh = p->neighbours;

@@ -207,6 +207,9 @@ SHAPE_CASES = [(dict(max_bodies=0, d=8), b"max_bodies"), (dict(max_bodies=65, d=
                (dict(n_means=2 ** 16, group_size=2 ** 15), b"2^31 - 1"), (dict(n_means=1, group_size=2 ** 31 - 1), b"group_size"),
                (dict(pair_chunk=-1), b"pair_chunk"), (dict(reserved=1), b"reserved")]
 E_WORDS = 114 * 32 + 32 + 32 * 16 + 16
+NEED = 4 * 4 * E_WORDS * 8             # scratch: 4 means x 4 chunks of 2 pairs x E words x 8 bytes
+SCRATCH_CASES = ((dict(scratch=None), b"scratch"), (dict(scratch_bytes=NEED - 1), b"are needed"), (dict(scratch_bytes=0), b"are needed"),
+                 (dict(scratch=(15 << 26) + 4), b"8-byte aligned"))
 
 
 def _overlaps(prefix, sets_bytes):
@@ -255,11 +258,8 @@ def test_bad_arguments_are_refused_before_anything_is_dereferenced():
             for kw, msg in _overlaps("new", W1_BYTES):
                 e = _desc(**kw)
                 assert fn(C.byref(e), None) == -1 and msg in err() and err().startswith(prefix), (kw, err())
-            # scratch: 4 means x 4 chunks of 2 pairs x E words x 8 bytes
-            need = 4 * 4 * E_WORDS * 8
-            assert L.rem2d_es_scratch_bytes(C.byref(_desc(pair_chunk=2))) == need
-            for kw, msg in ((dict(scratch=None), b"scratch"), (dict(scratch_bytes=need - 1), b"are needed"), (dict(scratch_bytes=0), b"are needed"),
-                            (dict(scratch=(15 << 26) + 4), b"8-byte aligned")):
+            assert L.rem2d_es_scratch_bytes(C.byref(_desc(pair_chunk=2))) == NEED
+            for kw, msg in SCRATCH_CASES:
                 e = _desc(pair_chunk=2, **kw)
                 assert fn(C.byref(e), None) == -1 and msg in err() and err().startswith(prefix), (kw, err())
         # the split that pair_chunk names, and the library's choice

@@ -233,6 +233,25 @@ SHAPE_CASES = [(dict(max_bodies=0, d=8), b"max_bodies"), (dict(max_bodies=65, d=
                (dict(group_size=-2), b"group_size"), (dict(group_size=7), b"group_size"), (dict(group_size=8194), b"at most 8192"),
                (dict(n_means=1, group_size=65536), b"at most 8192"), (dict(n_means=2 ** 19, group_size=2 ** 12), b"2^31 - 1"),
                (dict(pair_chunk=-1), b"pair_chunk"), (dict(flags=4), b"flags"), (dict(flags=2 ** 31 + 1), b"flags")]
+NEED = 2 * 4 * 4 * E_WORDS * 8                                      # 4 means x 4 chunks of 2 pairs x 2 sums x E words x 8 bytes
+SAMPLE_OVERLAPS = ((dict(child_w1=_at("w1")), b"child_w1 overlaps the mean's w1"),
+                   (dict(child_w1=_at("w1") + SET_BYTES["w1"] - 4), b"child_w1 overlaps the mean's w1"),
+                   (dict(child_w1=_at("w1") - 16 * SET_BYTES["w1"] + 4), b"child_w1 overlaps the mean's w1"),
+                   (dict(child_b2=_at("sigma_w2") + 8), b"child_b2 overlaps sigma_w2"),
+                   (dict(child_w2=_at("child_w1") + 64), b"child_w2 overlaps child_w1"))
+UPDATE_OVERLAPS = [(dict(new_w1=_at("w1")), b"new_w1 overlaps the mean's w1"), (dict(new_w1=_at("w1") + SET_BYTES["w1"] - 4), b"new_w1 overlaps the mean's w1"),
+                   (dict(new_w1=_at("w1") - SET_BYTES["w1"] + 4), b"new_w1 overlaps the mean's w1"),
+                   (dict(new_sigma_b1=_at("sigma_b1")), b"new_sigma_b1 overlaps sigma_b1"), (dict(new_sigma_w2=_at("m2_w2") + 4), b"new_sigma_w2 overlaps m2_w2"),
+                   (dict(new_m1_w1=_at("m1_w1")), b"new_m1_w1 overlaps m1_w1"), (dict(new_m2_b2=_at("b2")), b"new_m2_b2 overlaps the mean's b2"),
+                   (dict(new_b2=_at("util") + 4 * 63), b"new_b2 overlaps util"), (dict(new_m2_w1=_at("new_w1")), b"new_m2_w1 overlaps new_w1"),
+                   (dict(new_sigma_b2=_at("new_b2") + 4), b"new_sigma_b2 overlaps new_b2"),
+                   (dict(pair_chunk=2, scratch=_at("sigma_w1") + 8), b"scratch overlaps sigma_w1"),
+                   (dict(pair_chunk=2, scratch=_at("new_m1_w2") - NEED + 8), b"scratch overlaps new_m1_w2")]
+STEP_OVERLAPS = [(dict(new_b1=_at("fitness") + 8 * 63), b"new_b1 overlaps fitness")]
+SIGMA_BOUNDS = ((0.0, 1.0), (-1.0, 1.0), (2.0, 1.0), (float("nan"), 1.0), (1.0, float("nan")), (1.0, float("inf")), (float("inf"), float("inf")),
+                (-float("inf"), 1.0))
+SCRATCH_CASES = ((dict(scratch=None), b"scratch"), (dict(scratch_bytes=NEED - 1), b"are needed"), (dict(scratch_bytes=0), b"are needed"),
+                 (dict(scratch=_at("scratch") + 4), b"8-byte aligned"))
 
 
 def test_bad_arguments_are_refused_before_anything_is_dereferenced():
@@ -260,7 +279,7 @@ def test_bad_arguments_are_refused_before_anything_is_dereferenced():
             fn, prefix = calls[name]
             assert fn(C.byref(_desc(util=None)), None) == -1 and b"util" in err() and err().startswith(prefix)
         needs = {"sample": ("", "sigma_", "child_"), "update": IN_PREFIXES + OUT_PREFIXES[1:], "step": IN_PREFIXES + OUT_PREFIXES[1:]}
-        need = 2 * 4 * 4 * E_WORDS * 8                                      # 4 means x 4 chunks of 2 pairs x 2 sums x E words x 8 bytes
+        need = NEED
         for name, (fn, prefix) in calls.items():
             for pre in needs[name]:
                 for k in ARRAYS:
@@ -272,11 +291,7 @@ def test_bad_arguments_are_refused_before_anything_is_dereferenced():
                 assert fn(C.byref(e), None) == -1 and b"are needed" in err(), (name, err())
         # overlaps: an output with an input, an output with another output
         fn, prefix = calls["sample"]
-        for kw, msg in ((dict(child_w1=_at("w1")), b"child_w1 overlaps the mean's w1"),
-                        (dict(child_w1=_at("w1") + SET_BYTES["w1"] - 4), b"child_w1 overlaps the mean's w1"),
-                        (dict(child_w1=_at("w1") - 16 * SET_BYTES["w1"] + 4), b"child_w1 overlaps the mean's w1"),
-                        (dict(child_b2=_at("sigma_w2") + 8), b"child_b2 overlaps sigma_w2"),
-                        (dict(child_w2=_at("child_w1") + 64), b"child_w2 overlaps child_w1")):
+        for kw, msg in SAMPLE_OVERLAPS:
             e = _desc(**kw)
             assert fn(C.byref(e), None) == -1 and msg in err() and err().startswith(prefix), (kw, err())
         # (the moments and the new state are nothing to sample: the same descriptor with them in a heap passes every check but the last)
@@ -284,26 +299,15 @@ def test_bad_arguments_are_refused_before_anything_is_dereferenced():
         assert fn(C.byref(e), None) == -1 and b"child_b2 overlaps the mean's b2" in err(), err()
         for name in ("update", "step"):
             fn, prefix = calls[name]
-            cases = [(dict(new_w1=_at("w1")), b"new_w1 overlaps the mean's w1"), (dict(new_w1=_at("w1") + SET_BYTES["w1"] - 4), b"new_w1 overlaps the mean's w1"),
-                     (dict(new_w1=_at("w1") - SET_BYTES["w1"] + 4), b"new_w1 overlaps the mean's w1"),
-                     (dict(new_sigma_b1=_at("sigma_b1")), b"new_sigma_b1 overlaps sigma_b1"), (dict(new_sigma_w2=_at("m2_w2") + 4), b"new_sigma_w2 overlaps m2_w2"),
-                     (dict(new_m1_w1=_at("m1_w1")), b"new_m1_w1 overlaps m1_w1"), (dict(new_m2_b2=_at("b2")), b"new_m2_b2 overlaps the mean's b2"),
-                     (dict(new_b2=_at("util") + 4 * 63), b"new_b2 overlaps util"), (dict(new_m2_w1=_at("new_w1")), b"new_m2_w1 overlaps new_w1"),
-                     (dict(new_sigma_b2=_at("new_b2") + 4), b"new_sigma_b2 overlaps new_b2"),
-                     (dict(pair_chunk=2, scratch=_at("sigma_w1") + 8), b"scratch overlaps sigma_w1"),
-                     (dict(pair_chunk=2, scratch=_at("new_m1_w2") - need + 8), b"scratch overlaps new_m1_w2")]
-            if name == "step":
-                cases.append((dict(new_b1=_at("fitness") + 8 * 63), b"new_b1 overlaps fitness"))
-            for kw, msg in cases:
+            for kw, msg in UPDATE_OVERLAPS + (STEP_OVERLAPS if name == "step" else []):
                 e = _desc(**kw)
                 assert fn(C.byref(e), None) == -1 and msg in err() and err().startswith(prefix), (kw, err())
-            for lo, hi in ((0.0, 1.0), (-1.0, 1.0), (2.0, 1.0), (nan, 1.0), (1.0, nan), (1.0, inf), (inf, inf), (-inf, 1.0)):
+            for lo, hi in SIGMA_BOUNDS:
                 e = _desc(sigma_min=lo, sigma_max=hi)
                 assert fn(C.byref(e), None) == -1 and b"sigma_min" in err() and err().startswith(prefix), (lo, hi, err())
             # scratch
             assert L.rem2d_snes_scratch_bytes(C.byref(_desc(pair_chunk=2))) == need
-            for kw, msg in ((dict(scratch=None), b"scratch"), (dict(scratch_bytes=need - 1), b"are needed"), (dict(scratch_bytes=0), b"are needed"),
-                            (dict(scratch=_at("scratch") + 4), b"8-byte aligned")):
+            for kw, msg in SCRATCH_CASES:
                 e = _desc(pair_chunk=2, **kw)
                 assert fn(C.byref(e), None) == -1 and msg in err() and err().startswith(prefix), (kw, err())
             # without ADAM an output ON a moment is no overlap; buffers that touch are fine; the limits themselves are fine: each
