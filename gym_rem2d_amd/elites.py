@@ -11,19 +11,14 @@ is the directional iso+line variation between two elites, on grids and centroid 
 
 Nothing here allocates after the grid was made and ``out=`` is given; every call is one library call queued on the current stream;
 nothing synchronises.  tests/elites_model.py restates every output bit in numpy."""
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._tier import draw_ok, is_tensor, launch, overlaps, point, rate_threshold      # (rate_threshold is a public name of this module too)
 from .policy import MLPPolicy
-
-
-def rate_threshold(rate):
-    """floor(rate * 2^32), the ``rate_threshold`` of a rate in [0, 1] (the product of a binary64 by 2^32 is exact)"""
-    return int(math.floor(float(rate) * 4294967296.0))
 
 
 def _check_dims(dims, width):
@@ -134,23 +129,38 @@ class EliteGrid:
         for k in self._STATE:
             getattr(self, k).copy_(state[k])
 
-    # ---- the library's descriptor ----
-    def _descriptor(self, generation=0, seed=0, rate=0.0, sigma=0.0):
-        e = _lib.Elites()
-        e.d, e.hidden, e.max_bodies, e.width, e.n_blocks, e.n_dims = self.d, self.hidden, self.max_bodies, self.width, self.n_blocks, len(self.word)
-        for i in range(len(self.word)):
-            e.word[i], e.bins[i], e.lo[i], e.inv[i] = self.word[i], self.bins[i], self.lo[i], self.inv[i]
-        e.generation, e.sigma, e.rate_threshold, e.seed, e.reserved = int(generation), float(sigma), rate_threshold(rate), int(seed), 0
+    # ---- the library's descriptors ----
+    @property
+    def weights(self):
+        """(w1, b1, w2, b2): slot ``b C + q`` of each is cell q of block b"""
+        return self.w1, self.b1, self.w2, self.b2
+
+    def _elite_fields(self, e):
+        """the grids' state, written into a rem2d_elites or a rem2d_cvt: both name it alike"""
+        e.d, e.hidden, e.max_bodies, e.width, e.n_blocks = self.d, self.hidden, self.max_bodies, self.width, self.n_blocks
         e.elite_fitness, e.elite_desc, e.count = self.fitness.data_ptr(), self.desc.data_ptr(), self.count.data_ptr()
-        e.elite_w1, e.elite_b1, e.elite_w2, e.elite_b2 = (t.data_ptr() for t in (self.w1, self.b1, self.w2, self.b2))
+        point(e, "elite_", self.weights)
         e.winner, e.n_filled = self.winner.data_ptr(), self.filled.data_ptr()
         e.scratch, e.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel() * 8
         return e
 
-    def _call(self, name, e, wide):
-        L = _lib.lib(wide)
-        with torch.cuda.device(self.device):
-            _lib.check(getattr(L, name)(C.byref(e), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), wide)
+    def _descriptor(self, generation=0, seed=0, rate=0.0, sigma=0.0):
+        e = self._elite_fields(_lib.Elites())
+        e.n_dims = len(self.word)
+        for i in range(len(self.word)):
+            e.word[i], e.bins[i], e.lo[i], e.inv[i] = self.word[i], self.bins[i], self.lo[i], self.inv[i]
+        e.generation, e.sigma, e.rate_threshold, e.seed, e.reserved = int(generation), float(sigma), rate_threshold(rate), int(seed), 0
+        return e
+
+    def _line_descriptor(self, generation, seed, sigma_iso, sigma_line):
+        v = self._elite_fields(_lib.Cvt())
+        v.n_cells = self.n_cells
+        v.generation, v.seed, v.sigma_iso, v.sigma_line, v.splits, v.reserved = int(generation), int(seed), float(sigma_iso), float(sigma_line), 0, 0
+        return v
+
+    def _launch(self, name, e, wide):
+        """(a call of include/rem2d_cvt.h takes its stream as a member of the descriptor, not as a parameter)"""
+        launch(getattr(_lib.lib(wide), name), e, self.device, wide, stream_member=isinstance(e, _lib.Cvt))
 
     def _fits(self, what, policy, n_sets=None):
         if not isinstance(policy, MLPPolicy) or policy.index is not None:
@@ -162,11 +172,14 @@ class EliteGrid:
             raise ValueError("%s: the policy must be on %s, not %s" % (what, self.device, policy.device))
         if n_sets is not None and policy.n_sets != n_sets:
             raise ValueError("%s: the policy must have %d weight sets, not %d" % (what, n_sets, policy.n_sets))
-        mine = (self.w1, self.b1, self.w2, self.b2)
-        for a in (policy.w1, policy.b1, policy.w2, policy.b2):
-            for b in mine:
-                if a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
-                    raise ValueError("%s: the policy shares memory with the grid" % what)
+        if overlaps(policy.weights, self.weights):
+            raise ValueError("%s: the policy shares memory with the grid" % what)
+
+    _NOUN, _INSERT = "grid", "rem2d_elites_insert"       # what ``insert`` calls the object, and the library call it queues
+
+    def _insert_descriptor(self, G):
+        """the descriptor of an ``insert`` of G rows, with whatever outputs beyond ``cell`` the call has (made here if need be)"""
+        return self._descriptor()
 
     def insert(self, policy, fitness, desc, mask=None, group_size=None, wide=False):
         """File the G evaluated sets of ``policy`` into the grids (rem2d_elites_insert): ``fitness`` float64 ``[G]``, ``desc``
@@ -180,11 +193,11 @@ class EliteGrid:
         G = policy.n_sets
         if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
             raise ValueError("insert: fitness must be a torch.float64 tensor")
-        if tuple(fitness.shape) != (G,) or not fitness.is_contiguous() or fitness.device != dev:
+        if not is_tensor(fitness, torch.float64, (G,), dev):
             raise ValueError("insert: fitness must be a contiguous tensor of one entry per weight set [%d] on %s, not %s" % (G, dev, list(fitness.shape)))
         if not isinstance(desc, torch.Tensor) or desc.dtype != torch.float32:
             raise ValueError("insert: desc must be a torch.float32 tensor")
-        if tuple(desc.shape) != (G, self.width) or not desc.is_contiguous() or desc.device != dev:
+        if not is_tensor(desc, torch.float32, (G, self.width), dev):
             raise ValueError("insert: desc must be a contiguous tensor [%d, %d] on %s, not %s" % (G, self.width, dev, list(desc.shape)))
         if group_size is None:
             if G % self.n_blocks:
@@ -192,41 +205,54 @@ class EliteGrid:
             group_size = G // self.n_blocks
         S = int(group_size)
         if S < 1 or S * self.n_blocks != G:
-            raise ValueError("insert: %d rows in groups of %r are not the grid's %d blocks" % (G, group_size, self.n_blocks))
+            raise ValueError("insert: %d rows in groups of %r are not the %s's %d blocks" % (G, group_size, self._NOUN, self.n_blocks))
         if mask is not None:
             if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
                 raise ValueError("insert: mask must be a torch.bool or torch.uint8 tensor")
-            if tuple(mask.shape) != (G,) or not mask.is_contiguous() or mask.device != dev:
+            if not is_tensor(mask, (torch.bool, torch.uint8), (G,), dev):
                 raise ValueError("insert: mask must be a contiguous tensor of one entry per row [%d] on %s, not %s" % (G, dev, list(mask.shape)))
-        for name, other in (("fitness", self.fitness), ("desc", self.desc), ("count", self.count), ("w1", self.w1), ("b1", self.b1),
-                            ("w2", self.w2), ("b2", self.b2)):
-            a, an = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
-            b, bn = desc.data_ptr(), desc.data_ptr() + desc.numel() * 4
-            if a < bn and b < an:
-                raise ValueError("insert: desc shares memory with the grid's %s" % name)
+        for name in self._STATE:                            # (what a checkpoint holds is what the call reads beside its arguments)
+            if overlaps(getattr(self, name), desc):
+                raise ValueError("insert: desc shares memory with the %s's %s" % (self._NOUN, name))
         if dev.type != "cuda":
-            raise ValueError("insert: the grid is on %s; make it on the GPU (device=...)" % dev)
+            raise ValueError("insert: the %s is on %s; make it on the GPU (device=...)" % (self._NOUN, dev))
         if self.cell is None or tuple(self.cell.shape) != (G,):
             self.cell = torch.empty(G, dtype=torch.int32, device=dev)
-        e = self._descriptor()
+        e = self._insert_descriptor(G)
         e.group_size = S
         e.desc, e.fitness, e.mask = desc.data_ptr(), fitness.data_ptr(), None if mask is None else mask.data_ptr()
-        e.w1, e.b1, e.w2, e.b2 = (t.data_ptr() for t in (policy.w1, policy.b1, policy.w2, policy.b2))
+        point(e, "", policy.weights)
         e.cell = self.cell.data_ptr()
         self._keep = (policy, fitness, desc, mask)          # (the tensors the queued kernels read)
-        self._call("rem2d_elites_insert", e, wide)
+        self._launch(self._INSERT, e, wide)
         return self.winner
 
     def _draw(self, what, generation, seed, n_children, parents):
-        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError("%s: generation must fit 32 bits and seed 64 (unsigned)" % what)
+        draw_ok(what, generation, seed)
         n = self.n_blocks if n_children is None else int(n_children)
         if n < 1 or n % self.n_blocks or n > 2 ** 31 - 1:
             raise ValueError("%s: n_children must be a positive multiple of the grid's %d blocks, not %r" % (what, self.n_blocks, n_children))
-        if parents is not None and (not isinstance(parents, torch.Tensor) or parents.dtype != torch.int32 or tuple(parents.shape) != (n,)
-                                    or not parents.is_contiguous() or parents.device != self.device):
+        if parents is not None and not is_tensor(parents, torch.int32, (n,), self.device):
             raise ValueError("%s: parents must be a contiguous torch.int32 [%d] tensor on %s" % (what, n, self.device))
         return n
+
+    def _emit_checks(self, what, generation, seed, n_children, out):
+        """the first checks of ``emit`` and ``emit_line`` -> the number of children (default: those of ``out``, else one per block)"""
+        if out is not None:
+            self._fits(what, out, None if n_children is None else int(n_children))
+            if n_children is None:
+                n_children = out.n_sets
+        return self._draw(what, generation, seed, n_children, None)
+
+    def _emit_out(self, out, n, indices):
+        """``out``, or a new zeroed policy of n sets, with every int32 ``[n]`` attribute named in ``indices``: one it has is reused
+        where it is the tensor a kernel can write, else made"""
+        dev = self.device
+        out = self.like._sets(n, zeroed=True, device=dev) if out is None else self.like._adopt(out)
+        for attr in indices:
+            if not is_tensor(getattr(out, attr, None), torch.int32, (n,), dev):
+                setattr(out, attr, torch.empty(n, dtype=torch.int32, device=dev))
+        return out
 
     def sample(self, generation, seed=0, n_children=None, out=None, wide=False):
         """The draw alone (rem2d_elites_sample): ``parents`` int32 ``[n_children]``, for each child the slot ``b C + q`` of a
@@ -240,7 +266,7 @@ class EliteGrid:
             out = torch.empty(n, dtype=torch.int32, device=self.device)
         e = self._descriptor(generation, seed)
         e.n_children, e.parent = n, out.data_ptr()
-        self._call("rem2d_elites_sample", e, wide)
+        self._launch("rem2d_elites_sample", e, wide)
         return out
 
     def emit(self, generation, seed=0, rate=0.05, sigma=0.1, n_children=None, out=None, wide=False):
@@ -251,43 +277,17 @@ class EliteGrid:
         n_children sets of the grid's shapes whose weights and ``.parents`` are overwritten and which is returned.
 
         Returns the child ``MLPPolicy`` with ``.parents`` int32 ``[n_children]`` (slots of the grid, or -1)."""
-        if out is not None:
-            self._fits("emit", out, None if n_children is None else int(n_children))
-            if n_children is None:
-                n_children = out.n_sets
-        have = None if out is None else out.parents
-        n = self._draw("emit", generation, seed, n_children, None)
+        n = self._emit_checks("emit", generation, seed, n_children, out)
         if not 0.0 <= float(rate) <= 1.0:
             raise ValueError("emit: rate must be in [0, 1], not %r" % (rate,))
         if self.device.type != "cuda":
             raise ValueError("emit: the grid is on %s; make it on the GPU (device=...)" % self.device)
-        dev = self.device
-        if out is None:
-            out = self.like._like(*(torch.zeros((n,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-                                     for t in (self.w1, self.b1, self.w2, self.b2)), None)
-        else:
-            out.activation, out.scale, out.rays = self.like.activation, self.like.scale, self.like.rays
-        if have is None or have.dtype != torch.int32 or tuple(have.shape) != (n,) or have.device != dev or not have.is_contiguous():
-            have = torch.empty(n, dtype=torch.int32, device=dev)
-        out.parents = have
+        out = self._emit_out(out, n, ("parents",))
         e = self._descriptor(generation, seed, rate, sigma)
-        e.n_children, e.parent = n, have.data_ptr()
-        e.child_w1, e.child_b1, e.child_w2, e.child_b2 = (t.data_ptr() for t in (out.w1, out.b1, out.w2, out.b2))
-        self._call("rem2d_elites_emit", e, wide)
+        e.n_children, e.parent = n, out.parents.data_ptr()
+        point(e, "child_", out.weights)
+        self._launch("rem2d_elites_emit", e, wide)
         return out
-
-    def _line_descriptor(self, generation, seed, sigma_iso, sigma_line):
-        v = _lib.Cvt()
-        v.d, v.hidden, v.max_bodies, v.width, v.n_cells, v.n_blocks = self.d, self.hidden, self.max_bodies, self.width, self.n_cells, self.n_blocks
-        v.generation, v.seed, v.sigma_iso, v.sigma_line, v.splits, v.reserved = int(generation), int(seed), float(sigma_iso), float(sigma_line), 0, 0
-        v.elite_fitness, v.elite_desc, v.count = self.fitness.data_ptr(), self.desc.data_ptr(), self.count.data_ptr()
-        v.elite_w1, v.elite_b1, v.elite_w2, v.elite_b2 = (t.data_ptr() for t in (self.w1, self.b1, self.w2, self.b2))
-        v.winner, v.n_filled = self.winner.data_ptr(), self.filled.data_ptr()
-        v.scratch, v.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel() * 8
-        return v
-
-    def _call_cvt(self, name, v, wide):
-        _call_cvt(name, v, self.device, wide)
 
     def emit_line(self, generation, seed=0, sigma_iso=0.01, sigma_line=0.2, n_children=None, out=None, wide=False):
         """The next children by the iso+line variation (rem2d_cvt_emit_line; Vassiliades & Mouret 2018): child c descends from TWO
@@ -297,38 +297,17 @@ class EliteGrid:
         block whose grid is empty keeps the words its buffer holds.  ``n_children``, ``out``: as ``emit``.
 
         Returns the child ``MLPPolicy`` with ``.parents`` and ``.parents2`` int32 ``[n_children]`` (slots of the grid, or -1)."""
-        if out is not None:
-            self._fits("emit_line", out, None if n_children is None else int(n_children))
-            if n_children is None:
-                n_children = out.n_sets
-        n = self._draw("emit_line", generation, seed, n_children, None)
+        n = self._emit_checks("emit_line", generation, seed, n_children, out)
         if not math.isfinite(float(sigma_iso)) or not math.isfinite(float(sigma_line)):
             raise ValueError("emit_line: sigma_iso and sigma_line must be finite, not %r, %r" % (sigma_iso, sigma_line))
         if self.device.type != "cuda":
             raise ValueError("emit_line: the grid is on %s; make it on the GPU (device=...)" % self.device)
-        dev = self.device
-        if out is None:
-            out = self.like._like(*(torch.zeros((n,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-                                     for t in (self.w1, self.b1, self.w2, self.b2)), None)
-        else:
-            out.activation, out.scale, out.rays = self.like.activation, self.like.scale, self.like.rays
-        for attr in ("parents", "parents2"):
-            have = getattr(out, attr, None)
-            if have is None or have.dtype != torch.int32 or tuple(have.shape) != (n,) or have.device != dev or not have.is_contiguous():
-                setattr(out, attr, torch.empty(n, dtype=torch.int32, device=dev))
+        out = self._emit_out(out, n, ("parents", "parents2"))
         v = self._line_descriptor(generation, seed, sigma_iso, sigma_line)
         v.n_children, v.parent, v.parent2 = n, out.parents.data_ptr(), out.parents2.data_ptr()
-        v.child_w1, v.child_b1, v.child_w2, v.child_b2 = (t.data_ptr() for t in (out.w1, out.b1, out.w2, out.b2))
-        self._call_cvt("rem2d_cvt_emit_line", v, wide)
+        point(v, "child_", out.weights)
+        self._launch("rem2d_cvt_emit_line", v, wide)
         return out
-
-
-def _call_cvt(name, v, device, wide):
-    """a call of include/rem2d_cvt.h: the stream is a member of the descriptor, not a parameter"""
-    L = _lib.lib(wide)
-    with torch.cuda.device(device):
-        v.stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(getattr(L, name)(C.byref(v)), wide)
 
 
 def assign_host(desc, centroids, chunk=None):
@@ -371,7 +350,7 @@ def _assign(what, desc, centroids, out, dist, scratch, wide=False, splits=0):
     _check_rows(what, desc, centroids.shape[1], dev)
     n = desc.shape[0]
     for name, t, dt in (("out", out, torch.int32), ("dist", dist, torch.float32)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != dev):
+        if t is not None and not is_tensor(t, dt, (n,), dev):
             raise ValueError("%s: %s must be a contiguous %s [%d] tensor on %s" % (what, name, dt, n, dev))
     if not 0 <= int(splits) <= _lib.CVT_MAX_SPLITS:
         raise ValueError("%s: splits must be 0 .. %d, not %r" % (what, _lib.CVT_MAX_SPLITS, splits))
@@ -389,7 +368,7 @@ def _assign(what, desc, centroids, out, dist, scratch, wide=False, splits=0):
     v.width, v.n_cells, v.n_rows, v.splits, v.reserved = centroids.shape[1], centroids.shape[0], n, int(splits), 0
     v.centroids, v.desc, v.cell, v.dist = centroids.data_ptr(), desc.data_ptr(), out.data_ptr(), None if dist is None else dist.data_ptr()
     v.scratch, v.scratch_bytes = scratch.data_ptr(), scratch.numel() * 8
-    _call_cvt("rem2d_cvt_assign", v, dev, wide)
+    launch(_lib.lib(wide).rem2d_cvt_assign, v, dev, wide, stream_member=True)
     return out, scratch
 
 
@@ -435,57 +414,25 @@ class CentroidArchive(EliteGrid):
         out, self._vscratch = _assign("assign", desc, self.centroids, out, dist, self._vscratch, wide, splits)
         return out
 
-    def insert(self, policy, fitness, desc, mask=None, group_size=None, wide=False):
-        """``EliteGrid.insert`` with the nearest centroid as the cell (rem2d_cvt_insert): the same arguments, checks and return.
-        A row is admitted iff it has a finite distance to some centroid, its fitness is not a NaN and the mask admits it;
-        ``self.cell`` int32 ``[G]`` holds the cells (-1: not admitted), ``self.dist`` float32 ``[G]`` every row's squared distance."""
+    _NOUN, _INSERT = "archive", "rem2d_cvt_insert"
+
+    def _insert_descriptor(self, G):
         dev = self.device
-        self._fits("insert", policy)
-        G = policy.n_sets
-        if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
-            raise ValueError("insert: fitness must be a torch.float64 tensor")
-        if tuple(fitness.shape) != (G,) or not fitness.is_contiguous() or fitness.device != dev:
-            raise ValueError("insert: fitness must be a contiguous tensor of one entry per weight set [%d] on %s, not %s" % (G, dev, list(fitness.shape)))
-        if not isinstance(desc, torch.Tensor) or desc.dtype != torch.float32:
-            raise ValueError("insert: desc must be a torch.float32 tensor")
-        if tuple(desc.shape) != (G, self.width) or not desc.is_contiguous() or desc.device != dev:
-            raise ValueError("insert: desc must be a contiguous tensor [%d, %d] on %s, not %s" % (G, self.width, dev, list(desc.shape)))
-        if group_size is None:
-            if G % self.n_blocks:
-                raise ValueError("insert: %d rows are not %d blocks of one group_size" % (G, self.n_blocks))
-            group_size = G // self.n_blocks
-        S = int(group_size)
-        if S < 1 or S * self.n_blocks != G:
-            raise ValueError("insert: %d rows in groups of %r are not the archive's %d blocks" % (G, group_size, self.n_blocks))
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
-                raise ValueError("insert: mask must be a torch.bool or torch.uint8 tensor")
-            if tuple(mask.shape) != (G,) or not mask.is_contiguous() or mask.device != dev:
-                raise ValueError("insert: mask must be a contiguous tensor of one entry per row [%d] on %s, not %s" % (G, dev, list(mask.shape)))
-        for name, other in (("fitness", self.fitness), ("desc", self.desc), ("count", self.count), ("w1", self.w1), ("b1", self.b1),
-                            ("w2", self.w2), ("b2", self.b2), ("centroids", self.centroids)):
-            a, an = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
-            b, bn = desc.data_ptr(), desc.data_ptr() + desc.numel() * 4
-            if a < bn and b < an:
-                raise ValueError("insert: desc shares memory with the archive's %s" % name)
-        if dev.type != "cuda":
-            raise ValueError("insert: the archive is on %s; make it on the GPU (device=...)" % dev)
-        if self.cell is None or tuple(self.cell.shape) != (G,):
-            self.cell = torch.empty(G, dtype=torch.int32, device=dev)
         if self.dist is None or tuple(self.dist.shape) != (G,):
             self.dist = torch.empty(G, dtype=torch.float32, device=dev)
         need = (12 * self.n_blocks * self.n_cells + 8 * G + 7) // 8
         if self._vscratch is None or self._vscratch.numel() < need:
             self._vscratch = torch.empty(need, dtype=torch.int64, device=dev)
         v = self._line_descriptor(0, 0, 0.0, 0.0)
-        v.group_size = S
-        v.centroids, v.desc, v.fitness, v.mask = self.centroids.data_ptr(), desc.data_ptr(), fitness.data_ptr(), None if mask is None else mask.data_ptr()
-        v.w1, v.b1, v.w2, v.b2 = (t.data_ptr() for t in (policy.w1, policy.b1, policy.w2, policy.b2))
-        v.cell, v.dist = self.cell.data_ptr(), self.dist.data_ptr()
+        v.centroids, v.dist = self.centroids.data_ptr(), self.dist.data_ptr()
         v.scratch, v.scratch_bytes = self._vscratch.data_ptr(), self._vscratch.numel() * 8
-        self._keep = (policy, fitness, desc, mask)          # (the tensors the queued kernels read)
-        self._call_cvt("rem2d_cvt_insert", v, wide)
-        return self.winner
+        return v
+
+    def insert(self, policy, fitness, desc, mask=None, group_size=None, wide=False):
+        """``EliteGrid.insert`` with the nearest centroid as the cell (rem2d_cvt_insert): the same arguments, checks and return.
+        A row is admitted iff it has a finite distance to some centroid, its fitness is not a NaN and the mask admits it;
+        ``self.cell`` int32 ``[G]`` holds the cells (-1: not admitted), ``self.dist`` float32 ``[G]`` every row's squared distance."""
+        return super().insert(policy, fitness, desc, mask, group_size, wide)
 
 
 def cvt_centroids(n_cells, lo, hi, n_samples=None, iterations=10, seed=0, device=None, wide=False):

@@ -8,17 +8,10 @@ the root position sampled K times over the episode -- and ``evaluate.run_behavio
 
 Nothing here allocates after ``NoveltyArchive`` was made and ``out=`` is given; every call is one library call queued on the current
 stream; nothing synchronises.  tests/novelty_model.py restates every output bit in numpy."""
-import ctypes as C
-import math
-
 import torch
 
 from . import _lib
-
-
-def rate_threshold(rate):
-    """floor(rate * 2^32), the ``add_threshold`` of a rate in [0, 1] (the product of a binary64 by 2^32 is exact)"""
-    return int(math.floor(float(rate) * 4294967296.0))
+from ._tier import draw_ok, is_tensor, launch, overlaps, rate_threshold      # (rate_threshold, here the ``add_threshold``, is a public name of this module too)
 
 
 class NoveltyArchive:
@@ -76,25 +69,19 @@ class NoveltyArchive:
             raise ValueError("%s: %d rows in groups of %r are not the archive's %d blocks" % (what, G, group_size, self.n_blocks))
         if not 1 <= int(k) <= _lib.NOVELTY_MAX_K:
             raise ValueError("%s: k must be 1 .. %d, not %r" % (what, _lib.NOVELTY_MAX_K, k))
-        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError("%s: generation must fit 32 bits and seed 64 (unsigned)" % what)
+        draw_ok(what, generation, seed)
         if not 0.0 <= float(rate) <= 1.0:
             raise ValueError("%s: rate must be in [0, 1], not %r" % (what, rate))
         if mask is not None:
             if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
                 raise ValueError("%s: mask must be a torch.bool or torch.uint8 tensor" % what)
-            if tuple(mask.shape) != (G,) or not mask.is_contiguous() or mask.device != dev:
+            if not is_tensor(mask, (torch.bool, torch.uint8), (G,), dev):
                 raise ValueError("%s: mask must be a contiguous tensor of one entry per row [%d] on %s, not %s" % (what, G, dev, list(mask.shape)))
-        if out is not None:
-            if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (G,) or not out.is_contiguous()
-                    or out.device != dev):
-                raise ValueError("%s: out must be a contiguous torch.float64 [%d] tensor on %s" % (what, G, dev))
+        if out is not None and not is_tensor(out, torch.float64, (G,), dev):
+            raise ValueError("%s: out must be a contiguous torch.float64 [%d] tensor on %s" % (what, G, dev))
         for name, other in (("the archive's entries", self.entries), ("out", out)):
-            if other is not None and other.numel() and desc.numel():
-                a, an = other.data_ptr(), other.data_ptr() + other.numel() * other.element_size()
-                b, bn = desc.data_ptr(), desc.data_ptr() + desc.numel() * 4
-                if a < bn and b < an:
-                    raise ValueError("%s: desc shares memory with %s" % (what, name))
+            if other is not None and overlaps(other, desc):
+                raise ValueError("%s: desc shares memory with %s" % (what, name))
         if dev.type != "cuda":
             raise ValueError("%s: the archive is on %s; make it on the GPU (device=...)" % (what, dev))
         if want_out and out is None:
@@ -109,11 +96,6 @@ class NoveltyArchive:
         n.add_mask = None if mask is None else mask.data_ptr()
         return n, out
 
-    def _call(self, name, n, wide):
-        L = _lib.lib(wide)
-        with torch.cuda.device(self.device):
-            _lib.check(getattr(L, name)(C.byref(n), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), wide)
-
     def score(self, desc, k=15, group_size=None, out=None, wide=False):
         """novelty float64 ``[G]``: for every row of ``desc`` (float32 ``[G, width]`` on the archive's device) the mean Euclidean
         distance to its ``k`` nearest neighbours among the other rows of its block and the block's live archive entries
@@ -121,7 +103,7 @@ class NoveltyArchive:
         over those there are, 0.0 for none; candidates at a non-finite distance are ignored; a row with a non-finite word scores
         NaN, which ``evolve`` and the rank shaping put lowest.  ``out``: a contiguous float64 ``[G]`` tensor to write into."""
         n, out = self._descriptor("score", desc, group_size, k=k, out=out, want_out=True)
-        self._call("rem2d_novelty_score", n, wide)
+        launch(_lib.lib(wide).rem2d_novelty_score, n, self.device, wide)
         return out
 
     def add(self, desc, generation, seed=0, rate=0.02, mask=None, group_size=None, wide=False):
@@ -130,7 +112,7 @@ class NoveltyArchive:
         falls below ``rate`` -- a function of those alone, so a replay adds the same rows.  Returns ``total``."""
         n, _ = self._descriptor("add", desc, group_size, generation=generation, seed=seed, rate=rate, mask=mask)
         self._mask = mask   # (the tensor the queued kernel reads)
-        self._call("rem2d_novelty_add", n, wide)
+        launch(_lib.lib(wide).rem2d_novelty_add, n, self.device, wide)
         return self.total
 
     def step(self, desc, generation, k=15, seed=0, rate=0.02, mask=None, group_size=None, out=None, wide=False):
@@ -139,7 +121,7 @@ class NoveltyArchive:
         n, out = self._descriptor("step", desc, group_size, k=k, out=out, want_out=True, generation=generation, seed=seed, rate=rate,
                                   mask=mask)
         self._mask = mask
-        self._call("rem2d_novelty_step", n, wide)
+        launch(_lib.lib(wide).rem2d_novelty_step, n, self.device, wide)
         return out
 
 

@@ -9,26 +9,19 @@ competition: among a row's nearest behavioural neighbours, how many it out-perfo
 Every ValueError comes before anything is allocated; every call is one library call queued on the current stream; nothing
 synchronises.  tests/pareto_model.py restates every output bit in numpy."""
 import collections
-import ctypes as C
 
 import torch
 
 from . import _lib
+from ._tier import is_tensor, launch, overlaps
 
 ParetoRank = collections.namedtuple("ParetoRank", "front crowd util n_fronts")
 RANK_OUT = (("front", torch.int32), ("crowd", torch.float64), ("util", torch.int32), ("n_fronts", torch.int32))
 
 
-def _span(t):
-    return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
-
-
 def _disjoint(what, out_name, out, in_name, inp):
-    if out.numel() and inp.numel():
-        a, an = _span(out)
-        b, bn = _span(inp)
-        if a < bn and b < an:
-            raise ValueError("%s: %s shares memory with %s" % (what, out_name, in_name))
+    if overlaps(out, inp):
+        raise ValueError("%s: %s shares memory with %s" % (what, out_name, in_name))
 
 
 def _groups(what, G, group_size, limit=None):
@@ -36,12 +29,6 @@ def _groups(what, G, group_size, limit=None):
     if S < 1 or G % S or (limit is not None and S > limit):
         raise ValueError("%s: group_size must be 1 .. %s and divide the %d rows, not %r" % (what, "any" if limit is None else limit, G, group_size))
     return S
-
-
-def _call(name, p, dev, wide):
-    L = _lib.lib(wide)
-    with torch.cuda.device(dev):
-        _lib.check(getattr(L, name)(C.byref(p), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
 
 
 def rank(objectives, group_size=None, out=None, wide=False):
@@ -74,7 +61,7 @@ def rank(objectives, group_size=None, out=None, wide=False):
             if o is None:
                 continue
             n = G // S if name == "n_fronts" else G
-            if not isinstance(o, torch.Tensor) or o.dtype != dtype or tuple(o.shape) != (n,) or not o.is_contiguous() or o.device != dev:
+            if not is_tensor(o, dtype, (n,), dev):
                 raise ValueError("%s: out.%s must be a contiguous %s [%d] tensor on %s" % (what, name, dtype, n, dev))
             _disjoint(what, "out." + name, o, "objectives", objectives)
     if dev.type != "cuda":
@@ -85,7 +72,7 @@ def rank(objectives, group_size=None, out=None, wide=False):
     p.n_rows, p.group_size, p.n_obj, p.reserved = G, S, K, 0
     p.obj = objectives.data_ptr()
     p.front, p.crowd, p.util, p.n_fronts = (None if o is None else o.data_ptr() for o in out)
-    _call("rem2d_pareto_rank", p, dev, wide)
+    launch(_lib.lib(wide).rem2d_pareto_rank, p, dev, wide)
     return ParetoRank(*out)
 
 
@@ -105,15 +92,13 @@ def local_competition(desc, fitness, k=15, group_size=None, out=None, wide=False
     dev = desc.device
     if G > 2 ** 31 - 1:
         raise ValueError("%s: more than 2^31 - 1 rows" % what)
-    if (not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64 or tuple(fitness.shape) != (G,) or not fitness.is_contiguous()
-            or fitness.device != dev):
+    if not is_tensor(fitness, torch.float64, (G,), dev):
         raise ValueError("%s: fitness must be a contiguous torch.float64 [%d] tensor on %s" % (what, G, dev))
     if not 1 <= int(k) <= _lib.PARETO_MAX_K:
         raise ValueError("%s: k must be 1 .. %d, not %r" % (what, _lib.PARETO_MAX_K, k))
     S = _groups(what, G, group_size)
     if out is not None:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (G,) or not out.is_contiguous()
-                or out.device != dev):
+        if not is_tensor(out, torch.float64, (G,), dev):
             raise ValueError("%s: out must be a contiguous torch.float64 [%d] tensor on %s" % (what, G, dev))
         _disjoint(what, "out", out, "desc", desc)
         _disjoint(what, "out", out, "fitness", fitness)
@@ -124,5 +109,5 @@ def local_competition(desc, fitness, k=15, group_size=None, out=None, wide=False
     p = _lib.Pareto()
     p.n_rows, p.group_size, p.width, p.k, p.reserved = G, S, B, int(k), 0
     p.desc, p.fitness, p.local, p.neighbours = desc.data_ptr(), fitness.data_ptr(), out.data_ptr(), None
-    _call("rem2d_pareto_local", p, dev, wide)
+    launch(_lib.lib(wide).rem2d_pareto_local, p, dev, wide)
     return out

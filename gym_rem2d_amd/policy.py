@@ -12,13 +12,12 @@ every build of the library: what a policy computes is as reproducible as a step.
 ``RecurrentPolicy`` is the same controller with memory (include/rem2d_recurrent.h): K of its hidden activations are
 input words of the next step, carried per creature in device memory that its own kernel reads and rewrites in place.
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from . import _lib, control, sense
+from . import _lib, _tier, control, sense
 
 ABI_VERSION = _lib.POLICY_ABI_VERSION
 MAX_HIDDEN = _lib.POLICY_MAX_HIDDEN
@@ -42,6 +41,31 @@ def _f32(t, what, dims):
     if t.dim() != dims:
         raise ValueError("%s must have %d axes ([G, ...]), not shape %r" % (what, dims, tuple(t.shape)))
     return t.contiguous()
+
+
+def _check_fitness(what, fitness, n, per, dev):
+    """``fitness`` as a kernel reads it: float64 ``[n]`` (one entry per ``per``), contiguous, on ``dev``"""
+    if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
+        raise ValueError("%s: fitness must be a torch.float64 tensor" % what)
+    if tuple(fitness.shape) != (n,) or not fitness.is_contiguous():
+        raise ValueError("%s: fitness must be a contiguous tensor of one entry per %s [%d], not %s" % (what, per, n, list(fitness.shape)))
+    if fitness.device != dev:
+        raise ValueError("%s: fitness must be on %s, not %s" % (what, dev, fitness.device))
+
+
+def _check_ranked(what, fitness, util, n, dev):
+    """What an update is ranked by: the children's ``fitness``, or the caller's ``util`` int32 ``[n]``, beside which fitness is not
+    looked at"""
+    if util is None:
+        _check_fitness(what, fitness, n, "child", dev)
+    elif not _tier.is_tensor(util, torch.int32, (n,), dev):
+        raise ValueError("%s: util must be a contiguous torch.int32 [%d] tensor on %s" % (what, n, dev))
+
+
+def _check_scratch(what, scratch, need, dev):
+    """The caller's ``scratch``, if any: int64, contiguous, on ``dev``, of at least ``need`` bytes"""
+    if scratch is not None and (not _tier.is_tensor(scratch, torch.int64, None, dev) or scratch.numel() * 8 < need):
+        raise ValueError("%s: scratch must be a contiguous torch.int64 tensor of at least %d entries on %s" % (what, need // 8, dev))
 
 
 class MLPPolicy:
@@ -108,17 +132,61 @@ class MLPPolicy:
     def random(cls, n_sets, max_bodies, hidden, n_rays=10, seed=0, std=(0.3, 0.3, 0.5, 0.3), **kw):
         """n_sets controllers with normal weights: w1, b1, w2, b2 drawn in that order from ``numpy.random.default_rng(seed)``, scaled
         by ``std`` (one number, or one per array).  Keyword arguments go to the constructor."""
+        return cls._random(n_sets, max_bodies, hidden, n_rays, seed, std, kw)
+
+    @classmethod
+    def _random(cls, n_sets, max_bodies, hidden, n_rays, seed, std, kw, more_rows=0, more_args=()):
+        """``random`` of this class and of its subclasses: w1 has ``more_rows`` input rows beyond those of ``n_rays`` rays, and the
+        constructor takes ``more_args`` after the four arrays."""
         std = (float(std),) * 4 if np.isscalar(std) else tuple(float(s) for s in std)
         rng = np.random.default_rng(seed)
-        D = input_width(max_bodies, n_rays)
+        D = input_width(max_bodies, n_rays) + more_rows
         shapes = ((n_sets, D, hidden), (n_sets, hidden), (n_sets, hidden, max_bodies), (n_sets, max_bodies))
         arrays = [torch.from_numpy((rng.standard_normal(s) * sd).astype(np.float32)) for s, sd in zip(shapes, std)]
         if n_rays not in (0, 10) and "rays" not in kw:
             kw["rays"] = sense.bipedal_rays(n_rays)
-        return cls(*arrays, **kw)
+        return cls(*arrays, *more_args, **kw)
 
     def _like(self, w1, b1, w2, b2, index):
         return MLPPolicy(w1, b1, w2, b2, self.activation, self.scale, index, self.rays)
+
+    @property
+    def weights(self):
+        """(w1, b1, w2, b2)"""
+        return self.w1, self.b1, self.w2, self.b2
+
+    def _shapes(self, n):
+        """the shapes of w1, b1, w2, b2 of ``n`` sets of this policy's per-set shapes"""
+        D, H, MB = self.d, self.hidden, self.max_bodies
+        return (n, D, H), (n, H), (n, H, MB), (n, MB)
+
+    def _sets(self, n, zeroed=False, device=None):
+        """A policy like this one of ``n`` new weight sets of its per-set shapes, uninitialised or ``zeroed``, on its device or on
+        ``device``"""
+        make = torch.zeros if zeroed else torch.empty
+        dev = self.device if device is None else device
+        return self._like(*(make(shape, dtype=torch.float32, device=dev) for shape in self._shapes(n)), None)
+
+    def _adopt(self, out):
+        """``out``, a policy the caller gave to be overwritten, with this policy's activation, scale and rays"""
+        out.activation, out.scale, out.rays = self.activation, self.scale, self.rays
+        return out
+
+    def _out_ok(self, what, out, n_sets, than, shapes, shares):
+        """``out`` checked as the destination of n_sets sets of this policy's per-set shapes that shares no memory with it; the
+        caller's wording: out must be another MLPPolicy than ``than``, must have ``shapes``, shares memory with ``shares``."""
+        if out is self or not isinstance(out, MLPPolicy):
+            raise ValueError("%s: out must be another MLPPolicy than %s" % (what, than))
+        dev = self.device
+        if out.index is not None or any(a.shape != shape or a.device != dev for a, shape in zip(out.weights, self._shapes(n_sets))):
+            raise ValueError("%s: out must have %s, and no index" % (what, shapes))
+        if _tier.overlaps(out.weights, self.weights):    # (the library checks it too; here the message can name the argument)
+            raise ValueError("%s: out shares memory with %s" % (what, shares))
+
+    def _targets(self, n_rows):
+        """New zeroed ``(targets float64 [n_rows, max_bodies], valid uint8 [n_rows, max_bodies])`` for ``forward`` to write"""
+        return (torch.zeros((n_rows, self.max_bodies), dtype=torch.float64, device=self.device),
+                torch.zeros((n_rows, self.max_bodies), dtype=torch.uint8, device=self.device))
 
     def take(self, indices):
         """The policy of a selection: weight sets ``indices`` (repeats allowed), in that order, one per creature -- what an EA's
@@ -151,7 +219,7 @@ class MLPPolicy:
         dev, N = self.device, int(obs.shape[0])
 
         def ok(t, dtype, shape, what):
-            if t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape:
+            if not _tier.is_tensor(t, dtype, shape, dev):
                 raise ValueError("policy: %s must be a contiguous %s %r tensor on %s" % (what, dtype, shape, dev))
         if dev.type != "cuda":
             raise ValueError("policy: the weights are on %s; move the policy to the GPU with .to(device)" % dev)
@@ -169,7 +237,7 @@ class MLPPolicy:
         p = _lib.Policy()
         p.d, p.max_bodies, p.n_rays, p.hidden = self.d, self.max_bodies, self.n_rays, self.hidden
         p.activation, p.scale, p.n_sets, p.reserved = ACTIVATIONS.index(self.activation), self.scale, self.n_sets, 0
-        p.w1, p.b1, p.w2, p.b2 = (t.data_ptr() for t in (self.w1, self.b1, self.w2, self.b2))
+        _tier.point(p, "", self.weights)
         p.index = None if self.index is None else self.index.data_ptr()
         p.row_mask = None if row_mask is None else row_mask.data_ptr()
         p.obs, p.frac = obs.data_ptr(), (frac.data_ptr() if self.n_rays else None)
@@ -181,14 +249,10 @@ class MLPPolicy:
         float32 ``[N, R]`` (None when R is 0) -> ``(targets float64 [N, max_bodies], valid uint8 [N, max_bodies])``.  ``out``: that
         pair to write into (rows a ``row_mask`` uint8 ``[N]`` clears, or whose index names no weight set, keep what they hold);
         without it new zeroed tensors.  ``wide``: the build whose kernel runs (all three write the same bits)."""
-        N = int(obs.shape[0])
         if out is None:
-            out = (torch.zeros((N, self.max_bodies), dtype=torch.float64, device=self.device),
-                   torch.zeros((N, self.max_bodies), dtype=torch.uint8, device=self.device))
+            out = self._targets(int(obs.shape[0]))
         p = self.descriptor(obs, frac, out[0], out[1], row_mask)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib(wide).rem2d_policy_forward(C.byref(p), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                       wide)
+        _tier.launch(_lib.lib(wide).rem2d_policy_forward, p, self.device, wide)
         return out
 
     # ---- the next generation (include/rem2d_evolve.h) ----
@@ -210,12 +274,7 @@ class MLPPolicy:
         dev, G = self.device, self.n_sets
         if self.index is not None:
             raise ValueError("evolve: a policy with an index shares weight sets among creatures; evolve the sets of take() instead")
-        if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
-            raise ValueError("evolve: fitness must be a torch.float64 tensor")
-        if tuple(fitness.shape) != (G,) or not fitness.is_contiguous():
-            raise ValueError("evolve: fitness must be a contiguous tensor of one entry per weight set [%d], not %s" % (G, list(fitness.shape)))
-        if fitness.device != dev:
-            raise ValueError("evolve: fitness must be on %s, not %s" % (dev, fitness.device))
+        _check_fitness("evolve", fitness, G, "weight set", dev)
         S = G if group_size is None else int(group_size)
         if S < 1 or G % S:
             raise ValueError("evolve: group_size must divide the %d weight sets, not %d" % (G, S))
@@ -225,31 +284,15 @@ class MLPPolicy:
             raise ValueError("evolve: elite must be 0 or 1, not %r" % (elite,))
         if not 0.0 <= float(rate) <= 1.0:
             raise ValueError("evolve: rate must be in [0, 1], not %r" % (rate,))
-        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError("evolve: generation must fit 32 bits and seed 64 (unsigned)")
-        if parents is not None:
-            if (not isinstance(parents, torch.Tensor) or parents.dtype != torch.int32 or tuple(parents.shape) != (G,)
-                    or not parents.is_contiguous() or parents.device != dev):
-                raise ValueError("evolve: parents must be a contiguous torch.int32 [%d] tensor on %s" % (G, dev))
-        mine = (self.w1, self.b1, self.w2, self.b2)
+        _tier.draw_ok("evolve", generation, seed)
+        if parents is not None and not _tier.is_tensor(parents, torch.int32, (G,), dev):
+            raise ValueError("evolve: parents must be a contiguous torch.int32 [%d] tensor on %s" % (G, dev))
         if out is not None:
-            if out is self or not isinstance(out, MLPPolicy):
-                raise ValueError("evolve: out must be another MLPPolicy than the one that is evolved")
-            theirs = (out.w1, out.b1, out.w2, out.b2)
-            if out.index is not None or any(a.shape != b.shape or a.device != b.device for a, b in zip(mine, theirs)):
-                raise ValueError("evolve: out must have this policy's shapes and device, and no index")
-            for a in theirs:            # (the library checks it too; here the message can name the argument)
-                for b in mine:
-                    if a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
-                        raise ValueError("evolve: out shares memory with the policy that is evolved")
+            self._out_ok("evolve", out, G, "the one that is evolved", "this policy's shapes and device", "the policy that is evolved")
         if dev.type != "cuda":
             raise ValueError("evolve: the weights are on %s; move the policy to the GPU with .to(device)" % dev)
-        if out is None:             # (with parents= a skipped child keeps what its buffer held: zeros)
-            kids = tuple(torch.empty_like(t) for t in mine) if parents is None else tuple(torch.zeros_like(t) for t in mine)
-            child = self._like(*kids, None)
-        else:
-            child = out
-            child.activation, child.scale, child.rays = self.activation, self.scale, self.rays
+        # (with parents= a skipped child keeps what its buffer held: zeros)
+        child = self._sets(G, zeroed=parents is not None) if out is None else self._adopt(out)
         if parents is not None:
             child.parents = parents
         elif child.parents is None or child.parents is self.parents:
@@ -257,15 +300,13 @@ class MLPPolicy:
         e = _lib.Evolve()
         e.d, e.hidden, e.max_bodies, e.n_sets, e.group_size = self.d, self.hidden, self.max_bodies, G, S
         e.tournsize, e.elite, e.generation = int(tournsize), int(elite), int(generation)
-        e.rate_threshold, e.seed, e.sigma, e.reserved = int(math.floor(float(rate) * 4294967296.0)), int(seed), float(sigma), 0
+        e.rate_threshold, e.seed, e.sigma, e.reserved = _tier.rate_threshold(rate), int(seed), float(sigma), 0
         e.fitness = fitness.data_ptr()
-        e.w1, e.b1, e.w2, e.b2 = (t.data_ptr() for t in mine)
-        e.child_w1, e.child_b1, e.child_w2, e.child_b2 = (t.data_ptr() for t in (child.w1, child.b1, child.w2, child.b2))
+        _tier.point(e, "", self.weights)
+        _tier.point(e, "child_", child.weights)
         e.parent = child.parents.data_ptr()
         L = _lib.lib(wide)
-        call = L.rem2d_policy_evolve if parents is None else L.rem2d_policy_vary
-        with torch.cuda.device(dev):
-            _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
+        _tier.launch(L.rem2d_policy_evolve if parents is None else L.rem2d_policy_vary, e, dev, wide)
         return child
 
     # ---- an evolution strategy around this policy as the mean (include/rem2d_es.h) ----
@@ -277,8 +318,7 @@ class MLPPolicy:
             raise ValueError("%s: group_size (children per mean) must be even and at least 2, not %r" % (what, group_size))
         if self.n_sets * int(group_size) > 2 ** 31 - 1:
             raise ValueError("%s: %d means of group_size %d are more than 2^31 - 1 children" % (what, self.n_sets, int(group_size)))
-        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError("%s: generation must fit 32 bits and seed 64 (unsigned)" % what)
+        _tier.draw_ok(what, generation, seed)
         if int(pair_chunk) < 0:
             raise ValueError("%s: pair_chunk must be at least 0, not %r" % (what, pair_chunk))
         e = _lib.Es()
@@ -287,25 +327,13 @@ class MLPPolicy:
         return e
 
     def _es_out(self, what, out, n_sets):
-        """``out`` checked as the destination of n_sets sets of this policy's per-set shapes that shares no memory with it."""
-        mine = (self.w1, self.b1, self.w2, self.b2)
-        if out is self or not isinstance(out, MLPPolicy):
-            raise ValueError("%s: out must be another MLPPolicy than the mean" % what)
-        theirs = (out.w1, out.b1, out.w2, out.b2)
-        if out.index is not None or any(tuple(a.shape) != (n_sets,) + tuple(b.shape[1:]) or a.device != b.device for a, b in zip(theirs, mine)):
-            raise ValueError("%s: out must have %d sets of this policy's shapes on its device, and no index" % (what, n_sets))
-        for a in theirs:            # (the library checks it too; here the message can name the argument)
-            for b in mine:
-                if a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
-                    raise ValueError("%s: out shares memory with the mean" % what)
+        """``_out_ok`` in the words of a strategy, whose mean this policy is"""
+        self._out_ok(what, out, n_sets, "the mean", "%d sets of this policy's shapes on its device" % n_sets, "the mean")
 
     def es_scratch_bytes(self, group_size, pair_chunk=0, wide=False):
         """Bytes of scratch that ``es_update`` needs for this mean (rem2d_es_scratch_bytes); 0 where the update is one launch."""
         e = self._es_descriptor("es_scratch_bytes", 0, 0, group_size, pair_chunk)
-        n = int(_lib.lib(wide).rem2d_es_scratch_bytes(C.byref(e)))
-        if n < 0:
-            _lib.check(n, wide)
-        return n
+        return _tier.scratch_bytes(_lib.lib(wide).rem2d_es_scratch_bytes, e, wide)
 
     def es_sample(self, generation, seed=0, sigma=0.1, group_size=None, out=None, wide=False):
         """The children of one generation of an evolution strategy whose mean this policy is: ``group_size`` = S sets around each
@@ -323,17 +351,11 @@ class MLPPolicy:
             self._es_out("es_sample", out, G)
         if self.device.type != "cuda":
             raise ValueError("es_sample: the weights are on %s; move the policy to the GPU with .to(device)" % self.device)
-        mine = (self.w1, self.b1, self.w2, self.b2)
-        if out is None:
-            child = self._like(*(torch.empty((G,) + tuple(t.shape[1:]), dtype=torch.float32, device=self.device) for t in mine), None)
-        else:
-            child = out
-            child.activation, child.scale, child.rays = self.activation, self.scale, self.rays
+        child = self._sets(G) if out is None else self._adopt(out)
         e.sigma = float(sigma)
-        e.w1, e.b1, e.w2, e.b2 = (t.data_ptr() for t in mine)
-        e.child_w1, e.child_b1, e.child_w2, e.child_b2 = (t.data_ptr() for t in (child.w1, child.b1, child.w2, child.b2))
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib(wide).rem2d_es_sample(C.byref(e), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), wide)
+        _tier.point(e, "", self.weights)
+        _tier.point(e, "child_", child.weights)
+        _tier.launch(_lib.lib(wide).rem2d_es_sample, e, self.device, wide)
         return child
 
     def es_update(self, fitness, generation, seed=0, sigma=0.1, lr=0.05, group_size=None, out=None, scratch=None, util=None,
@@ -355,32 +377,16 @@ class MLPPolicy:
         e = self._es_descriptor("es_update", generation, seed, group_size, pair_chunk)
         S = e.group_size
         G = self.n_sets * S
-        if util is None:
-            if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
-                raise ValueError("es_update: fitness must be a torch.float64 tensor")
-            if tuple(fitness.shape) != (G,) or not fitness.is_contiguous():
-                raise ValueError("es_update: fitness must be a contiguous tensor of one entry per child [%d], not %s" % (G, list(fitness.shape)))
-            if fitness.device != dev:
-                raise ValueError("es_update: fitness must be on %s, not %s" % (dev, fitness.device))
-        elif (not isinstance(util, torch.Tensor) or util.dtype != torch.int32 or tuple(util.shape) != (G,) or not util.is_contiguous()
-              or util.device != dev):
-            raise ValueError("es_update: util must be a contiguous torch.int32 [%d] tensor on %s" % (G, dev))
+        _check_ranked("es_update", fitness, util, G, dev)
         if not float(sigma) > 0.0 or not math.isfinite(float(sigma)):
             raise ValueError("es_update: sigma must be positive and finite, not %r" % (sigma,))
         need = self.es_scratch_bytes(S, pair_chunk, wide)
-        if scratch is not None and (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.int64 or not scratch.is_contiguous()
-                                    or scratch.device != dev or scratch.numel() * 8 < need):
-            raise ValueError("es_update: scratch must be a contiguous torch.int64 tensor of at least %d entries on %s" % (need // 8, dev))
+        _check_scratch("es_update", scratch, need, dev)
         if out is not None:
             self._es_out("es_update", out, self.n_sets)
         if dev.type != "cuda":
             raise ValueError("es_update: the weights are on %s; move the policy to the GPU with .to(device)" % dev)
-        mine = (self.w1, self.b1, self.w2, self.b2)
-        if out is None:
-            new = self._like(*(torch.empty_like(t) for t in mine), None)
-        else:
-            new = out
-            new.activation, new.scale, new.rays = self.activation, self.scale, self.rays
+        new = self._sets(self.n_sets) if out is None else self._adopt(out)
         if util is not None:
             new.util = util
         elif new.util is None or tuple(new.util.shape) != (G,) or new.util.device != dev or new.util is self.util:
@@ -391,13 +397,11 @@ class MLPPolicy:
         e.step = float(np.float32(float(lr) / (2.0 * (S - 1) * S * float(sigma))))
         e.fitness = None if util is not None else fitness.data_ptr()
         e.util = new.util.data_ptr()
-        e.w1, e.b1, e.w2, e.b2 = (t.data_ptr() for t in mine)
-        e.new_w1, e.new_b1, e.new_w2, e.new_b2 = (t.data_ptr() for t in (new.w1, new.b1, new.w2, new.b2))
+        _tier.point(e, "", self.weights)
+        _tier.point(e, "new_", new.weights)
         e.scratch, e.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel() * 8)
         L = _lib.lib(wide)
-        call = L.rem2d_es_step if util is None else L.rem2d_es_update
-        with torch.cuda.device(dev):
-            _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
+        _tier.launch(L.rem2d_es_step if util is None else L.rem2d_es_update, e, dev, wide)
         return new
 
 
@@ -431,14 +435,7 @@ class RecurrentPolicy(MLPPolicy):
     def random(cls, n_sets, max_bodies, hidden, context, n_rays=10, seed=0, std=(0.3, 0.3, 0.5, 0.3), **kw):
         """As ``MLPPolicy.random``, with ``context`` more input rows in w1: the same draw as an ``MLPPolicy`` of
         ``n_rays + context`` rays."""
-        std = (float(std),) * 4 if np.isscalar(std) else tuple(float(s) for s in std)
-        rng = np.random.default_rng(seed)
-        D = input_width(max_bodies, n_rays) + int(context)
-        shapes = ((n_sets, D, hidden), (n_sets, hidden), (n_sets, hidden, max_bodies), (n_sets, max_bodies))
-        arrays = [torch.from_numpy((rng.standard_normal(s) * sd).astype(np.float32)) for s, sd in zip(shapes, std)]
-        if n_rays not in (0, 10) and "rays" not in kw:
-            kw["rays"] = sense.bipedal_rays(n_rays)
-        return cls(*arrays, context, **kw)
+        return cls._random(n_sets, max_bodies, hidden, n_rays, seed, std, kw, int(context), (context,))
 
     def _like(self, w1, b1, w2, b2, index):
         return RecurrentPolicy(w1, b1, w2, b2, self.context, self.activation, self.scale, index, self.rays)
@@ -453,11 +450,9 @@ class RecurrentPolicy(MLPPolicy):
         ``reset`` uint8 or bool ``[N]`` or None)."""
         p = super().descriptor(obs, frac, targets, valid, row_mask)
         dev, N = self.device, int(obs.shape[0])
-        if (not isinstance(memory, torch.Tensor) or memory.dtype != torch.float32 or not memory.is_contiguous() or memory.device != dev
-                or tuple(memory.shape) != (N, self.context)):
+        if not _tier.is_tensor(memory, torch.float32, (N, self.context), dev):
             raise ValueError("policy: memory must be a contiguous torch.float32 %r tensor on %s" % ((N, self.context), dev))
-        if reset is not None and (not isinstance(reset, torch.Tensor) or reset.dtype not in (torch.uint8, torch.bool)
-                                  or not reset.is_contiguous() or reset.device != dev or tuple(reset.shape) != (N,)):
+        if reset is not None and not _tier.is_tensor(reset, (torch.uint8, torch.bool), (N,), dev):
             raise ValueError("policy: reset must be a contiguous torch.uint8 or torch.bool %r tensor on %s" % ((N,), dev))
         q = _lib.Recurrent()
         q.p, q.context, q.reserved = p, self.context, 0
@@ -470,14 +465,10 @@ class RecurrentPolicy(MLPPolicy):
         overwritten IN PLACE with this step's first ``context`` hidden activations; ``reset`` uint8 / bool ``[N]``: a row whose
         entry is set reads +0 for its context whatever memory holds (a new episode).  A row that is skipped keeps its memory too.
         Returns ``(targets, valid)``."""
-        N = int(obs.shape[0])
         if out is None:
-            out = (torch.zeros((N, self.max_bodies), dtype=torch.float64, device=self.device),
-                   torch.zeros((N, self.max_bodies), dtype=torch.uint8, device=self.device))
+            out = self._targets(int(obs.shape[0]))
         q = self.descriptor(obs, frac, out[0], out[1], memory, reset, row_mask)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib(wide).rem2d_recurrent_forward(C.byref(q), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                       wide)
+        _tier.launch(_lib.lib(wide).rem2d_recurrent_forward, q, self.device, wide)
         return out
 
 
@@ -528,9 +519,9 @@ class SeparableES:
         self.group_size, self.sigma0, self.lr, self.lr_sigma = S, float(sigma), float(lr), float(lr_sigma)
         self.adam, self.natural, self.sigma_bounds = adam, bool(natural), (lo, hi)
         self.t = 0
-        own = [t.clone() for t in (mean.w1, mean.b1, mean.w2, mean.b2)]
+        own = [t.clone() for t in mean.weights]
         self.mean = mean._like(*own, None)
-        self._spare_mean = mean._like(*(torch.empty_like(t) for t in own), None)
+        self._spare_mean = mean._sets(mean.n_sets)
         self.sigma = [torch.full_like(t, float(sigma)) for t in own]
         self._spare_sigma = [torch.empty_like(t) for t in own]
         self.m1 = self.m2 = self._spare_m1 = self._spare_m2 = None
@@ -560,8 +551,7 @@ class SeparableES:
         return c
 
     def _descriptor(self, what, generation, seed, pair_chunk=0):
-        if not 0 <= int(generation) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError("%s: generation must fit 32 bits and seed 64 (unsigned)" % what)
+        _tier.draw_ok(what, generation, seed)
         if int(pair_chunk) < 0:
             raise ValueError("%s: pair_chunk must be at least 0, not %r" % (what, pair_chunk))
         m = self.mean
@@ -570,18 +560,10 @@ class SeparableES:
         e.pair_chunk, e.generation, e.flags, e.seed = int(pair_chunk), int(generation), self.flags, int(seed)
         return e
 
-    @staticmethod
-    def _point(e, prefix, tensors):
-        for k, t in zip(_lib.SNES_ARRAYS, tensors):
-            setattr(e, prefix + k, t.data_ptr())
-
     def scratch_bytes(self, pair_chunk=0, wide=False):
         """Bytes of scratch that ``update`` needs (rem2d_snes_scratch_bytes); 0 where the update is one launch."""
         e = self._descriptor("SeparableES.scratch_bytes", 0, 0, pair_chunk)
-        n = int(_lib.lib(wide).rem2d_snes_scratch_bytes(C.byref(e)))
-        if n < 0:
-            _lib.check(n, wide)
-        return n
+        return _tier.scratch_bytes(_lib.lib(wide).rem2d_snes_scratch_bytes, e, wide)
 
     def sample(self, generation, seed=0, out=None, wide=False):
         """The children of one generation: set ``b S + 2 q`` is ``mean[b] + sigma[b] z`` and set ``b S + 2 q + 1`` is
@@ -590,27 +572,22 @@ class SeparableES:
         allocated by the first call and overwritten by every later one."""
         e = self._descriptor("SeparableES.sample", generation, seed)
         G = self.mean.n_sets * self.group_size
-        mine = (self.mean.w1, self.mean.b1, self.mean.w2, self.mean.b2)
         if out is not None:
             self.mean._es_out("SeparableES.sample", out, G)
-            for a in (out.w1, out.b1, out.w2, out.b2):
-                for b in self.sigma:
-                    if a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
-                        raise ValueError("SeparableES.sample: out shares memory with sigma")
+            if _tier.overlaps(out.weights, self.sigma):
+                raise ValueError("SeparableES.sample: out shares memory with sigma")
         if self.device.type != "cuda":
             raise ValueError("SeparableES.sample: the weights are on %s; build the strategy around a mean on the GPU" % self.device)
         if out is None:
             if self._children is None:
-                self._children = self.mean._like(*(torch.empty((G,) + tuple(t.shape[1:]), dtype=torch.float32, device=self.device) for t in mine), None)
+                self._children = self.mean._sets(G)
             child = self._children
         else:
-            child = out
-            child.activation, child.scale, child.rays = self.mean.activation, self.mean.scale, self.mean.rays
-        self._point(e, "", mine)
-        self._point(e, "sigma_", self.sigma)
-        self._point(e, "child_", (child.w1, child.b1, child.w2, child.b2))
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib(wide).rem2d_snes_sample(C.byref(e), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), wide)
+            child = self.mean._adopt(out)
+        _tier.point(e, "", self.mean.weights)
+        _tier.point(e, "sigma_", self.sigma)
+        _tier.point(e, "child_", child.weights)
+        _tier.launch(_lib.lib(wide).rem2d_snes_sample, e, self.device, wide)
         return child
 
     def update(self, fitness, generation, seed=0, util=None, scratch=None, pair_chunk=0, wide=False):
@@ -625,20 +602,9 @@ class SeparableES:
         dev = self.device
         e = self._descriptor("SeparableES.update", generation, seed, pair_chunk)
         G = self.mean.n_sets * self.group_size
-        if util is None:
-            if not isinstance(fitness, torch.Tensor) or fitness.dtype != torch.float64:
-                raise ValueError("SeparableES.update: fitness must be a torch.float64 tensor")
-            if tuple(fitness.shape) != (G,) or not fitness.is_contiguous():
-                raise ValueError("SeparableES.update: fitness must be a contiguous tensor of one entry per child [%d], not %s" % (G, list(fitness.shape)))
-            if fitness.device != dev:
-                raise ValueError("SeparableES.update: fitness must be on %s, not %s" % (dev, fitness.device))
-        elif (not isinstance(util, torch.Tensor) or util.dtype != torch.int32 or tuple(util.shape) != (G,) or not util.is_contiguous()
-              or util.device != dev):
-            raise ValueError("SeparableES.update: util must be a contiguous torch.int32 [%d] tensor on %s" % (G, dev))
+        _check_ranked("SeparableES.update", fitness, util, G, dev)
         need = self.scratch_bytes(pair_chunk, wide)
-        if scratch is not None and (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.int64 or not scratch.is_contiguous()
-                                    or scratch.device != dev or scratch.numel() * 8 < need):
-            raise ValueError("SeparableES.update: scratch must be a contiguous torch.int64 tensor of at least %d entries on %s" % (need // 8, dev))
+        _check_scratch("SeparableES.update", scratch, need, dev)
         if dev.type != "cuda":
             raise ValueError("SeparableES.update: the weights are on %s; build the strategy around a mean on the GPU" % dev)
         new = self._spare_mean
@@ -656,20 +622,18 @@ class SeparableES:
             setattr(e, k, v)
         e.fitness = None if util is not None else fitness.data_ptr()
         e.util = new.util.data_ptr()
-        self._point(e, "", (self.mean.w1, self.mean.b1, self.mean.w2, self.mean.b2))
-        self._point(e, "sigma_", self.sigma)
-        self._point(e, "new_", (new.w1, new.b1, new.w2, new.b2))
-        self._point(e, "new_sigma_", self._spare_sigma)
+        _tier.point(e, "", self.mean.weights)
+        _tier.point(e, "sigma_", self.sigma)
+        _tier.point(e, "new_", new.weights)
+        _tier.point(e, "new_sigma_", self._spare_sigma)
         if self.adam is not None:
-            self._point(e, "m1_", self.m1)
-            self._point(e, "m2_", self.m2)
-            self._point(e, "new_m1_", self._spare_m1)
-            self._point(e, "new_m2_", self._spare_m2)
+            _tier.point(e, "m1_", self.m1)
+            _tier.point(e, "m2_", self.m2)
+            _tier.point(e, "new_m1_", self._spare_m1)
+            _tier.point(e, "new_m2_", self._spare_m2)
         e.scratch, e.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel() * 8)
         L = _lib.lib(wide)
-        call = L.rem2d_snes_step if util is None else L.rem2d_snes_update
-        with torch.cuda.device(dev):
-            _lib.check(call(C.byref(e), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), wide)
+        _tier.launch(L.rem2d_snes_step if util is None else L.rem2d_snes_update, e, dev, wide)
         self.mean, self._spare_mean = new, self.mean
         self.sigma, self._spare_sigma = self._spare_sigma, self.sigma
         self.m1, self._spare_m1 = self._spare_m1, self.m1
@@ -682,7 +646,7 @@ class SeparableES:
         """A plain dict for a checkpoint: ``mean``, ``sigma`` and, with Adam, ``m1`` and ``m2`` -- lists of four CPU tensors (w1, b1, w2,
         b2) -- and the update count ``t``."""
         cpu = lambda ts: [t.detach().cpu().clone() for t in ts]
-        s = {"mean": cpu((self.mean.w1, self.mean.b1, self.mean.w2, self.mean.b2)), "sigma": cpu(self.sigma), "t": int(self.t)}
+        s = {"mean": cpu(self.mean.weights), "sigma": cpu(self.sigma), "t": int(self.t)}
         if self.adam is not None:
             s["m1"], s["m2"] = cpu(self.m1), cpu(self.m2)
         return s
@@ -690,7 +654,7 @@ class SeparableES:
     def load_state(self, state):
         """Continue from ``state()``'s dict: the tensors are copied into the object's current buffers (same shapes), ``t`` is set."""
         names = ("mean", "sigma") + (("m1", "m2") if self.adam is not None else ())
-        mine = {"mean": (self.mean.w1, self.mean.b1, self.mean.w2, self.mean.b2), "sigma": self.sigma, "m1": self.m1, "m2": self.m2}
+        mine = {"mean": self.mean.weights, "sigma": self.sigma, "m1": self.m1, "m2": self.m2}
         if not isinstance(state, dict) or any(k not in state for k in names + ("t",)):
             raise ValueError("SeparableES.load_state: state must be a dict with %s and t" % ", ".join(names))
         if isinstance(state["t"], bool) or not isinstance(state["t"], int) or state["t"] < 0:
