@@ -123,6 +123,9 @@ PARETO_MAX_WIDTH = 32       # REM2D_PARETO_MAX_WIDTH
 PARETO_MAX_K = 32           # REM2D_PARETO_MAX_K
 RECURRENT_ABI_VERSION = 1   # include/rem2d_recurrent.h
 RECURRENT_MAX_INPUTS = SENSE_MAX_RAYS   # n_rays + context: what a feed-forward set may have as ray inputs
+OBSNORM_ABI_VERSION = 1     # include/rem2d_obsnorm.h
+OBSNORM_MAX_CHUNK = 65536   # REM2D_OBSNORM_MAX_CHUNK
+OBSNORM_CAPACITY_LOG2 = 39  # REM2D_OBSNORM_CAPACITY_LOG2
 SELFTEST_ABI_VERSION = 1    # include/rem2d_selftest.h
 SELFTEST_CASE_WORDS = 26    # REM2D_SELFTEST_CASE_WORDS
 SELFTEST_OUT_WORDS = 8      # REM2D_SELFTEST_OUT_WORDS
@@ -191,6 +194,14 @@ class Policy(C.Structure):
 class Recurrent(C.Structure):
     """rem2d_recurrent (include/rem2d_recurrent.h): a rem2d_policy, the context width and the device memory the caller owns."""
     _fields_ = [("p", Policy), ("context", C.c_int32), ("reserved", C.c_int32), ("memory", C.c_void_p), ("reset", C.c_void_p)]
+
+
+class Obsnorm(C.Structure):
+    """rem2d_obsnorm (include/rem2d_obsnorm.h): device pointers the caller owns, and the stream the calls queue on."""
+    _fields_ = ([(k, C.c_int32) for k in ("max_bodies", "n_rays", "n_blocks", "group_size", "row_chunk", "context")]
+                + [("clip", C.c_float), ("min_var", C.c_float), ("min_count", C.c_int64), ("n_rows", C.c_int64)]
+                + [(k, C.c_void_p) for k in ("obs", "frac", "row_mask", "count", "s1", "s2hi", "s2lo", "mu", "inv", "memory", "reset")]
+                + [("reserved", C.c_int64), ("stream", C.c_void_p)])
 
 
 class Evolve(C.Structure):
@@ -554,6 +565,15 @@ def lib(wide=False):
     L.rem2d_worlds_act_recurrent.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Recurrent), C.c_void_p, C.c_void_p]
     if L.rem2d_recurrent_abi_version() != RECURRENT_ABI_VERSION:
         raise Rem2dError("%s: recurrent ABI version mismatch" % os.path.basename(path))
+    # observation normalisation (include/rem2d_obsnorm.h): the stream is a member of the descriptor
+    L.rem2d_obsnorm_abi_version.restype = C.c_int
+    for fn in (L.rem2d_obsnorm_accumulate, L.rem2d_obsnorm_freeze):
+        fn.argtypes = [C.POINTER(Obsnorm)]
+    for fn in (L.rem2d_obsnorm_forward, L.rem2d_obsnorm_forward_memory):
+        fn.argtypes = [C.POINTER(Obsnorm), C.POINTER(Policy)]
+    L.rem2d_worlds_act_normed.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Obsnorm), C.POINTER(Policy), C.c_void_p, C.c_int32]
+    if L.rem2d_obsnorm_abi_version() != OBSNORM_ABI_VERSION:
+        raise Rem2dError("%s: obsnorm ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

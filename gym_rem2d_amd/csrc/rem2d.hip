@@ -54,6 +54,7 @@
 #include <rem2d_snes.h>    // (likewise)
 #include <rem2d_pareto.h>  // (likewise)
 #include <rem2d_recurrent.h> // (likewise)
+#include <rem2d_obsnorm.h> // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -110,6 +111,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_raster.h"
 #include "rem2d_control.h"
 #include "rem2d_sense.h"
+#include "rem2d_obsnorm.h" // (before the two forward kernels, whose NORM instantiations stage their rows through it)
 #include "rem2d_policy.h"
 #include "rem2d_recurrent.h"
 #include "rem2d_episode.h"
@@ -1589,8 +1591,8 @@ static unsigned pow2_at_least(unsigned v) {
     while (p < v) p <<= 1;
     return p;
 }
-// The forward pass of a checked descriptor on `st`.
-static int policy_launch(const rem2d_policy *p, hipStream_t st) {
+// The forward pass of a checked descriptor on `st`; with `nm` the normalised one (include/rem2d_obsnorm.h): the same launch shape.
+static int policy_launch(const rem2d_policy *p, hipStream_t st, const PolNorm *nm = nullptr) {
     if (p->n_rows == 0) return REM2D_OK;
     PolicyArgs A;
     memset(&A, 0, sizeof(A));
@@ -1610,9 +1612,16 @@ static int policy_launch(const rem2d_policy *p, hipStream_t st) {
     const long long blocks = (p->n_rows + rpw - 1) / rpw;
     if (blocks > 0x7fffffffLL) return fail(REM2D_E_INVALID, "policy: too many rows for one launch");
     const size_t lds = (size_t)rpw * (size_t)(p->d + p->hidden) * sizeof(float);
-    void (*kernel)(PolicyArgs) = v1 ? (v2 ? rem2d_policy_forward_kernel<4, 4> : rem2d_policy_forward_kernel<4, 1>)
+    if (nm) {
+        void (*normed)(PolicyArgs, PolNorm) = v1 ? (v2 ? rem2d_policy_forward_kernel<4, 4, true> : rem2d_policy_forward_kernel<4, 1, true>)
+                                              : (v2 ? rem2d_policy_forward_kernel<1, 4, true> : rem2d_policy_forward_kernel<1, 1, true>);
+        hipLaunchKernelGGL(normed, dim3((unsigned)blocks), dim3(WAVE), lds, st, A, *nm);
+        HIP_TRY(hipGetLastError());
+        return REM2D_OK;
+    }
+    void (*kernel)(PolicyArgs, PolNoNorm) = v1 ? (v2 ? rem2d_policy_forward_kernel<4, 4> : rem2d_policy_forward_kernel<4, 1>)
                                     : (v2 ? rem2d_policy_forward_kernel<1, 4> : rem2d_policy_forward_kernel<1, 1>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, A);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, A, PolNoNorm());
     HIP_TRY(hipGetLastError());
     return REM2D_OK;
 }
@@ -1669,8 +1678,8 @@ static int recurrent_ok(const char *what, const rem2d_recurrent *q) {
     if (!q->memory) return fail(REM2D_E_INVALID, s + "NULL device pointer (memory)");
     return REM2D_OK;
 }
-// The recurrent forward pass of a checked descriptor on `st`: policy_launch's launch shape.
-static int recurrent_launch(const rem2d_recurrent *q, hipStream_t st) {
+// The recurrent forward pass of a checked descriptor on `st`: policy_launch's launch shape; with `nm` the normalised one.
+static int recurrent_launch(const rem2d_recurrent *q, hipStream_t st, const PolNorm *nm = nullptr) {
     const rem2d_policy *p = &q->p;
     if (p->n_rows == 0) return REM2D_OK;
     RecurrentArgs Q;
@@ -1692,9 +1701,16 @@ static int recurrent_launch(const rem2d_recurrent *q, hipStream_t st) {
     const long long blocks = (p->n_rows + rpw - 1) / rpw;
     if (blocks > 0x7fffffffLL) return fail(REM2D_E_INVALID, "recurrent: too many rows for one launch");
     const size_t lds = (size_t)rpw * (size_t)(p->d + p->hidden) * sizeof(float);
-    void (*kernel)(RecurrentArgs) = v1 ? (v2 ? rem2d_recurrent_forward_kernel<4, 4> : rem2d_recurrent_forward_kernel<4, 1>)
+    if (nm) {
+        void (*normed)(RecurrentArgs, PolNorm) = v1 ? (v2 ? rem2d_recurrent_forward_kernel<4, 4, true> : rem2d_recurrent_forward_kernel<4, 1, true>)
+                                                 : (v2 ? rem2d_recurrent_forward_kernel<1, 4, true> : rem2d_recurrent_forward_kernel<1, 1, true>);
+        hipLaunchKernelGGL(normed, dim3((unsigned)blocks), dim3(WAVE), lds, st, Q, *nm);
+        HIP_TRY(hipGetLastError());
+        return REM2D_OK;
+    }
+    void (*kernel)(RecurrentArgs, PolNoNorm) = v1 ? (v2 ? rem2d_recurrent_forward_kernel<4, 4> : rem2d_recurrent_forward_kernel<4, 1>)
                                        : (v2 ? rem2d_recurrent_forward_kernel<1, 4> : rem2d_recurrent_forward_kernel<1, 1>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, Q);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, Q, PolNoNorm());
     HIP_TRY(hipGetLastError());
     return REM2D_OK;
 }
@@ -2712,6 +2728,161 @@ extern "C" int rem2d_pareto_local(const rem2d_pareto *p, void *stream) {
     else pa_launch_local<32>(A, grid, st);
     HIP_TRY(hipGetLastError());
     return REM2D_OK;
+}
+
+// ---- observation normalisation (include/rem2d_obsnorm.h, csrc/rem2d_obsnorm.h) ----
+extern "C" int rem2d_obsnorm_abi_version(void) { return REM2D_OBSNORM_ABI_VERSION; }
+enum { ON_ACC = 1, ON_FREEZE = 2, ON_APPLY = 4 };
+static int on_dn(const rem2d_obsnorm *n) { return REM2D_OBS_HEAD + REM2D_OBS_BODY * n->max_bodies + n->n_rays; }
+// The refusals of a normaliser's shapes; `s` prefixes the message.  No pointer is looked at.
+static int on_shapes_ok(const std::string &s, const rem2d_obsnorm *n) {
+    if (!n) return fail(REM2D_E_INVALID, s + "NULL descriptor");
+    if (n->max_bodies < 1 || n->max_bodies > REM2D_CONTROL_MAX_BODIES)
+        return fail(REM2D_E_INVALID, s + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(n->max_bodies));
+    if (n->n_rays < 0 || n->n_rays > REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, s + "n_rays must be 0.." + std::to_string(REM2D_SENSE_MAX_RAYS) + ", not " + std::to_string(n->n_rays));
+    if (n->n_blocks < 1) return fail(REM2D_E_INVALID, s + "n_blocks must be at least 1, not " + std::to_string(n->n_blocks));
+    if (n->group_size < 1) return fail(REM2D_E_INVALID, s + "group_size must be at least 1, not " + std::to_string(n->group_size));
+    if ((long long)n->n_blocks * (long long)n->group_size > 0x7fffffffLL)
+        return fail(REM2D_E_INVALID, s + "n_blocks * group_size must be at most 2^31 - 1");
+    if ((long long)n->n_blocks * (long long)on_dn(n) > 0x7fffffffLL)
+        return fail(REM2D_E_INVALID, s + "n_blocks times the words of a row must be at most 2^31 - 1");
+    if (n->row_chunk < 0 || n->row_chunk > REM2D_OBSNORM_MAX_CHUNK)
+        return fail(REM2D_E_INVALID, s + "row_chunk must be 0.." + std::to_string(REM2D_OBSNORM_MAX_CHUNK) + ", not " + std::to_string(n->row_chunk));
+    if (n->reserved != 0) return fail(REM2D_E_INVALID, s + "reserved must be 0, not " + std::to_string(n->reserved));
+    return REM2D_OK;
+}
+// Checks a normaliser for `stages`; `what` prefixes the message.  Nothing it points to is read.
+static int on_ok(const char *what, const rem2d_obsnorm *n, int stages) {
+    const std::string s = std::string(what) + ": ";
+    OK_TRY(on_shapes_ok(s, n));
+    if (stages & ON_ACC) {
+        if (n->n_rows < 0) return fail(REM2D_E_INVALID, s + "negative row count");
+        if (n->n_rows > (int64_t)n->n_blocks * (int64_t)n->group_size)
+            return fail(REM2D_E_INVALID, s + std::to_string(n->n_rows) + " rows are more than n_blocks * group_size = " +
+                                             std::to_string((long long)n->n_blocks * (long long)n->group_size));
+        if (!n->obs) return fail(REM2D_E_INVALID, s + "NULL device pointer (obs)");
+        if (n->n_rays > 0 && !n->frac) return fail(REM2D_E_INVALID, s + "NULL device pointer (frac)");
+    }
+    if (stages & ON_FREEZE) {
+        if (n->min_count < 1) return fail(REM2D_E_INVALID, s + "min_count must be at least 1, not " + std::to_string(n->min_count));
+        if (!(n->min_var > 0.0f) || !std::isfinite(n->min_var)) return fail(REM2D_E_INVALID, s + "min_var must be positive and finite");
+    }
+    if (stages & ON_APPLY) {
+        if (!(n->clip > 0.0f)) return fail(REM2D_E_INVALID, s + "clip must be greater than 0 (it may be +inf)");
+        if (n->context < 0) return fail(REM2D_E_INVALID, s + "context must be at least 0, not " + std::to_string(n->context));
+    }
+    if (stages & (ON_ACC | ON_FREEZE)) {
+        const Span st[4] = {span(n->count, 0, "count"), span(n->s1, 0, "s1"), span(n->s2hi, 0, "s2hi"), span(n->s2lo, 0, "s2lo")};
+        for (const Span &x : st) {
+            if (!x.at) return fail(REM2D_E_INVALID, s + "NULL device pointer (" + x.name + ")");
+            if (x.at % 8 != 0) return fail(REM2D_E_INVALID, s + x.name + " must be 8-byte aligned");
+        }
+    }
+    if (stages & (ON_FREEZE | ON_APPLY)) {
+        if (!n->mu) return fail(REM2D_E_INVALID, s + "NULL device pointer (mu)");
+        if (!n->inv) return fail(REM2D_E_INVALID, s + "NULL device pointer (inv)");
+    }
+    return REM2D_OK;
+}
+template <int WPL> static void on_launch_acc(const OnArgs &A, dim3 grid, size_t slots, hipStream_t st) {
+    hipLaunchKernelGGL(rem2d_obsnorm_accumulate_kernel<WPL>, grid, dim3(ON_THREADS), slots * (size_t)(3 * WPL * WAVE + 1) * sizeof(long long), st, A);
+}
+// The accumulation and / or the tables of a checked descriptor on `st`.
+static int on_launch(const rem2d_obsnorm *n, int stages, hipStream_t st) {
+    const int Dn = on_dn(n);
+    if ((stages & ON_ACC) && n->n_rows > 0) {
+        OnArgs A;
+        memset(&A, 0, sizeof(A));
+        A.obs = n->obs; A.frac = n->frac; A.rowMask = n->row_mask;
+        A.count = (long long *)n->count; A.s1 = (long long *)n->s1; A.s2hi = (long long *)n->s2hi; A.s2lo = (long long *)n->s2lo;
+        A.nRows = n->n_rows;
+        A.nObs = Dn - n->n_rays; A.R = n->n_rays; A.Dn = Dn; A.S = n->group_size;
+        // rows of a block per wavefront: the caller's, or 32 -- 2048 wavefronts at 65 536 rows, one wavefront per block of up to 32
+        A.rowChunk = std::min(n->group_size, n->row_chunk > 0 ? n->row_chunk : 32);
+        A.nChunks = (n->group_size + A.rowChunk - 1) / A.rowChunk;
+        A.items = ((n->n_rows + n->group_size - 1) / n->group_size) * (long long)A.nChunks; // (only the blocks that have rows)
+        const long long groups = (A.items + ON_WAVES - 1) / ON_WAVES;
+        if (groups > 0x7fffffffLL) return fail(REM2D_E_INVALID, "obsnorm: too many rows for one launch");
+        const dim3 grid((unsigned)groups);
+        const size_t slots = A.nChunks > 1 ? ON_WAVES - 1 : 0;
+        if (Dn <= WAVE) on_launch_acc<1>(A, grid, slots, st);
+        else if (Dn <= 2 * WAVE) on_launch_acc<2>(A, grid, slots, st);
+        else if (Dn <= 4 * WAVE) on_launch_acc<4>(A, grid, slots, st);
+        else on_launch_acc<ON_MAX_WPL>(A, grid, slots, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (stages & ON_FREEZE) {
+        OnFreezeArgs F;
+        memset(&F, 0, sizeof(F));
+        F.count = (const long long *)n->count; F.s1 = (const long long *)n->s1; F.s2hi = (const long long *)n->s2hi; F.s2lo = (const long long *)n->s2lo;
+        F.mu = n->mu; F.inv = n->inv;
+        F.total = (long long)n->n_blocks * (long long)Dn; F.minCount = n->min_count; F.Dn = Dn; F.minVar = n->min_var;
+        hipLaunchKernelGGL(rem2d_obsnorm_freeze_kernel, dim3((unsigned)((F.total + ON_THREADS - 1) / ON_THREADS)), dim3(ON_THREADS), 0, st, F);
+        HIP_TRY(hipGetLastError());
+    }
+    return REM2D_OK;
+}
+static_assert(REM2D_CONTROL_MAX_BODIES * REM2D_OBS_BODY + REM2D_OBS_HEAD + REM2D_SENSE_MAX_RAYS <= ON_MAX_WPL * WAVE, "a row's words fit the lanes' registers");
+extern "C" int rem2d_obsnorm_accumulate(const rem2d_obsnorm *n) { return run(on_ok, on_launch, "obsnorm_accumulate", n, ON_ACC, n ? n->stream : nullptr); }
+extern "C" int rem2d_obsnorm_freeze(const rem2d_obsnorm *n) { return run(on_ok, on_launch, "obsnorm_freeze", n, ON_FREEZE, n ? n->stream : nullptr); }
+// Checks a normaliser against the policy it is applied to (`memory`: the pass with context words), before anything is launched;
+// *q is the recurrent descriptor made of p and the normaliser's context members where memory is set.
+static int on_policy_ok(const char *what, const rem2d_obsnorm *n, const rem2d_policy *p, bool memory, rem2d_recurrent *q) {
+    const std::string s = std::string(what) + ": ";
+    OK_TRY(on_ok(what, n, ON_APPLY));
+    if (!p) return fail(REM2D_E_INVALID, s + "NULL policy");
+    if (memory) {
+        q->p = *p; q->context = n->context; q->reserved = 0; q->memory = n->memory; q->reset = n->reset;
+        OK_TRY(recurrent_ok(what, q));
+    } else {
+        if (n->context != 0) return fail(REM2D_E_INVALID, s + "context must be 0 for a feed-forward policy, not " + std::to_string(n->context));
+        OK_TRY(policy_ok(what, p));
+    }
+    if (p->max_bodies != n->max_bodies || p->n_rays != n->n_rays)
+        return fail(REM2D_E_INVALID, s + "the policy has max_bodies " + std::to_string(p->max_bodies) + " and n_rays " + std::to_string(p->n_rays) +
+                                         ", the normaliser " + std::to_string(n->max_bodies) + " and " + std::to_string(n->n_rays));
+    if (p->n_rows > (int64_t)n->n_blocks * (int64_t)n->group_size)
+        return fail(REM2D_E_INVALID, s + std::to_string(p->n_rows) + " rows are more than n_blocks * group_size = " +
+                                         std::to_string((long long)n->n_blocks * (long long)n->group_size));
+    return REM2D_OK;
+}
+static PolNorm on_tables(const rem2d_obsnorm *n) { return {n->mu, n->inv, n->clip, n->group_size, on_dn(n)}; }
+extern "C" int rem2d_obsnorm_forward(const rem2d_obsnorm *n, const rem2d_policy *p) {
+    OK_TRY(on_policy_ok("obsnorm_forward", n, p, false, nullptr));
+    const PolNorm nm = on_tables(n);
+    return policy_launch(p, (hipStream_t)n->stream, &nm);
+}
+extern "C" int rem2d_obsnorm_forward_memory(const rem2d_obsnorm *n, const rem2d_policy *p) {
+    rem2d_recurrent q;
+    OK_TRY(on_policy_ok("obsnorm_forward_memory", n, p, true, &q));
+    const PolNorm nm = on_tables(n);
+    return recurrent_launch(&q, (hipStream_t)n->stream, &nm);
+}
+extern "C" int rem2d_worlds_act_normed(rem2d_world *const *worlds, int32_t n_worlds, const rem2d_obsnorm *n, const rem2d_policy *p,
+                                       const double *ray_offsets_dev, int32_t accumulate) {
+    // (rem2d_worlds_act's order: arguments first, worlds after, everything before the first launch)
+    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "act_normed: no worlds");
+    rem2d_recurrent q;
+    const bool memory = n && n->context > 0;
+    OK_TRY(on_policy_ok("act_normed", n, p, memory, &q));
+    rem2d_obsnorm acc = *n; // the accumulation reads what this call's observe and sense write
+    acc.obs = p->obs; acc.frac = p->frac; acc.row_mask = p->row_mask; acc.n_rows = p->n_rows;
+    if (accumulate) OK_TRY(on_ok("act_normed", &acc, ON_ACC));
+    if (p->n_rays > 0 && !ray_offsets_dev) return fail(REM2D_E_INVALID, "act_normed: NULL device pointer (ray offsets)");
+    for (int32_t i = 0; i < n_worlds; ++i)
+        if (!worlds[i]) return fail(REM2D_E_INVALID, "act_normed: world " + std::to_string(i) + " is NULL");
+    OK_TRY(control_worlds_ok("act_normed", worlds, n_worlds, p->max_bodies, p->n_rows, p->obs));
+    if (p->n_rays > 0)
+        for (int32_t i = 0; i < n_worlds; ++i)
+            if (!worlds[i]->haveTerrain) return fail(REM2D_E_STATE, "act_normed: rem2d_world_set_terrain must be called first");
+    void *stream = n->stream;
+    OK_TRY(rem2d_worlds_observe(worlds, n_worlds, p->max_bodies, const_cast<float *>(p->obs), p->n_rows, stream));
+    if (p->n_rays > 0) OK_TRY(rem2d_worlds_sense(worlds, n_worlds, ray_offsets_dev, p->n_rays, const_cast<float *>(p->frac), nullptr, p->n_rows, stream));
+    if (accumulate) OK_TRY(on_launch(&acc, ON_ACC, (hipStream_t)stream));
+    const PolNorm nm = on_tables(n);
+    OK_TRY(memory ? recurrent_launch(&q, (hipStream_t)stream, &nm) : policy_launch(p, (hipStream_t)stream, &nm));
+    return rem2d_worlds_control(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, stream);
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

@@ -78,8 +78,15 @@ template <int V> DEV void pol_accumulate(const float *xs, int nIn, const float *
 
 DEV float pol_softsign(float a) { return a / __fadd_rn(1.0f, __builtin_fabsf(a)); }
 
-// V1 / V2: output units a lane owns per pass of the hidden / the output layer
-template <int V1, int V2> __global__ __launch_bounds__(WAVE) void rem2d_policy_forward_kernel(PolicyArgs P) {
+// The second kernel argument of a forward kernel: nothing, or with NORM the normaliser's tables (rem2d_obsnorm.h: PolNorm,
+// on_apply).  The NORM = false instantiations hold the code they held before NORM existed.
+struct PolNoNorm {};
+template <bool NORM> struct PolNormArg { typedef PolNoNorm type; };
+template <> struct PolNormArg<true> { typedef PolNorm type; };
+
+// V1 / V2: output units a lane owns per pass of the hidden / the output layer; NORM: the row is staged through on_apply
+template <int V1, int V2, bool NORM = false>
+__global__ __launch_bounds__(WAVE) void rem2d_policy_forward_kernel(PolicyArgs P, typename PolNormArg<NORM>::type Nm) {
     extern __shared__ float pol_lds[];
     const int lane = (int)threadIdx.x, lpr = P.lpr;
     const int sub = lane / lpr, u = lane & (lpr - 1); // row of the wavefront, lane inside the row
@@ -93,10 +100,20 @@ template <int V1, int V2> __global__ __launch_bounds__(WAVE) void rem2d_policy_f
     if (on) { // the row's input: observation words, then ray fractions
         const int nObs = P.D - P.R;
         const float *obs = P.obs + (size_t)r * (size_t)nObs;
-        for (int i = u; i < nObs; i += lpr) xs[i] = obs[i];
-        if (P.R > 0) {
-            const float *frac = P.frac + (size_t)r * (size_t)P.R;
-            for (int i = u; i < P.R; i += lpr) xs[nObs + i] = frac[i];
+        if constexpr (NORM) { // the row's block of S consecutive rows names its tables
+            const size_t tb = (size_t)(r / (long long)Nm.S) * (size_t)Nm.Dn;
+            const float *mu = Nm.mu + tb, *inv = Nm.inv + tb;
+            for (int i = u; i < nObs; i += lpr) xs[i] = on_apply(obs[i], mu[i], inv[i], Nm.clip);
+            if (P.R > 0) {
+                const float *frac = P.frac + (size_t)r * (size_t)P.R;
+                for (int i = u; i < P.R; i += lpr) xs[nObs + i] = on_apply(frac[i], mu[nObs + i], inv[nObs + i], Nm.clip);
+            }
+        } else {
+            for (int i = u; i < nObs; i += lpr) xs[i] = obs[i];
+            if (P.R > 0) {
+                const float *frac = P.frac + (size_t)r * (size_t)P.R;
+                for (int i = u; i < P.R; i += lpr) xs[nObs + i] = frac[i];
+            }
         }
     }
     lds_sync();

@@ -28,8 +28,10 @@ struct RecurrentArgs {
     int K;
 };
 
-// V1 / V2: output units a lane owns per pass of the hidden / the output layer
-template <int V1, int V2> __global__ __launch_bounds__(WAVE) void rem2d_recurrent_forward_kernel(RecurrentArgs Q) {
+// V1 / V2: output units a lane owns per pass of the hidden / the output layer; NORM (as in rem2d_policy.h): the observation words
+// and the ray fractions are staged through on_apply, the context words as they are
+template <int V1, int V2, bool NORM = false>
+__global__ __launch_bounds__(WAVE) void rem2d_recurrent_forward_kernel(RecurrentArgs Q, typename PolNormArg<NORM>::type Nm) {
     extern __shared__ float rec_lds[];
     const PolicyArgs &P = Q.P;
     const int lane = (int)threadIdx.x, lpr = P.lpr;
@@ -45,10 +47,20 @@ template <int V1, int V2> __global__ __launch_bounds__(WAVE) void rem2d_recurren
     if (on) { // the row's input: observation words, ray fractions, context words
         const int nObs = P.D - P.R - Q.K;
         const float *obs = P.obs + (size_t)r * (size_t)nObs;
-        for (int i = u; i < nObs; i += lpr) xs[i] = obs[i];
-        if (P.R > 0) {
-            const float *frac = P.frac + (size_t)r * (size_t)P.R;
-            for (int i = u; i < P.R; i += lpr) xs[nObs + i] = frac[i];
+        if constexpr (NORM) {
+            const size_t tb = (size_t)(r / (long long)Nm.S) * (size_t)Nm.Dn;
+            const float *mu = Nm.mu + tb, *inv = Nm.inv + tb;
+            for (int i = u; i < nObs; i += lpr) xs[i] = on_apply(obs[i], mu[i], inv[i], Nm.clip);
+            if (P.R > 0) {
+                const float *frac = P.frac + (size_t)r * (size_t)P.R;
+                for (int i = u; i < P.R; i += lpr) xs[nObs + i] = on_apply(frac[i], mu[nObs + i], inv[nObs + i], Nm.clip);
+            }
+        } else {
+            for (int i = u; i < nObs; i += lpr) xs[i] = obs[i];
+            if (P.R > 0) {
+                const float *frac = P.frac + (size_t)r * (size_t)P.R;
+                for (int i = u; i < P.R; i += lpr) xs[nObs + i] = frac[i];
+            }
         }
         const bool fresh = Q.reset && Q.reset[r] != 0; // substituted, not multiplied: memory is not read at all
         for (int k = u; k < Q.K; k += lpr) xs[nObs + P.R + k] = fresh ? 0.0f : mem[k];

@@ -634,7 +634,7 @@ class BatchedModular2D:
         return (frac, hit) if hits else frac
 
     # ---- device policies: the controllers live on the device as data (include/rem2d_policy.h) ----
-    def set_policy(self, policy):
+    def set_policy(self, policy, normalizer=None, accumulate=True):
         """Attach a ``policy.MLPPolicy`` to the population in place (after reset; a new upload drops it), or None to detach it.  The
         policy needs one weight set per creature, or an ``index`` with one entry per creature, and at most 64 bodies' worth of
         columns; it is moved to the env's device.  The buffers act() works in -- observation rows, ray fractions, targets, validity
@@ -643,11 +643,19 @@ class BatchedModular2D:
         A ``policy.RecurrentPolicy`` also gets its context words here: ``policy_memory``, float32 ``[N, context]`` in population
         order, zeroed -- attaching a policy again zeroes them again.  act() carries them from step to step and reads zeros for a
         creature that reset_where() has just restarted.  Streaming under a recurrent policy is not built: a slot's next creature
-        would inherit its predecessor's context, so with a streamed evaluation in place this raises ValueError."""
-        from .policy import RecurrentPolicy
+        would inherit its predecessor's context, so with a streamed evaluation in place this raises ValueError.
+
+        ``normalizer``: a ``policy.ObsNormalizer`` of the policy's ``max_bodies`` and rays on the env's device whose blocks cover the
+        creatures (``n_blocks * group_size >= n_envs``; creature r belongs to block ``r // group_size``): act() then stages every
+        row through the normaliser's tables as they stand (rem2d_worlds_act_normed) and, with ``accumulate``, first adds the rows
+        it has just observed to the normaliser's sums -- one launch more; the tables move at the normaliser's next ``freeze()``,
+        never by themselves.  Without a normaliser nothing changes."""
+        from .policy import ObsNormalizer, RecurrentPolicy
         self._act_args = None
         self._context_reset = False
         if policy is None:
+            if normalizer is not None:
+                raise ValueError("set_policy: a normalizer needs a policy")
             self._policy = None
             return
         if not self.worlds:
@@ -663,7 +671,12 @@ class BatchedModular2D:
         dev = self.worlds[0][0].device
         policy = policy.to(dev)
         N, M, R = self.n_envs, policy.max_bodies, policy.n_rays
+        if normalizer is not None:
+            if not isinstance(normalizer, ObsNormalizer):
+                raise ValueError("set_policy: normalizer must be a policy.ObsNormalizer")
+            normalizer._fits("set_policy", policy, N)
         self._policy = dict(
+            normalizer=normalizer, accumulate=bool(accumulate) and normalizer is not None,
             policy=policy, rays=self._ray_table(policy.rays) if R else None,
             obs=torch.zeros((N, control.width(M)), dtype=torch.float32, device=dev),
             frac=torch.ones((N, R), dtype=torch.float32, device=dev) if R else None,
@@ -689,6 +702,10 @@ class BatchedModular2D:
         target is not finite and that joint was left as it is.  After compact(), rows no live world holds are masked out of the
         forward pass and keep their last values.
 
+        With a normaliser attached (set_policy) the call is rem2d_worlds_act_normed: the same launches, the forward pass staging
+        its rows through the normaliser's tables, and one launch more where the rows are also added to its sums; the compacted row
+        mask and a recurrent policy's reset mask mean what they mean without one.
+
         Under a ``policy.RecurrentPolicy`` the call is rem2d_worlds_act_recurrent -- as many launches -- which also carries
         ``policy_memory`` forward.  The first act() after a reset_where() (under set_autoreset: every act()) hands that call's
         ``episodes.ended`` to the kernel as its reset mask: a creature that has just restarted reads zero context, everybody else
@@ -713,7 +730,9 @@ class BatchedModular2D:
         if worlds:
             w0 = worlds[0]
             rays = None if P["rays"] is None else P["rays"].data_ptr()
-            if P["memory"] is None:
+            if P["normalizer"] is not None:
+                self._act_normed(P, worlds, arr, desc, rays)
+            elif P["memory"] is None:
                 _lib.check(w0.L.rem2d_worlds_act(arr, len(worlds), C.byref(desc), rays, w0._stream()), w0.wide)
             else:   # (the reset mask is this one call's: the cached descriptor points at it now and at nothing afterwards)
                 desc.reset = self._episodes.ended.data_ptr() if self._context_reset else None
@@ -723,6 +742,22 @@ class BatchedModular2D:
                 finally:
                     desc.reset = None
         return P["targets"], P["valid"]
+
+    def _act_normed(self, P, worlds, arr, desc, rays):
+        """act() under a normaliser: the cached policy descriptor (a recurrent one: its ``p``, the context members travel in the
+        normaliser's descriptor) and the normaliser's, on the worlds' stream"""
+        norm, w0 = P["normalizer"], worlds[0]
+        most = norm._offer("act", self.n_envs) if P["accumulate"] else 0
+        n = norm.descriptor()
+        p = desc
+        if P["memory"] is not None:
+            p = desc.p
+            n.context, n.memory = desc.context, desc.memory
+            n.reset = self._episodes.ended.data_ptr() if self._context_reset else None
+            self._context_reset = False
+        n.stream = w0._stream()
+        _lib.check(w0.L.rem2d_worlds_act_normed(arr, len(worlds), C.byref(n), C.byref(p), rays, int(P["accumulate"])), w0.wide)
+        norm.offered += most
 
     def step_policy(self, n_steps=1):
         """n_steps x (act(), step(1)), queued without any synchronisation: the closed loop with the controller on the device.

@@ -257,17 +257,21 @@ def run_episode(env, max_steps=EPISODE_CAP, chunk=100, on_error="fallback", comp
     return env.fitness.clone()
 
 
-def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_error="raise"):
+def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_error="raise", normalizer=None):
     """run_episode for a BatchedModular2D with a device policy attached (``env.set_policy``): the same episode loop, every step
     preceded by the policy's control step (``env.step_policy``), chunks of ``chunk`` steps queued without a synchronisation in
     between.  Returns fitness[N] (float64 tensor on the env's device).  on_error: "raise" | "warn" | "ignore", judged by
     ``check_errors`` on the default build's flags.  There is no second attempt here: replaying the flagged creatures from reset in
     the wide build, as run_episode's fallback does for open-loop creatures, is not built for policies yet -- construct the env
-    with wide=True where creatures may outgrow the default build's contact slots.  ``env.last_episode`` is None afterwards."""
+    with wide=True where creatures may outgrow the default build's contact slots.  ``env.last_episode`` is None afterwards.
+    ``normalizer``: a ``policy.ObsNormalizer`` that is only APPLIED: the env's policy is attached again under it with ``accumulate=False`` (its tables as they stand; its sums are
+    not touched).  Without it the env runs as ``set_policy`` left it, a normaliser attached there included."""
     if on_error not in ("raise", "warn", "ignore"):
         raise ValueError("on_error must be 'raise', 'warn' or 'ignore', not %r" % (on_error,))
     if env.policy is None:
         raise ValueError("run_policy_episode: the env has no policy (set_policy first)")
+    if normalizer is not None:
+        env.set_policy(env.policy, normalizer=normalizer, accumulate=False)
     env.last_episode = None
     _episode(env, max_steps, chunk, compact, step=env.step_policy)
     check_errors(env, on_error)
@@ -275,7 +279,8 @@ def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_e
 
 
 def run_policy_generations(env, policy, n_generations, seed=0, rate=0.05, sigma=0.1, tournsize=4, group_size=None, elite=0,
-                           max_steps=EPISODE_CAP, chunk=100, on_error="raise", log=None, on_generation=None):
+                           max_steps=EPISODE_CAP, chunk=100, on_error="raise", log=None, on_generation=None,
+                           normalizer=None):
     """population.run_generations for device policies: the generational loop of run2D.run_deap (REM2D_main.py:280-298) with the
     population -- the weight sets of ``policy``, one per creature of ``env`` (reset first) -- on the device throughout.  Generation
     0's episode runs first; every generation is then ``policy.evolve`` (generation g = 1 .., this ``seed``), ``env.set_policy``,
@@ -284,10 +289,14 @@ def run_policy_generations(env, policy, n_generations, seed=0, rate=0.05, sigma=
     fitness (float64 [N] on the device) and rows ``(gen, min, max, mean)``, the only numbers that leave the device.
     ``on_generation(gen, policy, fitness)``, if given, is called after every episode, generation 0's included, with the tensors
     themselves (a checkpoint hook: clone what must last, the weight buffers are overwritten two generations later).  The creatures
-    do not change: group_size names the blocks of consecutive creatures whose policies compete (those of one morphology)."""
+    do not change: group_size names the blocks of consecutive creatures whose policies compete (those of one morphology).
+    ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
+    a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
     n = env.n_envs
     everyone = torch.ones(n, dtype=torch.uint8, device=env.worlds[0][0].device) if env.worlds else None
-    env.set_policy(policy)
+    if normalizer is not None:
+        normalizer.freeze()      # one set of tables per generation: every child sees the same
+    env.set_policy(policy, normalizer=normalizer)
     policy = env.policy
     fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
     if on_generation:
@@ -297,7 +306,9 @@ def run_policy_generations(env, policy, n_generations, seed=0, rate=0.05, sigma=
         child = policy.evolve(fit, gen, seed=seed, rate=rate, sigma=sigma, tournsize=tournsize, group_size=group_size, elite=elite,
                               out=spare)
         spare, policy = (policy if gen > 1 else None), child    # (generation 0's buffers are the caller's: never written)
-        env.set_policy(policy)
+        if normalizer is not None:
+            normalizer.freeze()      # one set of tables per generation: every child sees the same
+        env.set_policy(policy, normalizer=normalizer)
         env.reset_where(mask=everyone)
         fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
         stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
@@ -310,7 +321,8 @@ def run_policy_generations(env, policy, n_generations, seed=0, rate=0.05, sigma=
 
 
 def run_policy_es(env, mean, n_generations, seed=0, sigma=0.1, lr=0.05, group_size=None, max_steps=EPISODE_CAP, chunk=100,
-                  on_error="raise", log=None, on_generation=None):
+                  on_error="raise", log=None, on_generation=None,
+                  normalizer=None):
     """An evolution strategy for device policies: ``mean`` holds one controller per block of ``group_size`` = S consecutive
     creatures of ``env`` (reset first; the creatures of a block share a morphology, or are whatever the caller wants ranked
     together; default: one block of everyone), M = n_envs / S sets in all.  Every generation g = 1 .. is ``mean.es_sample`` (the
@@ -321,7 +333,9 @@ def run_policy_es(env, mean, n_generations, seed=0, sigma=0.1, lr=0.05, group_si
     ``mean`` itself is never written.  Returns ``(mean, fitness, history)``: the mean after the last update, the last generation's
     fitness (float64 [N] on the device) and rows ``(gen, min, max, mean)``, the only numbers that leave the device.
     ``on_generation(gen, children, fitness, mean)``, if given, is called after every update with the tensors themselves and the
-    NEW mean (a checkpoint hook: clone what must last, every buffer is overwritten one or two generations later)."""
+    NEW mean (a checkpoint hook: clone what must last, every buffer is overwritten one or two generations later).
+    ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
+    a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
     if not env.worlds:
         raise ValueError("run_policy_es: no population in place (reset first)")
     n = env.n_envs
@@ -337,7 +351,9 @@ def run_policy_es(env, mean, n_generations, seed=0, sigma=0.1, lr=0.05, group_si
         scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
     for gen in range(1, int(n_generations) + 1):
         children = mean.es_sample(gen, seed=seed, sigma=sigma, group_size=S, out=children)
-        env.set_policy(children)
+        if normalizer is not None:
+            normalizer.freeze()      # one set of tables per generation: every child sees the same
+        env.set_policy(children, normalizer=normalizer)
         env.reset_where(mask=everyone)
         fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
         new = mean.es_update(fit, gen, seed=seed, sigma=sigma, lr=lr, group_size=S, out=spare, scratch=scratch)
@@ -351,13 +367,16 @@ def run_policy_es(env, mean, n_generations, seed=0, sigma=0.1, lr=0.05, group_si
     return mean, fit, history
 
 
-def run_policy_snes(env, es, n_generations, seed=0, max_steps=EPISODE_CAP, chunk=100, on_error="raise", log=None, on_generation=None):
+def run_policy_snes(env, es, n_generations, seed=0, max_steps=EPISODE_CAP, chunk=100, on_error="raise", log=None, on_generation=None,
+                    normalizer=None):
     """``run_policy_es`` around a ``policy.SeparableES`` (per-parameter sigma, Adam on request; include/rem2d_snes.h): ``es`` holds one
     mean per block of ``es.group_size`` consecutive creatures of ``env`` (reset first).  Every generation g = 1 .. is ``es.sample``,
     ``env.set_policy``, ``env.reset_where`` of everyone, ``run_policy_episode(compact=False)`` and ``es.update``.  The strategy's own
     buffers are reused throughout: after the first generation nothing is allocated.  Returns ``(mean, fitness, history)`` as
     ``run_policy_es`` does; ``on_generation(gen, children, fitness, mean)`` likewise (``es.sigma``, ``es.t`` and ``es.state()`` are
-    there for a checkpoint hook)."""
+    there for a checkpoint hook).
+    ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
+    a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
     if not env.worlds:
         raise ValueError("run_policy_snes: no population in place (reset first)")
     n, S = env.n_envs, es.group_size
@@ -370,7 +389,9 @@ def run_policy_snes(env, es, n_generations, seed=0, max_steps=EPISODE_CAP, chunk
     fit, history = None, []
     for gen in range(1, int(n_generations) + 1):
         children = es.sample(gen, seed=seed)
-        env.set_policy(children)
+        if normalizer is not None:
+            normalizer.freeze()      # one set of tables per generation: every child sees the same
+        env.set_policy(children, normalizer=normalizer)
         env.reset_where(mask=everyone)
         fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
         mean = es.update(fit, gen, seed=seed)
@@ -428,7 +449,8 @@ def _es_ranks(mean, values, group_size, out):
 
 
 def run_policy_nses(env, mean, n_generations, archive, k=15, rate=0.02, weights=(1, 1), period=None, samples=4, seed=0, sigma=0.1,
-                    lr=0.05, group_size=None, max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None):
+                    lr=0.05, group_size=None, max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None,
+                    normalizer=None):
     """run_policy_es with behavioural novelty beside the fitness (NS-ES / NSR-ES): every generation is ``mean.es_sample``,
     ``env.set_policy``, ``env.reset_where`` of everyone, ``run_behaviour_episode`` (``samples`` root positions, one every ``period``
     steps; default period: ``max_steps`` over ``samples``, rounded up, so that the samples span the episode -- the episode ends after
@@ -440,7 +462,9 @@ def run_policy_nses(env, mean, n_generations, archive, k=15, rate=0.02, weights=
     two sets of mean buffers and one each of novelty, rank and scratch tensors are reused throughout; ``mean`` itself is never
     written.  Returns ``(mean, fitness, history)`` as run_policy_es, the history rows being ``(gen, min, max, mean)`` of the fitness.
     ``on_generation(gen, children, fitness, mean, behaviour, novelty, util)``, if given, is called after every update with the
-    tensors themselves and the NEW mean (clone what must last)."""
+    tensors themselves and the NEW mean (clone what must last).
+    ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
+    a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
     if not env.worlds:
         raise ValueError("run_policy_nses: no population in place (reset first)")
     n = env.n_envs
@@ -468,7 +492,9 @@ def run_policy_nses(env, mean, n_generations, archive, k=15, rate=0.02, weights=
     util_f, util_n, util = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
     for gen in range(1, int(n_generations) + 1):
         children = mean.es_sample(gen, seed=seed, sigma=sigma, group_size=S, out=children)
-        env.set_policy(children)
+        if normalizer is not None:
+            normalizer.freeze()      # one set of tables per generation: every child sees the same
+        env.set_policy(children, normalizer=normalizer)
         env.reset_where(mask=everyone)
         fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
         archive.step(behaviour, gen, k=k, seed=seed, rate=rate, group_size=S, out=nov)
@@ -603,7 +629,8 @@ def run_policy_nslc(env, policy, n_generations, archive, k=15, rate=0.02, period
 
 
 def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples=4, seed=0, rate=0.05, sigma=0.1, group_size=None,
-                          max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None, sigma_line=None):
+                          max_steps=EPISODE_CAP, on_error="raise", log=None, on_generation=None, sigma_line=None,
+                          normalizer=None):
     """MAP-Elites for device policies: ``grid`` (an ``elites.EliteGrid`` of M = n_envs / ``group_size`` blocks over descriptor rows
     of ``2 * samples`` words on the env's device) keeps, per block of consecutive creatures -- a morphology -- and per cell of
     behaviour space, the best controller seen so far.  Generation 0 evaluates ``policy`` (one weight set per creature of ``env``,
@@ -619,7 +646,9 @@ def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples
 
     ``grid`` may be an ``elites.CentroidArchive`` over rows of ``2 * samples`` words: insertion is then by nearest centroid.
     ``sigma_line``: None is the emission above; a float switches it to ``grid.emit_line(sigma_iso=sigma, sigma_line=sigma_line)``,
-    the iso+line variation between two elites, which moves every element: ``rate`` is then unused."""
+    the iso+line variation between two elites, which moves every element: ``rate`` is then unused.
+    ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
+    a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
     from .elites import EliteGrid
     if not isinstance(grid, EliteGrid):
         raise ValueError("run_policy_map_elites: grid must be an elites.EliteGrid")
@@ -652,7 +681,9 @@ def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples
             else:
                 grid.emit_line(gen, seed=seed, sigma_iso=sigma, sigma_line=float(sigma_line), n_children=n, out=children)
             env.reset_where(mask=everyone)
-        env.set_policy(children)
+        if normalizer is not None:
+            normalizer.freeze()      # one set of tables per generation: every child sees the same
+        env.set_policy(children, normalizer=normalizer)
         fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
         grid.insert(children, fit, behaviour, group_size=S)
         stats = torch.stack((fit.min(), fit.max(), fit.mean(), grid.n_filled.sum().to(torch.float64), grid.qd_score().sum())).cpu().tolist()

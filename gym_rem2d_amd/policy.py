@@ -668,3 +668,183 @@ class SeparableES:
             for a, b in zip(state[k], mine[k]):
                 b.copy_(a)
         self.t = state["t"]
+
+
+class ObsNormalizer:
+    """Running mean / standard deviation of the policies' input words, kept on the device in exact integer sums and applied inside
+    the forward pass (include/rem2d_obsnorm.h): ARS's "V2", OpenAI-ES's virtual batch normalisation.  A block is
+    ``group_size`` consecutive population rows -- row r belongs to block ``r // group_size`` -- and every block has its own
+    statistics of the ``Dn = 8 + 6 * max_bodies + n_rays`` words of a row (a ``RecurrentPolicy``'s context words are not normalised).
+    ``accumulate`` adds rows to the sums; ``freeze`` turns the sums into the two float32 tables ``mu`` and ``inv`` (``tables``) that
+    a normalised forward pass stages a row through: ``clamp((x - mu) * inv, -clip, clip)``.  Until a block holds ``min_count`` rows
+    (default: ``max(2, group_size)``) its tables are the identity; a word whose variance stays below ``min_var`` gets ``inv = 0``
+    (switched off).  ``clip`` may be ``inf``.  A row with a NaN or an infinite word contributes nothing; words are clamped to
+    +-2048 and quantised to 2**-12 on their way into the sums, which makes them exact: the same bits whatever the launch shape, and
+    two calls equal one call on the concatenation.
+
+    A block may take ``2**39`` rows in its lifetime.  The object keeps a host-side upper bound (``offered``: the most rows any one
+    block can have been given, call by call) and raises ``OverflowError`` before a call that could pass it; ``reset()`` starts
+    over.  ``BatchedModular2D.set_policy(policy, normalizer=...)`` attaches one to a population; ``forward`` is the kernel alone."""
+
+    CAPACITY = 2 ** _lib.OBSNORM_CAPACITY_LOG2
+
+    def __init__(self, n_blocks, group_size, max_bodies, n_rays, clip=5.0, min_count=None, min_var=2.0 ** -20, device="cuda"):
+        M, S, MB, R = (int(v) for v in (n_blocks, group_size, max_bodies, n_rays))
+        if M < 1 or S < 1 or M * S > 2 ** 31 - 1:
+            raise ValueError("ObsNormalizer: n_blocks and group_size must be at least 1 and their product at most 2^31 - 1, not %r and %r"
+                             % (n_blocks, group_size))
+        if not 1 <= MB <= control.MAX_BODIES or not 0 <= R <= sense.MAX_RAYS:
+            raise ValueError("ObsNormalizer: max_bodies must be 1..%d and n_rays 0..%d, not %r and %r"
+                             % (control.MAX_BODIES, sense.MAX_RAYS, max_bodies, n_rays))
+        if not float(clip) > 0.0:
+            raise ValueError("ObsNormalizer: clip must be greater than 0 (it may be inf), not %r" % (clip,))
+        min_count = max(2, S) if min_count is None else min_count
+        if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= int(min_count) < 2 ** 63:
+            raise ValueError("ObsNormalizer: min_count must be an integer of at least 1, not %r" % (min_count,))
+        mv = float(np.float32(min_var))
+        if not mv > 0.0 or not math.isfinite(mv):
+            raise ValueError("ObsNormalizer: min_var must be positive and finite as binary32, not %r" % (min_var,))
+        self.n_blocks, self.group_size, self.max_bodies, self.n_rays = M, S, MB, R
+        self.width = input_width(MB, R)
+        self.clip, self.min_count, self.min_var = float(np.float32(clip)), int(min_count), mv
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.count = torch.zeros(M, dtype=torch.int64, device=dev)
+        self.s1, self.s2hi, self.s2lo = (torch.zeros((M, self.width), dtype=torch.int64, device=dev) for _ in range(3))
+        self.mu = torch.zeros((M, self.width), dtype=torch.float32, device=dev)
+        self.inv = torch.ones((M, self.width), dtype=torch.float32, device=dev)
+        self.offered = 0
+
+    @property
+    def device(self):
+        return self.count.device
+
+    @property
+    def tables(self):
+        """``(mu, inv)``: float32 ``[n_blocks, Dn]`` each, as the last ``freeze()`` left them (the identity before the first)"""
+        return self.mu, self.inv
+
+    def reset(self):
+        """Empty sums, identity tables, a fresh capacity."""
+        for t in (self.count, self.s1, self.s2hi, self.s2lo, self.mu):
+            t.zero_()
+        self.inv.fill_(1.0)
+        self.offered = 0
+
+    def _offer(self, what, n_rows):
+        """Count a call that offers ``n_rows`` rows against the capacity: no block can get more than group_size of them"""
+        most = min(int(n_rows), self.group_size)
+        if self.offered + most > self.CAPACITY:
+            raise OverflowError("%s: a block may have been given %d rows already; %d more could pass the capacity of 2^%d rows per block "
+                                "(reset() starts over)" % (what, self.offered, most, _lib.OBSNORM_CAPACITY_LOG2))
+        return most
+
+    def descriptor(self, row_chunk=0):
+        """rem2d_obsnorm over this object's state and tables; no row, policy or stream is set."""
+        n = _lib.Obsnorm()
+        n.max_bodies, n.n_rays, n.n_blocks, n.group_size = self.max_bodies, self.n_rays, self.n_blocks, self.group_size
+        n.row_chunk, n.context, n.clip, n.min_var, n.min_count, n.n_rows, n.reserved = int(row_chunk), 0, self.clip, self.min_var, self.min_count, 0, 0
+        n.count, n.s1, n.s2hi, n.s2lo = (t.data_ptr() for t in (self.count, self.s1, self.s2hi, self.s2lo))
+        n.mu, n.inv = self.mu.data_ptr(), self.inv.data_ptr()
+        return n
+
+    def _on_gpu(self, what):
+        if self.device.type != "cuda":
+            raise ValueError("%s: the normaliser is on %s; build it with device='cuda'" % (what, self.device))
+
+    def accumulate(self, obs, frac=None, row_mask=None, row_chunk=0, wide=False):
+        """Add rows to the sums (rem2d_obsnorm_accumulate) on the current stream: ``obs`` float32 ``[N, 8 + 6 * max_bodies]``,
+        ``frac`` float32 ``[N, n_rays]`` (None when n_rays is 0), ``N <= n_blocks * group_size``; ``row_mask`` uint8 ``[N]``: 0 keeps
+        a row out.  ``row_chunk``: rows of a block per wavefront, 0 for the library's choice; no result depends on it."""
+        dev = self.device
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
+            raise ValueError("ObsNormalizer.accumulate: obs must be a 2-d tensor")
+        N = int(obs.shape[0])
+
+        def ok(t, dtype, shape, what):
+            if not _tier.is_tensor(t, dtype, shape, dev):
+                raise ValueError("ObsNormalizer.accumulate: %s must be a contiguous %s %r tensor on %s" % (what, dtype, shape, dev))
+        ok(obs, torch.float32, (N, control.width(self.max_bodies)), "obs")
+        if self.n_rays:
+            ok(frac, torch.float32, (N, self.n_rays), "frac")
+        if row_mask is not None:
+            ok(row_mask, torch.uint8, (N,), "row_mask")
+        if N > self.n_blocks * self.group_size:
+            raise ValueError("ObsNormalizer.accumulate: %d rows are more than n_blocks * group_size = %d" % (N, self.n_blocks * self.group_size))
+        if not 0 <= int(row_chunk) <= _lib.OBSNORM_MAX_CHUNK:
+            raise ValueError("ObsNormalizer.accumulate: row_chunk must be 0..%d, not %r" % (_lib.OBSNORM_MAX_CHUNK, row_chunk))
+        most = self._offer("ObsNormalizer.accumulate", N)
+        self._on_gpu("ObsNormalizer.accumulate")
+        if N == 0:                  # (nothing to add, and an empty tensor has no address to hand over)
+            return
+        n = self.descriptor(row_chunk)
+        n.n_rows, n.obs, n.frac = N, obs.data_ptr(), (frac.data_ptr() if self.n_rays else None)
+        n.row_mask = None if row_mask is None else row_mask.data_ptr()
+        _tier.launch(_lib.lib(wide).rem2d_obsnorm_accumulate, n, dev, wide, stream_member=True)
+        self.offered += most
+
+    def freeze(self, wide=False):
+        """The tables of the sums as they stand (rem2d_obsnorm_freeze), on the current stream; returns ``tables``."""
+        self._on_gpu("ObsNormalizer.freeze")
+        _tier.launch(_lib.lib(wide).rem2d_obsnorm_freeze, self.descriptor(), self.device, wide, stream_member=True)
+        return self.tables
+
+    def _fits(self, what, policy, n_rows):
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError("%s: policy must be an MLPPolicy" % what)
+        if policy.max_bodies != self.max_bodies or policy.n_rays != self.n_rays:
+            raise ValueError("%s: the policy has max_bodies %d and %d rays, the normaliser %d and %d"
+                             % (what, policy.max_bodies, policy.n_rays, self.max_bodies, self.n_rays))
+        if policy.device != self.device:
+            raise ValueError("%s: the policy is on %s, the normaliser on %s" % (what, policy.device, self.device))
+        if int(n_rows) > self.n_blocks * self.group_size:
+            raise ValueError("%s: %d rows are more than n_blocks * group_size = %d" % (what, n_rows, self.n_blocks * self.group_size))
+
+    def forward(self, policy, obs, frac=None, memory=None, reset=None, out=None, row_mask=None, wide=False):
+        """The normalised forward pass alone (rem2d_obsnorm_forward; with a ``RecurrentPolicy`` rem2d_obsnorm_forward_memory, which
+        reads and rewrites ``memory`` in place) on the current stream, under the tables as they stand.  Arguments and return value
+        as ``MLPPolicy.forward`` / ``RecurrentPolicy.forward`` take and give them; ``obs`` and ``frac`` are not written."""
+        self._fits("ObsNormalizer.forward", policy, obs.shape[0])
+        self._on_gpu("ObsNormalizer.forward")
+        if out is None:
+            out = policy._targets(int(obs.shape[0]))
+        n = self.descriptor()
+        if isinstance(policy, RecurrentPolicy):
+            q = policy.descriptor(obs, frac, out[0], out[1], memory, reset, row_mask)
+            n.context, n.memory, n.reset = q.context, q.memory, q.reset
+            self._call(_lib.lib(wide).rem2d_obsnorm_forward_memory, n, q.p, wide)
+        else:
+            self._call(_lib.lib(wide).rem2d_obsnorm_forward, n, policy.descriptor(obs, frac, out[0], out[1], row_mask), wide)
+        return out
+
+    def _call(self, fn, n, p, wide):
+        """``fn(&n, &p)`` queued on the current stream of the normaliser's device, checked"""
+        import ctypes as C
+        with torch.cuda.device(self.device):
+            n.stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(fn(C.byref(n), C.byref(p)), wide)
+
+    # ---- checkpoints ----
+    def state(self):
+        """A plain dict for a checkpoint: the sums ``count``, ``s1``, ``s2hi``, ``s2lo`` (int64 CPU tensors), the tables ``mu`` and
+        ``inv`` (float32 CPU tensors) and ``offered``."""
+        s = {k: getattr(self, k).detach().cpu().clone() for k in ("count", "s1", "s2hi", "s2lo", "mu", "inv")}
+        s["offered"] = int(self.offered)
+        return s
+
+    def load_state(self, state):
+        """Continue from ``state()``'s dict: the tensors are copied into the object's buffers (same shapes), ``offered`` is set."""
+        names = ("count", "s1", "s2hi", "s2lo", "mu", "inv")
+        if not isinstance(state, dict) or any(k not in state for k in names + ("offered",)):
+            raise ValueError("ObsNormalizer.load_state: state must be a dict with %s and offered" % ", ".join(names))
+        off = state["offered"]
+        if isinstance(off, bool) or not isinstance(off, int) or not 0 <= off <= self.CAPACITY:
+            raise ValueError("ObsNormalizer.load_state: offered must be an integer in 0..2^%d, not %r" % (_lib.OBSNORM_CAPACITY_LOG2, off))
+        for k in names:
+            a, b = state[k], getattr(self, k)
+            if not isinstance(a, torch.Tensor) or a.dtype != b.dtype or a.shape != b.shape:
+                raise ValueError("ObsNormalizer.load_state: %s must be a %s tensor of shape %r" % (k, b.dtype, tuple(b.shape)))
+        for k in names:
+            getattr(self, k).copy_(state[k])
+        self.offered = off
