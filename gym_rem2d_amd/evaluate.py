@@ -127,6 +127,26 @@ def _episode(env, max_steps, chunk, compact, step=None):
             break
 
 
+def _replay_env(env, uploaded, ids, wide, options):
+    """A fresh BatchedModular2D that holds, reset, exactly the creatures ``ids`` (a sorted array) of ``uploaded`` ([(Morphology, ids)]
+    as reset_batches takes them), creature ``ids[i]`` at index i: ``env``'s terrain, seed, flags and device, the build ``wide``, its
+    launch options with ``options`` on top, on_handover="flag".  The caller closes it."""
+    from .env import BatchedModular2D
+    opts = dict(env.options)
+    opts.pop("train_fault", None)   # (a test hook of the first run's launch form; the second run is there to be trusted)
+    opts.update(options or {})
+    again = BatchedModular2D(hardcore=env.hardcore, flat=env.flat, seed=env._seed, device=env.device, flags=env.flags,
+                             wide=wide, options=opts, on_handover="flag")
+    again.terrain = env._terrain()
+    batches = []
+    for morph, idx in uploaded:
+        sel = np.nonzero(np.isin(idx, ids))[0]
+        if sel.size:
+            batches.append((morph.take(sel), np.searchsorted(ids, idx[sel]).tolist()))
+    again.reset_batches(batches, int(ids.size))
+    return again
+
+
 def reevaluate(env, mask, fit, wide=None, options=None, max_steps=EPISODE_CAP, chunk=100):
     """Creatures are independent and an episode is a function of the morphology alone (fixed terrain seed, open-loop controller:
     SURVEY facts 5 / 6), so any subset can simply be evaluated AGAIN from reset in worlds of another build or launch form -- same
@@ -138,23 +158,11 @@ def reevaluate(env, mask, fit, wide=None, options=None, max_steps=EPISODE_CAP, c
         more -- re-run in librem2d_wide.so (32 / 12);
       * the hand-over fallback: creatures a step train flagged REM2D_ERR_HANDOVER -- re-run in the SAME build on per-step launches
         (``options={"fuse_velpost": 1}``: no hand-over between workgroups exists there)."""
-    from .env import BatchedModular2D
     idx_bad = torch.nonzero(mask).flatten().cpu().numpy()
     codes = torch.zeros(mask.shape, dtype=torch.int32, device=mask.device)
     if idx_bad.size == 0:
         return codes
-    opts = dict(env.options)
-    opts.pop("train_fault", None)   # (a test hook of the first run's launch form; the second run is there to be trusted)
-    opts.update(options or {})
-    again = BatchedModular2D(hardcore=env.hardcore, flat=env.flat, seed=env._seed, device=env.device, flags=env.flags,
-                             wide=env.wide if wide is None else wide, options=opts, on_handover="flag")
-    again.terrain = env._terrain()
-    batches = []
-    for morph, idx in env._uploaded:
-        sel = np.nonzero(np.isin(idx, idx_bad))[0]
-        if sel.size:
-            batches.append((morph.take(sel), np.searchsorted(idx_bad, idx[sel]).tolist()))
-    again.reset_batches(batches, int(idx_bad.size))
+    again = _replay_env(env, env._uploaded, idx_bad, env.wide if wide is None else wide, options)
     _episode(again, max_steps, chunk, compact=False)
     where = torch.as_tensor(idx_bad, dtype=torch.long, device=fit.device)
     fit.index_copy_(0, where, again.fitness.to(fit.device))
@@ -257,6 +265,12 @@ def run_episode(env, max_steps=EPISODE_CAP, chunk=100, on_error="fallback", comp
     return env.fitness.clone()
 
 
+def _strict_on_error(on_error):
+    """The episodes of device policies have no second attempt: on_error is one of check_errors' three modes"""
+    if on_error not in ("raise", "warn", "ignore"):
+        raise ValueError("on_error must be 'raise', 'warn' or 'ignore', not %r" % (on_error,))
+
+
 def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_error="raise", normalizer=None):
     """run_episode for a BatchedModular2D with a device policy attached (``env.set_policy``): the same episode loop, every step
     preceded by the policy's control step (``env.step_policy``), chunks of ``chunk`` steps queued without a synchronisation in
@@ -266,8 +280,7 @@ def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_e
     with wide=True where creatures may outgrow the default build's contact slots.  ``env.last_episode`` is None afterwards.
     ``normalizer``: a ``policy.ObsNormalizer`` that is only APPLIED: the env's policy is attached again under it with ``accumulate=False`` (its tables as they stand; its sums are
     not touched).  Without it the env runs as ``set_policy`` left it, a normaliser attached there included."""
-    if on_error not in ("raise", "warn", "ignore"):
-        raise ValueError("on_error must be 'raise', 'warn' or 'ignore', not %r" % (on_error,))
+    _strict_on_error(on_error)
     if env.policy is None:
         raise ValueError("run_policy_episode: the env has no policy (set_policy first)")
     if normalizer is not None:
@@ -276,6 +289,94 @@ def run_policy_episode(env, max_steps=EPISODE_CAP, chunk=100, compact=True, on_e
     _episode(env, max_steps, chunk, compact, step=env.step_policy)
     check_errors(env, on_error)
     return env.fitness.clone()
+
+
+# ---- the generational loops of device policies: one driver; a loop keeps its checks, its buffers and its two steps
+def _fitness_row(fit, *more):
+    """(min, max, mean) of the fitness and ``more`` float64 scalars on the device: one read, the only numbers that leave it"""
+    return tuple(torch.stack((fit.min(), fit.max(), fit.mean()) + more).cpu().tolist())
+
+
+def _generations(env, first, n_generations, produce, episode, update, on_generation, log, normalizer=None, reset_first=False,
+                 rows_from=1, row=_fitness_row, text="Generation %d : Min %s, Max %s, Avg %s"):
+    """Generations ``first`` (0 or 1) .. n_generations of a search loop.  Every one is ``produce(gen)`` -> the policy to run;
+    ``normalizer.freeze()`` (one set of tables per generation: every child sees the same) and ``env.set_policy``;
+    ``env.reset_where`` of everyone, except in generation 0, which runs the population as the caller reset it; ``episode()`` ->
+    ``(fitness, ...)``; ``update(gen, that policy, fitness, ...)`` -> what ``on_generation`` is told after ``gen``; from generation
+    ``rows_from`` on the history row ``(gen,) + row(fitness)`` and, after ``on_generation``, the ``log`` line ``text % row``.
+    ``reset_first``: reset_where comes before freeze / set_policy instead of after.  The order is part of the launch arguments:
+    set_policy clears the env's note that a reset happened and reset_where sets it, so it decides whether a RecurrentPolicy's
+    first act() is handed a reset mask (the context words are zero either way).  Returns ``(fitness, history)`` of the last
+    generation run."""
+    everyone = torch.ones(env.n_envs, dtype=torch.uint8, device=env.worlds[0][0].device) if env.worlds else None
+    fit, history = None, []
+    for gen in range(first, int(n_generations) + 1):
+        running = produce(gen)
+        if gen and reset_first:
+            env.reset_where(mask=everyone)
+        if normalizer is not None:
+            normalizer.freeze()
+        env.set_policy(running, normalizer=normalizer)
+        if gen and not reset_first:
+            env.reset_where(mask=everyone)
+        fit, *seen = episode()
+        told = update(gen, running, fit, *seen)
+        if gen >= rows_from:
+            history.append((gen,) + row(fit))
+        if on_generation:
+            on_generation(gen, *told)
+        if log and gen >= rows_from:
+            log(text % history[-1])
+    return fit, history
+
+
+def _policy_episode(env, max_steps, chunk, on_error):
+    """A loop's episode without a descriptor.  (compact=False: compaction would drop the device morphology the next reset needs)"""
+    return lambda: (run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error),)
+
+
+def _behaviour_episode(env, period, samples, max_steps, on_error):
+    """A loop's episode with a descriptor -> (fitness, behaviour)"""
+    return lambda: run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+
+
+def _population(what, env, described=False):
+    """The population a loop needs in place -> how many creatures; ``described``: one whose descriptors can be recorded"""
+    if not env.worlds:
+        raise ValueError("%s: no population in place (reset first)" % what)
+    if described and (env._autoreset is not None or env._stream_rec is not None):
+        raise ValueError("%s: descriptors are not recorded under auto-reset or streaming" % what)
+    return env.n_envs
+
+
+def _es_groups(what, n, mean, group_size):
+    """-> S, the children per mean of run_policy_es and run_policy_nses"""
+    S = n if group_size is None else int(group_size)
+    if S < 2 or S % 2 or n % S or mean.n_sets * S != n:
+        raise ValueError("%s: %d creatures are not %d means times an even group_size (%r)" % (what, n, mean.n_sets, group_size))
+    return S
+
+
+def _period(period, samples, max_steps):
+    """The steps between two samples of a loop's descriptor; default: max_steps over samples, rounded up"""
+    return -(-int(max_steps) // samples) if period is None else int(period)
+
+
+def _archive_fits(what, env, archive, n_blocks, samples):
+    """The novelty archive of a loop: its shape, then its device -> the env's device"""
+    if archive.n_blocks != n_blocks or archive.width != 2 * samples:
+        raise ValueError("%s: the archive must have %d blocks of width %d, not %d of %d"
+                         % (what, n_blocks, 2 * samples, archive.n_blocks, archive.width))
+    dev = env.worlds[0][0].device
+    if archive.device != dev:
+        raise ValueError("%s: the archive must be on %s, not %s" % (what, dev, archive.device))
+    return dev
+
+
+def _es_scratch(mean, group_size, dev):
+    """The scratch tensor es_update asks for, or None where the update is one launch"""
+    need = mean.es_scratch_bytes(group_size)
+    return torch.empty(need // 8, dtype=torch.int64, device=dev) if need else None
 
 
 def run_policy_generations(env, policy, n_generations, seed=0, rate=0.05, sigma=0.1, tournsize=4, group_size=None, elite=0,
@@ -292,31 +393,24 @@ def run_policy_generations(env, policy, n_generations, seed=0, rate=0.05, sigma=
     do not change: group_size names the blocks of consecutive creatures whose policies compete (those of one morphology).
     ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
     a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
-    n = env.n_envs
-    everyone = torch.ones(n, dtype=torch.uint8, device=env.worlds[0][0].device) if env.worlds else None
-    if normalizer is not None:
-        normalizer.freeze()      # one set of tables per generation: every child sees the same
-    env.set_policy(policy, normalizer=normalizer)
-    policy = env.policy
-    fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
-    if on_generation:
-        on_generation(0, policy, fit)
-    spare, history = None, []
-    for gen in range(1, int(n_generations) + 1):
-        child = policy.evolve(fit, gen, seed=seed, rate=rate, sigma=sigma, tournsize=tournsize, group_size=group_size, elite=elite,
-                              out=spare)
-        spare, policy = (policy if gen > 1 else None), child    # (generation 0's buffers are the caller's: never written)
-        if normalizer is not None:
-            normalizer.freeze()      # one set of tables per generation: every child sees the same
-        env.set_policy(policy, normalizer=normalizer)
-        env.reset_where(mask=everyone)
-        fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
-        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
-        history.append((gen,) + tuple(stats))
-        if on_generation:
-            on_generation(gen, policy, fit)
-        if log:
-            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+    spare = last = None
+
+    def child(gen):
+        nonlocal policy, spare
+        if gen:
+            new = policy.evolve(last, gen, seed=seed, rate=rate, sigma=sigma, tournsize=tournsize, group_size=group_size, elite=elite,
+                                out=spare)
+            spare, policy = (policy if gen > 1 else None), new    # (generation 0's buffers are the caller's: never written)
+        return policy
+
+    def scored(gen, attached, fit):
+        nonlocal policy, last
+        if not gen:
+            policy = env.policy      # (the caller's, on the env's device)
+        last = fit
+        return policy, fit
+    fit, history = _generations(env, 0, n_generations, child, _policy_episode(env, max_steps, chunk, on_error), scored, on_generation, log,
+                                normalizer=normalizer)
     return policy, fit, history
 
 
@@ -336,34 +430,25 @@ def run_policy_es(env, mean, n_generations, seed=0, sigma=0.1, lr=0.05, group_si
     NEW mean (a checkpoint hook: clone what must last, every buffer is overwritten one or two generations later).
     ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
     a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
-    if not env.worlds:
-        raise ValueError("run_policy_es: no population in place (reset first)")
-    n = env.n_envs
-    S = n if group_size is None else int(group_size)
-    if S < 2 or S % 2 or n % S or mean.n_sets * S != n:
-        raise ValueError("run_policy_es: %d creatures are not %d means times an even group_size (%r)" % (n, mean.n_sets, group_size))
+    n = _population("run_policy_es", env)
+    S = _es_groups("run_policy_es", n, mean, group_size)
     dev = env.worlds[0][0].device
-    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
     mean = mean.to(dev)
-    children, spare, scratch, fit, history = None, None, None, None, []
-    need = mean.es_scratch_bytes(S)
-    if need:
-        scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
-    for gen in range(1, int(n_generations) + 1):
+    children = spare = None
+    scratch = _es_scratch(mean, S, dev)
+
+    def sample(gen):
+        nonlocal children
         children = mean.es_sample(gen, seed=seed, sigma=sigma, group_size=S, out=children)
-        if normalizer is not None:
-            normalizer.freeze()      # one set of tables per generation: every child sees the same
-        env.set_policy(children, normalizer=normalizer)
-        env.reset_where(mask=everyone)
-        fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
+        return children
+
+    def update(gen, children, fit):
+        nonlocal mean, spare
         new = mean.es_update(fit, gen, seed=seed, sigma=sigma, lr=lr, group_size=S, out=spare, scratch=scratch)
         spare, mean = (mean if gen > 1 else None), new      # (the first mean's buffers are the caller's: never written)
-        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
-        history.append((gen,) + tuple(stats))
-        if on_generation:
-            on_generation(gen, children, fit, mean)
-        if log:
-            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+        return children, fit, mean
+    fit, history = _generations(env, 1, n_generations, sample, _policy_episode(env, max_steps, chunk, on_error), update, on_generation, log,
+                                normalizer=normalizer)
     return mean, fit, history
 
 
@@ -377,30 +462,16 @@ def run_policy_snes(env, es, n_generations, seed=0, max_steps=EPISODE_CAP, chunk
     there for a checkpoint hook).
     ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
     a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
-    if not env.worlds:
-        raise ValueError("run_policy_snes: no population in place (reset first)")
-    n, S = env.n_envs, es.group_size
+    n = _population("run_policy_snes", env)
+    S = es.group_size
     if n % S or es.mean.n_sets * S != n:
         raise ValueError("run_policy_snes: %d creatures are not %d means times the strategy's group_size %d" % (n, es.mean.n_sets, S))
     dev = env.worlds[0][0].device
     if es.device != dev:
         raise ValueError("run_policy_snes: the strategy is on %s, the population on %s" % (es.device, dev))
-    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
-    fit, history = None, []
-    for gen in range(1, int(n_generations) + 1):
-        children = es.sample(gen, seed=seed)
-        if normalizer is not None:
-            normalizer.freeze()      # one set of tables per generation: every child sees the same
-        env.set_policy(children, normalizer=normalizer)
-        env.reset_where(mask=everyone)
-        fit = run_policy_episode(env, max_steps, chunk, compact=False, on_error=on_error)
-        mean = es.update(fit, gen, seed=seed)
-        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
-        history.append((gen,) + tuple(stats))
-        if on_generation:
-            on_generation(gen, children, fit, mean)
-        if log:
-            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+    fit, history = _generations(env, 1, n_generations, lambda gen: es.sample(gen, seed=seed), _policy_episode(env, max_steps, chunk, on_error),
+                                lambda gen, children, fit: (children, fit, es.update(fit, gen, seed=seed)), on_generation, log,
+                                normalizer=normalizer)
     return es.mean, fit, history
 
 
@@ -412,10 +483,8 @@ def run_behaviour_episode(env, period, samples, max_steps=EPISODE_CAP, on_error=
     retire rows.  Returns ``(fitness, behaviour)``: float64 ``[N]`` (a clone) and the env's float32 ``[N, 2 * samples]`` descriptor
     buffer itself (clone what must last), slot k the root position at step ``(k + 1) * period`` or the last one recorded before the
     creature's episode ended (include/rem2d_novelty.h).  on_error: "raise" | "warn" | "ignore", as run_policy_episode."""
-    if on_error not in ("raise", "warn", "ignore"):
-        raise ValueError("on_error must be 'raise', 'warn' or 'ignore', not %r" % (on_error,))
-    if not env.worlds:
-        raise ValueError("run_behaviour_episode: no population in place (reset first)")
+    _strict_on_error(on_error)
+    _population("run_behaviour_episode", env)
     have = env._descriptor
     if have is None or have[0] != int(period) or have[1] != (None if samples is None else int(samples)):
         env.set_descriptor(period, samples)
@@ -465,75 +534,50 @@ def run_policy_nses(env, mean, n_generations, archive, k=15, rate=0.02, weights=
     tensors themselves and the NEW mean (clone what must last).
     ``normalizer``: a ``policy.ObsNormalizer`` whose blocks cover the creatures: every generation starts with its ``freeze()`` -- within
     a generation every child sees the same tables -- and the generation's episodes add what they observe to its sums."""
-    if not env.worlds:
-        raise ValueError("run_policy_nses: no population in place (reset first)")
-    n = env.n_envs
-    S = n if group_size is None else int(group_size)
-    if S < 2 or S % 2 or n % S or mean.n_sets * S != n:
-        raise ValueError("run_policy_nses: %d creatures are not %d means times an even group_size (%r)" % (n, mean.n_sets, group_size))
+    n = _population("run_policy_nses", env)
+    S = _es_groups("run_policy_nses", n, mean, group_size)
     wf, wn = (int(w) for w in weights)
     if (wf, wn) != tuple(weights) or abs(wf) > 32767 or abs(wn) > 32767:
         raise ValueError("run_policy_nses: weights must be two integers of at most 15 bits, not %r" % (weights,))
     samples = int(samples)
-    period = -(-int(max_steps) // samples) if period is None else int(period)
-    if archive.n_blocks != mean.n_sets or archive.width != 2 * samples:
-        raise ValueError("run_policy_nses: the archive must have %d blocks of width %d, not %d of %d"
-                         % (mean.n_sets, 2 * samples, archive.n_blocks, archive.width))
-    dev = env.worlds[0][0].device
-    if archive.device != dev:
-        raise ValueError("run_policy_nses: the archive must be on %s, not %s" % (dev, archive.device))
-    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
+    period = _period(period, samples, max_steps)
+    dev = _archive_fits("run_policy_nses", env, archive, mean.n_sets, samples)
     mean = mean.to(dev)
-    children, spare, scratch, fit, history = None, None, None, None, []
-    need = mean.es_scratch_bytes(S)
-    if need:
-        scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    children = spare = None
+    scratch = _es_scratch(mean, S, dev)
     nov = torch.empty(n, dtype=torch.float64, device=dev)
     util_f, util_n, util = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
-    for gen in range(1, int(n_generations) + 1):
+
+    def sample(gen):
+        nonlocal children
         children = mean.es_sample(gen, seed=seed, sigma=sigma, group_size=S, out=children)
-        if normalizer is not None:
-            normalizer.freeze()      # one set of tables per generation: every child sees the same
-        env.set_policy(children, normalizer=normalizer)
-        env.reset_where(mask=everyone)
-        fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+        return children
+
+    def update(gen, children, fit, behaviour):
+        nonlocal mean, spare
         archive.step(behaviour, gen, k=k, seed=seed, rate=rate, group_size=S, out=nov)
         _es_ranks(mean, fit, S, util_f)
         _es_ranks(mean, nov, S, util_n)
         torch.add(util_f.mul_(wf), util_n, alpha=wn, out=util)
         new = mean.es_update(None, gen, seed=seed, sigma=sigma, lr=lr, group_size=S, out=spare, scratch=scratch, util=util)
         spare, mean = (mean if gen > 1 else None), new      # (the first mean's buffers are the caller's: never written)
-        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
-        history.append((gen,) + tuple(stats))
-        if on_generation:
-            on_generation(gen, children, fit, mean, behaviour, nov, util)
-        if log:
-            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+        return children, fit, mean, behaviour, nov, util
+    fit, history = _generations(env, 1, n_generations, sample, _behaviour_episode(env, period, samples, max_steps, on_error), update,
+                                on_generation, log, normalizer=normalizer)
     return mean, fit, history
 
 
 def _pareto_loop_checks(what, env, n_sets, group_size, even, archive, samples, max_steps, period, on_error):
     """What run_policy_pareto_es and run_policy_nslc refuse, before anything is allocated -> (n, S, samples, period, device)"""
-    if on_error not in ("raise", "warn", "ignore"):
-        raise ValueError("on_error must be 'raise', 'warn' or 'ignore', not %r" % (on_error,))
-    if not env.worlds:
-        raise ValueError("%s: no population in place (reset first)" % what)
-    if env._autoreset is not None or env._stream_rec is not None:
-        raise ValueError("%s: descriptors are not recorded under auto-reset or streaming" % what)
-    n = env.n_envs
+    _strict_on_error(on_error)
+    n = _population(what, env, described=True)
     S = n if group_size is None else int(group_size)
     if S < 1 or n % S or S > _lib.PARETO_MAX_GROUP or (even and (S < 2 or S % 2)) or n_sets * (S if even else 1) != n:
         raise ValueError("%s: %d creatures and %d weight sets are not blocks of %s group_size of at most %d (%r)"
                          % (what, n, n_sets, "an even" if even else "one", _lib.PARETO_MAX_GROUP, group_size))
     samples = int(samples)
-    period = -(-int(max_steps) // samples) if period is None else int(period)
-    if archive.n_blocks != n // S or archive.width != 2 * samples:
-        raise ValueError("%s: the archive must have %d blocks of width %d, not %d of %d"
-                         % (what, n // S, 2 * samples, archive.n_blocks, archive.width))
-    dev = env.worlds[0][0].device
-    if archive.device != dev:
-        raise ValueError("%s: the archive must be on %s, not %s" % (what, dev, archive.device))
-    return n, S, samples, period, dev
+    period = _period(period, samples, max_steps)
+    return n, S, samples, period, _archive_fits(what, env, archive, n // S, samples)
 
 
 def run_policy_pareto_es(env, mean, n_generations, archive, k=15, rate=0.02, period=None, samples=4, seed=0, sigma=0.1, lr=0.05,
@@ -551,33 +595,30 @@ def run_policy_pareto_es(env, mean, n_generations, archive, k=15, rate=0.02, per
     from . import pareto
     n, S, samples, period, dev = _pareto_loop_checks("run_policy_pareto_es", env, mean.n_sets, group_size, True, archive, samples,
                                                      max_steps, period, on_error)
-    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
     mean = mean.to(dev)
-    children, scratch, fit, history = None, None, None, []
-    need = mean.es_scratch_bytes(S)
-    if need:
-        scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    children = None
+    scratch = _es_scratch(mean, S, dev)
     # (the two sets of mean buffers, written in turn: the first mean's buffers are the caller's and never written)
     turn = [mean._like(*(torch.empty_like(t) for t in (mean.w1, mean.b1, mean.w2, mean.b2)), None) for _ in range(2)]
     nov = torch.empty(n, dtype=torch.float64, device=dev)
     obj = torch.empty((n, 2), dtype=torch.float64, device=dev)
     ranks = (None, None, torch.empty(n, dtype=torch.int32, device=dev), None)
-    for gen in range(1, int(n_generations) + 1):
+
+    def sample(gen):
+        nonlocal children
         children = mean.es_sample(gen, seed=seed, sigma=sigma, group_size=S, out=children)
-        env.set_policy(children)
-        env.reset_where(mask=everyone)
-        fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+        return children
+
+    def update(gen, children, fit, behaviour):
+        nonlocal mean
         archive.step(behaviour, gen, k=k, seed=seed, rate=rate, group_size=S, out=nov)
         obj[:, 0].copy_(fit)
         obj[:, 1].copy_(nov)
         util = pareto.rank(obj, group_size=S, out=ranks).util
         mean = mean.es_update(None, gen, seed=seed, sigma=sigma, lr=lr, group_size=S, out=turn[gen & 1], scratch=scratch, util=util)
-        stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
-        history.append((gen,) + tuple(stats))
-        if on_generation:
-            on_generation(gen, children, fit, mean, behaviour, nov, util)
-        if log:
-            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+        return children, fit, mean, behaviour, nov, util
+    fit, history = _generations(env, 1, n_generations, sample, _behaviour_episode(env, period, samples, max_steps, on_error), update,
+                                on_generation, log)
     return mean, fit, history
 
 
@@ -597,34 +638,32 @@ def run_policy_nslc(env, policy, n_generations, archive, k=15, rate=0.02, period
     from . import pareto
     n, S, samples, period, dev = _pareto_loop_checks("run_policy_nslc", env, policy.n_sets, group_size, False, archive, samples,
                                                      max_steps, period, on_error)
-    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
     nov, loc = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2))
     obj = torch.empty((n, 2), dtype=torch.float64, device=dev)
     sel = torch.empty(n, dtype=torch.float64, device=dev)
     ranks = (None, None, torch.empty(n, dtype=torch.int32, device=dev), None)
-    spare, history, fit = None, [], None
-    env.set_policy(policy)
-    policy = env.policy
-    for gen in range(0, int(n_generations) + 1):
+    spare = None
+
+    def child(gen):
+        nonlocal policy, spare
         if gen:
-            child = policy.evolve(sel, gen, seed=seed, rate=mut_rate, sigma=sigma, tournsize=tournsize, group_size=S, elite=elite, out=spare)
-            spare, policy = (policy if gen > 1 else None), child    # (generation 0's buffers are the caller's: never written)
-            env.set_policy(policy)
-            env.reset_where(mask=everyone)
-        fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+            new = policy.evolve(sel, gen, seed=seed, rate=mut_rate, sigma=sigma, tournsize=tournsize, group_size=S, elite=elite, out=spare)
+            spare, policy = (policy if gen > 1 else None), new    # (generation 0's buffers are the caller's: never written)
+        return policy
+
+    def scored(gen, attached, fit, behaviour):
+        nonlocal policy
+        if not gen:
+            policy = env.policy      # (the caller's, on the env's device)
         archive.step(behaviour, gen, k=k, seed=seed, rate=rate, group_size=S, out=nov)
         pareto.local_competition(behaviour, fit, k=k, group_size=S, out=loc)
         obj[:, 0].copy_(nov)
         obj[:, 1].copy_(loc)
         util = pareto.rank(obj, group_size=S, out=ranks).util
         sel.copy_(util)
-        if gen:
-            stats = torch.stack((fit.min(), fit.max(), fit.mean())).cpu().tolist()
-            history.append((gen,) + tuple(stats))
-        if on_generation:
-            on_generation(gen, policy, fit, behaviour, nov, loc, util)
-        if log and gen:
-            log("Generation %d : Min %s, Max %s, Avg %s" % history[-1])
+        return policy, fit, behaviour, nov, loc, util
+    fit, history = _generations(env, 0, n_generations, child, _behaviour_episode(env, period, samples, max_steps, on_error), scored,
+                                on_generation, log)
     return policy, fit, history
 
 
@@ -652,11 +691,7 @@ def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples
     from .elites import EliteGrid
     if not isinstance(grid, EliteGrid):
         raise ValueError("run_policy_map_elites: grid must be an elites.EliteGrid")
-    if not env.worlds:
-        raise ValueError("run_policy_map_elites: no population in place (reset first)")
-    if env._autoreset is not None or env._stream_rec is not None:
-        raise ValueError("run_policy_map_elites: descriptors are not recorded under auto-reset or streaming")
-    n = env.n_envs
+    n = _population("run_policy_map_elites", env, described=True)
     S = n // grid.n_blocks if group_size is None else int(group_size)
     if S < 1 or S * grid.n_blocks != n:
         raise ValueError("run_policy_map_elites: %d creatures in groups of %r are not the grid's %d blocks" % (n, group_size, grid.n_blocks))
@@ -665,33 +700,33 @@ def run_policy_map_elites(env, policy, grid, n_generations, period=None, samples
     samples = int(samples)
     if grid.width != 2 * samples:
         raise ValueError("run_policy_map_elites: the grid must be over rows of %d words (2 * samples), not %d" % (2 * samples, grid.width))
-    period = -(-int(max_steps) // samples) if period is None else int(period)
+    period = _period(period, samples, max_steps)
     dev = env.worlds[0][0].device
     if grid.device != dev:
         raise ValueError("run_policy_map_elites: the grid must be on %s, not %s" % (dev, grid.device))
-    everyone = torch.ones(n, dtype=torch.uint8, device=dev)
-    policy = policy.to(dev)
-    children, fit, history = policy, None, []
-    for gen in range(0, int(n_generations) + 1):
-        if gen > 0:
+    children = policy = policy.to(dev)
+
+    def emit(gen):
+        nonlocal children
+        if gen:
             if children is policy:      # the one child buffer, made of the caller's sets: what a still empty block runs again
                 children = policy._like(policy.w1.clone(), policy.b1.clone(), policy.w2.clone(), policy.b2.clone(), None)
             if sigma_line is None:
                 grid.emit(gen, seed=seed, rate=rate, sigma=sigma, n_children=n, out=children)
             else:
                 grid.emit_line(gen, seed=seed, sigma_iso=sigma, sigma_line=float(sigma_line), n_children=n, out=children)
-            env.reset_where(mask=everyone)
-        if normalizer is not None:
-            normalizer.freeze()      # one set of tables per generation: every child sees the same
-        env.set_policy(children, normalizer=normalizer)
-        fit, behaviour = run_behaviour_episode(env, period, samples, max_steps=max_steps, on_error=on_error)
+        return children
+
+    def insert(gen, children, fit, behaviour):
         grid.insert(children, fit, behaviour, group_size=S)
-        stats = torch.stack((fit.min(), fit.max(), fit.mean(), grid.n_filled.sum().to(torch.float64), grid.qd_score().sum())).cpu().tolist()
-        history.append((gen,) + tuple(stats[:3]) + (int(stats[3]), stats[4]))
-        if on_generation:
-            on_generation(gen, children, fit, behaviour, grid)
-        if log:
-            log("Generation %d : Min %s, Max %s, Avg %s, Cells %d, QD %s" % history[-1])
+        return children, fit, behaviour, grid
+
+    def row(fit):
+        stats = _fitness_row(fit, grid.n_filled.sum().to(torch.float64), grid.qd_score().sum())
+        return stats[:3] + (int(stats[3]), stats[4])
+    fit, history = _generations(env, 0, n_generations, emit, _behaviour_episode(env, period, samples, max_steps, on_error), insert,
+                                on_generation, log, normalizer=normalizer, reset_first=True, rows_from=0, row=row,
+                                text="Generation %d : Min %s, Max %s, Avg %s, Cells %d, QD %s")
     return grid, fit, history
 
 
@@ -709,7 +744,6 @@ def run_stream(env, batches, n_total, slots, max_steps=EPISODE_CAP, chunk=100, o
     them); "fallback" / "penalty" evaluate the creatures with any error bit -- a failed hand-over of the step train, a capacity
     overflow -- again from reset in a fresh env on per-step launches through run_episode(on_error=...), which resolves overflow in
     the wide build and applies the penalty, and leave the EpisodeReport (by id) in ``env.last_episode``."""
-    from .env import BatchedModular2D
     if on_error not in ("fallback", "penalty", "raise", "warn", "ignore"):
         raise ValueError("on_error must be 'fallback', 'penalty', 'raise', 'warn' or 'ignore', not %r" % (on_error,))
     if not env.flags & _lib.FLAG_SKIP_FROZEN:
@@ -743,18 +777,7 @@ def run_stream(env, batches, n_total, slots, max_steps=EPISODE_CAP, chunk=100, o
     bad = torch.nonzero(err != 0).flatten().cpu().numpy()
     handover, overflow, unresolved = [], [], []
     if bad.size:
-        opts = dict(env.options)
-        opts.pop("train_fault", None)
-        opts["fuse_velpost"] = 1                      # per-step launches: no hand-over between workgroups exists there
-        again = BatchedModular2D(hardcore=env.hardcore, flat=env.flat, seed=env._seed, device=env.device, flags=env.flags,
-                                 wide=env.wide, options=opts, on_handover="flag")
-        again.terrain = env._terrain()
-        sub = []
-        for m, idx in batches:
-            sel = np.nonzero(np.isin(idx, bad))[0]
-            if sel.size:
-                sub.append((m.take(sel), np.searchsorted(bad, idx[sel]).tolist()))
-        again.reset_batches(sub, int(bad.size))
+        again = _replay_env(env, batches, bad, env.wide, {"fuse_velpost": 1})   # per-step launches: no hand-over between workgroups exists there
         try:
             fit2 = run_episode(again, max_steps, chunk, on_error=on_error, compact=False)
         except SolverOverflow as e:

@@ -151,3 +151,65 @@ def test_strict_modes_name_the_handover():
 def test_train_fault_encoding():
     assert _lib.train_fault(3) == 3 | (1 << 16) and _lib.train_fault(2, 4, drop=True) == 2 | (4 << 16) | (1 << 30)
     assert _lib.OPTIONS[-1] == "train_fault" and _lib.ERR_CAPACITY == 3
+
+
+def test_replay_env_holds_exactly_the_selected_creatures(monkeypatch):
+    """evaluate._replay_env, behind reevaluate and run_stream's fallback: a fresh env of the first one's terrain, seed, flags and
+    device, without the train_fault hook, with the caller's options on top, that is handed exactly the selected rows of every batch
+    at their places in the sorted id array."""
+    from gym_rem2d_amd import env as envmod
+    made = []
+
+    class Morph:
+        def __init__(self, rows):
+            self.rows = list(rows)
+
+        def take(self, sel):
+            return Morph(self.rows[i] for i in sel)
+
+    class Recording:
+        def __init__(self, **kw):
+            self.kw, self.terrain, self.reset, self.closed = kw, None, None, False
+            made.append(self)
+
+        def reset_batches(self, batches, n_envs):
+            self.reset = ([(m.rows, idx) for m, idx in batches], n_envs)
+
+    class First:
+        hardcore, flat, _seed, device, flags, wide = True, False, 9, "cuda:1", 5, False
+        options = {"fuse_velpost": 0, "train_fault": 77, "graph": 1}
+        _terrain = staticmethod(lambda: "the first env's terrain")
+    monkeypatch.setattr(envmod, "BatchedModular2D", Recording)
+    # three batches with unsorted ids; the subset hits the first and the last and misses the one in the middle
+    uploaded = [(Morph("abcd"), np.array([7, 2, 9, 4])), (Morph("ef"), np.array([5, 1])), (Morph("ghi"), np.array([8, 0, 3]))]
+    ids = np.array([0, 2, 7, 8])
+    a = evaluate._replay_env(First, uploaded, ids, True, None)
+    b = evaluate._replay_env(First, uploaded, ids, False, {"fuse_velpost": 1})
+    assert made == [a, b]
+    for env, wide, options in ((a, True, {"fuse_velpost": 0, "graph": 1}), (b, False, {"fuse_velpost": 1, "graph": 1})):
+        assert env.kw == dict(hardcore=True, flat=False, seed=9, device="cuda:1", flags=5, wide=wide, options=options, on_handover="flag")
+        assert env.terrain == "the first env's terrain" and not env.closed
+        # creature 7 is row `a` of the first batch and third of the ids; 2 is row `b` and second; 8 and 0 are rows `g`, `h` of the last
+        assert env.reset == ([(["a", "b"], [2, 1]), (["g", "h"], [3, 0])], 4)
+    assert First.options == {"fuse_velpost": 0, "train_fault": 77, "graph": 1}        # (the first env's options are not written)
+
+
+def test_both_fallbacks_replay_through_the_one_helper(monkeypatch):
+    """reevaluate hands on the env's own upload, the build asked for and the caller's options; the selected ids are the mask's."""
+    seen = []
+
+    class Again(FakeEnv):
+        def close(self):
+            seen.append("closed")
+
+    def fake(env, uploaded, ids, wide, options):
+        seen.append((uploaded, ids.tolist(), wide, options))
+        return Again([0] * len(ids))
+    monkeypatch.setattr(evaluate, "_replay_env", fake)
+    env = FakeEnv([0, 1, 0, 1])
+    env._uploaded, env.wide = "the upload", False
+    fit = torch.zeros(4, dtype=torch.float64)
+    mask = torch.tensor([False, True, False, True])
+    assert evaluate.reevaluate(env, mask, fit, max_steps=10, chunk=10).tolist() == [0, 0, 0, 0] and fit.tolist() == [0.0, 0.0, 0.0, 1.0]
+    evaluate.reevaluate(env, mask, fit, wide=True, options={"fuse_velpost": 1}, max_steps=10, chunk=10)
+    assert seen == [("the upload", [1, 3], False, None), "closed", ("the upload", [1, 3], True, {"fuse_velpost": 1}), "closed"]
