@@ -137,6 +137,8 @@ static int fail(int code, const std::string &msg) {
         hipError_t e_ = (expr);                                                                        \
         if (e_ != hipSuccess) return fail(REM2D_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+#define OK_TRY(expr) \
+    do { const int rc_ = (expr); if (rc_ != REM2D_OK) return rc_; } while (0)
 
 // Pairs of timing events: made by rem2d_world_enable_timing (outside any timed region), recorded by the step calls, read back by
 // rem2d_world_kernel_time_ms / rem2d_world_step_time_ms.  Launches beyond the pool go untimed.
@@ -1456,20 +1458,40 @@ extern "C" int rem2d_world_render(const rem2d_world *w, const int32_t *creatures
 
 // ---- closed-loop control (include/rem2d_control.h, csrc/rem2d_control.h) ----
 extern "C" int rem2d_control_abi_version(void) { return REM2D_CONTROL_ABI_VERSION; }
-// Checks the worlds of a control call; `what` prefixes the message.
-static int control_worlds_ok(const char *what, rem2d_world *const *worlds, int32_t n_worlds, int32_t max_bodies, int64_t rows,
-                             const void *buffer_dev) {
-    const std::string p = std::string(what) + ": ";
-    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, p + "no worlds");
-    if (!buffer_dev) return fail(REM2D_E_INVALID, p + "NULL device pointer");
-    if (max_bodies < 1 || max_bodies > REM2D_CONTROL_MAX_BODIES)
-        return fail(REM2D_E_INVALID, p + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(max_bodies));
-    if (rows < 0) return fail(REM2D_E_INVALID, p + "negative row count");
+// The refusals that the calls on a list of worlds share, one fault each; `p` is the caller's prefix ("observe: ").  Every call
+// composes them in an order of its own, which tests/golden/world_call_refusals.json holds: no function here knows its caller.
+static int worlds_given(const std::string &p, rem2d_world *const *worlds, int32_t n_worlds) {
+    return worlds && n_worlds > 0 ? REM2D_OK : fail(REM2D_E_INVALID, p + "no worlds");
+}
+static int rows_ok(const std::string &p, int64_t rows) { return rows >= 0 ? REM2D_OK : fail(REM2D_E_INVALID, p + "negative row count"); }
+static int max_bodies_ok(const std::string &p, int32_t max_bodies) {
+    if (max_bodies >= 1 && max_bodies <= REM2D_CONTROL_MAX_BODIES) return REM2D_OK;
+    return fail(REM2D_E_INVALID, p + "max_bodies must be 1.." + std::to_string(REM2D_CONTROL_MAX_BODIES) + ", not " + std::to_string(max_bodies));
+}
+static int world_present(const std::string &p, rem2d_world *const *worlds, int32_t i) {
+    return worlds[i] ? REM2D_OK : fail(REM2D_E_INVALID, p + "world " + std::to_string(i) + " is NULL");
+}
+static int worlds_present(const std::string &p, rem2d_world *const *worlds, int32_t n_worlds) {
+    for (int32_t i = 0; i < n_worlds; ++i) OK_TRY(world_present(p, worlds, i));
+    return REM2D_OK;
+}
+// (lanes, then device: no call has anything between the two)
+static int world_fits(const std::string &p, const rem2d_world *w, const rem2d_world *first) {
+    if (w->cfg.lanes > 64) return fail(REM2D_E_INVALID, p + "more than 64 lanes per creature");
+    return w->cfg.device == first->cfg.device ? REM2D_OK : fail(REM2D_E_INVALID, p + "the worlds must share a device");
+}
+static int world_terrain(const std::string &p, const rem2d_world *w) {
+    return w->haveTerrain ? REM2D_OK : fail(REM2D_E_STATE, p + "rem2d_world_set_terrain must be called first");
+}
+static int world_reset(const std::string &p, const rem2d_world *w) {
+    return w->haveReset ? REM2D_OK : fail(REM2D_E_STATE, p + "rem2d_world_reset (or adopt) must be called first");
+}
+// The order of observe, control, describe and the act calls: world by world, a NULL among them.
+static int worlds_ready(const std::string &p, rem2d_world *const *worlds, int32_t n_worlds) {
     for (int32_t i = 0; i < n_worlds; ++i) {
-        if (!worlds[i]) return fail(REM2D_E_INVALID, p + "world " + std::to_string(i) + " is NULL");
-        if (worlds[i]->cfg.lanes > 64) return fail(REM2D_E_INVALID, p + "more than 64 lanes per creature");
-        if (worlds[i]->cfg.device != worlds[0]->cfg.device) return fail(REM2D_E_INVALID, p + "the worlds must share a device");
-        if (!worlds[i]->haveReset) return fail(REM2D_E_STATE, p + "rem2d_world_reset (or adopt) must be called first");
+        OK_TRY(world_present(p, worlds, i));
+        OK_TRY(world_fits(p, worlds[i], worlds[0]));
+        OK_TRY(world_reset(p, worlds[i]));
     }
     return REM2D_OK;
 }
@@ -1489,62 +1511,60 @@ static unsigned control_table(CtlTable &Tb, rem2d_world *const *worlds, int firs
     Tb.n = n;
     return blocks;
 }
-extern "C" int rem2d_worlds_observe(rem2d_world *const *worlds, int32_t n_worlds, int32_t max_bodies, float *out_dev, int64_t out_rows,
-                                    void *stream) {
-    const int rc = control_worlds_ok("observe", worlds, n_worlds, max_bodies, out_rows, out_dev);
-    if (rc != REM2D_OK) return rc;
+// The launches of a call on checked worlds, one per `table` worlds (CTL_TABLE; STREAM_TABLE where the call's second table is the
+// longer one): launch(first, n, Tb, grid) fills the call's own table for worlds [first, first + n), if it has one, and launches.
+template <typename Launch> static int table_launches(int table, rem2d_world *const *worlds, int n_worlds, Launch launch) {
     HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
-    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
+    for (int first = 0; first < n_worlds; first += table) {
         CtlTable Tb;
-        const unsigned blocks = control_table(Tb, worlds, first, std::min(CTL_TABLE, (int)n_worlds - first));
-        const unsigned per = CTL_THREADS / WAVE;
-        hipLaunchKernelGGL(rem2d_observe_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb,
-                           (int)max_bodies, out_dev, (long long)out_rows);
+        const int n = std::min(table, n_worlds - first);
+        const unsigned blocks = control_table(Tb, worlds, first, n), per = CTL_THREADS / WAVE;
+        launch(first, n, Tb, dim3((blocks + per - 1) / per));
         HIP_TRY(hipGetLastError());
     }
     return REM2D_OK;
+}
+static int observe_launch(rem2d_world *const *worlds, int n_worlds, int max_bodies, float *out_dev, long long out_rows, hipStream_t st) {
+    return table_launches(CTL_TABLE, worlds, n_worlds, [&](int, int, const CtlTable &Tb, dim3 grid) {
+        hipLaunchKernelGGL(rem2d_observe_kernel, grid, dim3(CTL_THREADS), 0, st, Tb, max_bodies, out_dev, out_rows);
+    });
+}
+static int control_launch(rem2d_world *const *worlds, int n_worlds, int mode, const double *values_dev, int max_bodies, long long n_rows,
+                          const unsigned char *mask_dev, hipStream_t st) {
+    return table_launches(CTL_TABLE, worlds, n_worlds, [&](int, int, const CtlTable &Tb, dim3 grid) {
+        hipLaunchKernelGGL(rem2d_control_kernel, grid, dim3(CTL_THREADS), 0, st, Tb, mode, values_dev, max_bodies, n_rows, mask_dev);
+    });
+}
+static int buffer_given(const std::string &p, const void *buffer_dev) {
+    return buffer_dev ? REM2D_OK : fail(REM2D_E_INVALID, p + "NULL device pointer");
+}
+// What observe and control refuse, in their order.
+static int table_call_ok(const std::string &p, rem2d_world *const *worlds, int32_t n_worlds, const void *buffer_dev, int32_t max_bodies,
+                         int64_t rows) {
+    OK_TRY(worlds_given(p, worlds, n_worlds));
+    OK_TRY(buffer_given(p, buffer_dev));
+    OK_TRY(max_bodies_ok(p, max_bodies));
+    OK_TRY(rows_ok(p, rows));
+    return worlds_ready(p, worlds, n_worlds);
+}
+extern "C" int rem2d_worlds_observe(rem2d_world *const *worlds, int32_t n_worlds, int32_t max_bodies, float *out_dev, int64_t out_rows,
+                                    void *stream) {
+    OK_TRY(table_call_ok("observe: ", worlds, n_worlds, out_dev, max_bodies, out_rows));
+    return observe_launch(worlds, n_worlds, max_bodies, out_dev, out_rows, (hipStream_t)stream);
 }
 extern "C" int rem2d_worlds_control(rem2d_world *const *worlds, int32_t n_worlds, int32_t mode, const double *values_dev,
                                     int32_t max_bodies, int64_t n_rows, const uint8_t *mask_dev, void *stream) {
     if (mode != REM2D_CTRL_TARGET && mode != REM2D_CTRL_PARAMS) return fail(REM2D_E_INVALID, "control: unknown mode " + std::to_string(mode));
-    const int rc = control_worlds_ok("control", worlds, n_worlds, max_bodies, n_rows, values_dev);
-    if (rc != REM2D_OK) return rc;
-    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
-    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
-        CtlTable Tb;
-        const unsigned blocks = control_table(Tb, worlds, first, std::min(CTL_TABLE, (int)n_worlds - first));
-        const unsigned per = CTL_THREADS / WAVE;
-        hipLaunchKernelGGL(rem2d_control_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb,
-                           (int)mode, values_dev, (int)max_bodies, (long long)n_rows, (const unsigned char *)mask_dev);
-        HIP_TRY(hipGetLastError());
-    }
-    return REM2D_OK;
+    OK_TRY(table_call_ok("control: ", worlds, n_worlds, values_dev, max_bodies, n_rows));
+    return control_launch(worlds, n_worlds, mode, values_dev, max_bodies, n_rows, mask_dev, (hipStream_t)stream);
 }
 
 // ---- terrain range sensing (include/rem2d_sense.h, csrc/rem2d_sense.h) ----
 extern "C" int rem2d_sense_abi_version(void) { return REM2D_SENSE_ABI_VERSION; }
-extern "C" int rem2d_worlds_sense(rem2d_world *const *worlds, int32_t n_worlds, const double *ray_offsets_dev, int32_t n_rays,
-                                  float *frac_dev, int32_t *hit_dev, int64_t rows, void *stream) {
-    // (arguments first, worlds after: nothing is dereferenced before it has been checked)
-    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "sense: no worlds");
-    if (!ray_offsets_dev || !frac_dev) return fail(REM2D_E_INVALID, "sense: NULL device pointer");
-    if (n_rays < 1 || n_rays > REM2D_SENSE_MAX_RAYS)
-        return fail(REM2D_E_INVALID, "sense: n_rays must be 1.." + std::to_string(REM2D_SENSE_MAX_RAYS) + ", not " + std::to_string(n_rays));
-    if (rows < 0) return fail(REM2D_E_INVALID, "sense: negative row count");
-    for (int32_t i = 0; i < n_worlds; ++i)
-        if (!worlds[i]) return fail(REM2D_E_INVALID, "sense: world " + std::to_string(i) + " is NULL");
-    for (int32_t i = 0; i < n_worlds; ++i) {
-        if (worlds[i]->cfg.lanes > 64) return fail(REM2D_E_INVALID, "sense: more than 64 lanes per creature");
-        if (worlds[i]->cfg.device != worlds[0]->cfg.device) return fail(REM2D_E_INVALID, "sense: the worlds must share a device");
-        if (!worlds[i]->haveTerrain) return fail(REM2D_E_STATE, "sense: rem2d_world_set_terrain must be called first");
-        if (!worlds[i]->haveReset) return fail(REM2D_E_STATE, "sense: rem2d_world_reset (or adopt) must be called first");
-    }
-    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
-    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
-        CtlTable Tb;
+static int sense_launch(rem2d_world *const *worlds, int n_worlds, const double *ray_offsets_dev, int n_rays, float *frac_dev, int *hit_dev,
+                        long long rows, hipStream_t st) {
+    return table_launches(CTL_TABLE, worlds, n_worlds, [&](int first, int n, const CtlTable &Tb, dim3 grid) {
         SenseTable Ts;
-        const int n = std::min(CTL_TABLE, (int)n_worlds - first);
-        const unsigned blocks = control_table(Tb, worlds, first, n);
         memset(&Ts, 0, sizeof(Ts));
         for (int i = 0; i < n; ++i) {
             const Terrain &T = worlds[first + i]->T; // (flx is the start of the 20 planes rem2d_world_set_terrain uploads)
@@ -1552,12 +1572,26 @@ extern "C" int rem2d_worlds_sense(rem2d_world *const *worlds, int32_t n_worlds, 
             Ts.t[i].nEdge = T.nEdge; Ts.t[i].nPoly = T.nPoly;
             Ts.t[i].x0 = T.x0; Ts.t[i].invPitch = T.invPitch;
         }
-        const unsigned per = CTL_THREADS / WAVE;
-        hipLaunchKernelGGL(rem2d_sense_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Ts,
-                           ray_offsets_dev, (int)n_rays, frac_dev, (int *)hit_dev, (long long)rows);
-        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rem2d_sense_kernel, grid, dim3(CTL_THREADS), 0, st, Tb, Ts, ray_offsets_dev, n_rays, frac_dev, hit_dev, rows);
+    });
+}
+extern "C" int rem2d_worlds_sense(rem2d_world *const *worlds, int32_t n_worlds, const double *ray_offsets_dev, int32_t n_rays,
+                                  float *frac_dev, int32_t *hit_dev, int64_t rows, void *stream) {
+    // (arguments first, worlds after: nothing is dereferenced before it has been checked)
+    const std::string p = "sense: ";
+    OK_TRY(worlds_given(p, worlds, n_worlds));
+    OK_TRY(buffer_given(p, ray_offsets_dev));
+    OK_TRY(buffer_given(p, frac_dev));
+    if (n_rays < 1 || n_rays > REM2D_SENSE_MAX_RAYS)
+        return fail(REM2D_E_INVALID, p + "n_rays must be 1.." + std::to_string(REM2D_SENSE_MAX_RAYS) + ", not " + std::to_string(n_rays));
+    OK_TRY(rows_ok(p, rows));
+    OK_TRY(worlds_present(p, worlds, n_worlds));
+    for (int32_t i = 0; i < n_worlds; ++i) {
+        OK_TRY(world_fits(p, worlds[i], worlds[0]));
+        OK_TRY(world_terrain(p, worlds[i]));
+        OK_TRY(world_reset(p, worlds[i]));
     }
-    return REM2D_OK;
+    return sense_launch(worlds, n_worlds, ray_offsets_dev, n_rays, frac_dev, (int *)hit_dev, rows, (hipStream_t)stream);
 }
 
 // ---- device policies (include/rem2d_policy.h, csrc/rem2d_policy.h) ----
@@ -1591,68 +1625,78 @@ static unsigned pow2_at_least(unsigned v) {
     while (p < v) p <<= 1;
     return p;
 }
-// The forward pass of a checked descriptor on `st`; with `nm` the normalised one (include/rem2d_obsnorm.h): the same launch shape.
-static int policy_launch(const rem2d_policy *p, hipStream_t st, const PolNorm *nm = nullptr) {
+// The two families of forward kernels as types, for the one launcher below: Args is the first kernel argument, kernel<V1, V2, NORM>()
+// the instantiation.  rem2d_recurrent.h comes after rem2d_policy.h, so both are known here.
+struct PolicyKernels {
+    typedef PolicyArgs Args;
+    template <int V1, int V2, bool NORM> static auto kernel() { return rem2d_policy_forward_kernel<V1, V2, NORM>; }
+};
+struct RecurrentKernels {
+    typedef RecurrentArgs Args;
+    template <int V1, int V2, bool NORM> static auto kernel() { return rem2d_recurrent_forward_kernel<V1, V2, NORM>; }
+};
+// The forward pass of a checked descriptor on `st`, feed-forward or recurrent, plain (Nm = PolNoNorm) or normalised (PolNorm,
+// include/rem2d_obsnorm.h): one launch shape.  A is the family's zeroed argument struct, P the PolicyArgs in it; `what` names the
+// family in the one refusal that is left to the launch.
+template <typename Kernels, bool NORM>
+static int forward_launch(const char *what, const rem2d_policy *p, typename Kernels::Args &A, PolicyArgs &P,
+                          const typename PolNormArg<NORM>::type &nm, hipStream_t st) {
     if (p->n_rows == 0) return REM2D_OK;
-    PolicyArgs A;
-    memset(&A, 0, sizeof(A));
-    A.w1 = p->w1; A.b1 = p->b1; A.w2 = p->w2; A.b2 = p->b2;
-    A.index = p->index; A.rowMask = p->row_mask;
-    A.obs = p->obs; A.frac = p->frac; A.targets = p->targets; A.valid = p->valid;
-    A.nRows = p->n_rows;
-    A.D = p->d; A.MB = p->max_bodies; A.R = p->n_rays; A.H = p->hidden; A.G = p->n_sets; A.act = p->activation;
-    A.scale = p->scale;
+    P.w1 = p->w1; P.b1 = p->b1; P.w2 = p->w2; P.b2 = p->b2;
+    P.index = p->index; P.rowMask = p->row_mask;
+    P.obs = p->obs; P.frac = p->frac; P.targets = p->targets; P.valid = p->valid;
+    P.nRows = p->n_rows;
+    P.D = p->d; P.MB = p->max_bodies; P.R = p->n_rays; P.H = p->hidden; P.G = p->n_sets; P.act = p->activation;
+    P.scale = p->scale;
     // 16-byte loads where a weight row is whole float4s and its base is aligned (the sets' strides D H and H MB then are too)
     const bool v1 = p->hidden % 4 == 0 && (uintptr_t)p->w1 % 16 == 0;
     const bool v2 = p->max_bodies % 4 == 0 && (uintptr_t)p->w2 % 16 == 0;
     const unsigned need = std::max((unsigned)(p->hidden + (v1 ? 3 : 0)) / (v1 ? 4u : 1u), (unsigned)(p->max_bodies + (v2 ? 3 : 0)) / (v2 ? 4u : 1u));
     const unsigned lpr = std::min((unsigned)WAVE, std::max((unsigned)POL_MIN_LPR, pow2_at_least(need)));
-    A.lpr = (int)lpr;
+    P.lpr = (int)lpr;
     const unsigned rpw = WAVE / lpr;
     const long long blocks = (p->n_rows + rpw - 1) / rpw;
-    if (blocks > 0x7fffffffLL) return fail(REM2D_E_INVALID, "policy: too many rows for one launch");
+    if (blocks > 0x7fffffffLL) return fail(REM2D_E_INVALID, std::string(what) + ": too many rows for one launch");
     const size_t lds = (size_t)rpw * (size_t)(p->d + p->hidden) * sizeof(float);
-    if (nm) {
-        void (*normed)(PolicyArgs, PolNorm) = v1 ? (v2 ? rem2d_policy_forward_kernel<4, 4, true> : rem2d_policy_forward_kernel<4, 1, true>)
-                                              : (v2 ? rem2d_policy_forward_kernel<1, 4, true> : rem2d_policy_forward_kernel<1, 1, true>);
-        hipLaunchKernelGGL(normed, dim3((unsigned)blocks), dim3(WAVE), lds, st, A, *nm);
-        HIP_TRY(hipGetLastError());
-        return REM2D_OK;
-    }
-    void (*kernel)(PolicyArgs, PolNoNorm) = v1 ? (v2 ? rem2d_policy_forward_kernel<4, 4> : rem2d_policy_forward_kernel<4, 1>)
-                                    : (v2 ? rem2d_policy_forward_kernel<1, 4> : rem2d_policy_forward_kernel<1, 1>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, A, PolNoNorm());
+    const auto kernel = v1 ? (v2 ? Kernels::template kernel<4, 4, NORM>() : Kernels::template kernel<4, 1, NORM>())
+                           : (v2 ? Kernels::template kernel<1, 4, NORM>() : Kernels::template kernel<1, 1, NORM>());
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, A, nm);
     HIP_TRY(hipGetLastError());
     return REM2D_OK;
 }
+template <typename Kernels>
+static int forward_launch(const char *what, const rem2d_policy *p, typename Kernels::Args &A, PolicyArgs &P, const PolNorm *nm, hipStream_t st) {
+    return nm ? forward_launch<Kernels, true>(what, p, A, P, *nm, st) : forward_launch<Kernels, false>(what, p, A, P, PolNoNorm(), st);
+}
+static int policy_launch(const rem2d_policy *p, hipStream_t st, const PolNorm *nm = nullptr) {
+    PolicyArgs A;
+    memset(&A, 0, sizeof(A));
+    return forward_launch<PolicyKernels>("policy", p, A, A, nm, st);
+}
 extern "C" int rem2d_policy_forward(const rem2d_policy *p, void *stream) {
-    const int rc = policy_ok("policy", p);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(policy_ok("policy", p));
     return policy_launch(p, (hipStream_t)stream);
+}
+// What rem2d_worlds_act, _act_recurrent and _act_normed do once their descriptors are checked: the ray offsets and the worlds
+// (everything before the first launch), then observe, sense, `forward()` and control on `st`, launches only.
+template <typename Forward>
+static int act(const std::string &s, rem2d_world *const *worlds, int32_t n_worlds, const rem2d_policy *p, const double *ray_offsets_dev,
+               hipStream_t st, Forward forward) {
+    if (p->n_rays > 0 && !ray_offsets_dev) return fail(REM2D_E_INVALID, s + "NULL device pointer (ray offsets)");
+    OK_TRY(worlds_present(s, worlds, n_worlds));
+    OK_TRY(worlds_ready(s, worlds, n_worlds));
+    if (p->n_rays > 0)
+        for (int32_t i = 0; i < n_worlds; ++i) OK_TRY(world_terrain(s, worlds[i]));
+    OK_TRY(observe_launch(worlds, n_worlds, p->max_bodies, const_cast<float *>(p->obs), p->n_rows, st));
+    if (p->n_rays > 0) OK_TRY(sense_launch(worlds, n_worlds, ray_offsets_dev, p->n_rays, const_cast<float *>(p->frac), nullptr, p->n_rows, st));
+    OK_TRY(forward());
+    return control_launch(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, st);
 }
 extern "C" int rem2d_worlds_act(rem2d_world *const *worlds, int32_t n_worlds, const rem2d_policy *p, const double *ray_offsets_dev,
                                 void *stream) {
-    // (arguments first, worlds after, everything before the first launch)
-    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "act: no worlds");
-    int rc = policy_ok("act", p);
-    if (rc != REM2D_OK) return rc;
-    if (p->n_rays > 0 && !ray_offsets_dev) return fail(REM2D_E_INVALID, "act: NULL device pointer (ray offsets)");
-    for (int32_t i = 0; i < n_worlds; ++i)
-        if (!worlds[i]) return fail(REM2D_E_INVALID, "act: world " + std::to_string(i) + " is NULL");
-    rc = control_worlds_ok("act", worlds, n_worlds, p->max_bodies, p->n_rows, p->obs);
-    if (rc != REM2D_OK) return rc;
-    if (p->n_rays > 0)
-        for (int32_t i = 0; i < n_worlds; ++i)
-            if (!worlds[i]->haveTerrain) return fail(REM2D_E_STATE, "act: rem2d_world_set_terrain must be called first");
-    rc = rem2d_worlds_observe(worlds, n_worlds, p->max_bodies, const_cast<float *>(p->obs), p->n_rows, stream);
-    if (rc != REM2D_OK) return rc;
-    if (p->n_rays > 0) {
-        rc = rem2d_worlds_sense(worlds, n_worlds, ray_offsets_dev, p->n_rays, const_cast<float *>(p->frac), nullptr, p->n_rows, stream);
-        if (rc != REM2D_OK) return rc;
-    }
-    rc = policy_launch(p, (hipStream_t)stream);
-    if (rc != REM2D_OK) return rc;
-    return rem2d_worlds_control(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, stream);
+    OK_TRY(worlds_given("act: ", worlds, n_worlds));
+    OK_TRY(policy_ok("act", p));
+    return act("act: ", worlds, n_worlds, p, ray_offsets_dev, (hipStream_t)stream, [&] { return policy_launch(p, (hipStream_t)stream); });
 }
 
 // ---- recurrent device policies (include/rem2d_recurrent.h, csrc/rem2d_recurrent.h) ----
@@ -1678,103 +1722,64 @@ static int recurrent_ok(const char *what, const rem2d_recurrent *q) {
     if (!q->memory) return fail(REM2D_E_INVALID, s + "NULL device pointer (memory)");
     return REM2D_OK;
 }
-// The recurrent forward pass of a checked descriptor on `st`: policy_launch's launch shape; with `nm` the normalised one.
 static int recurrent_launch(const rem2d_recurrent *q, hipStream_t st, const PolNorm *nm = nullptr) {
-    const rem2d_policy *p = &q->p;
-    if (p->n_rows == 0) return REM2D_OK;
     RecurrentArgs Q;
     memset(&Q, 0, sizeof(Q));
-    PolicyArgs &A = Q.P;
-    A.w1 = p->w1; A.b1 = p->b1; A.w2 = p->w2; A.b2 = p->b2;
-    A.index = p->index; A.rowMask = p->row_mask;
-    A.obs = p->obs; A.frac = p->frac; A.targets = p->targets; A.valid = p->valid;
-    A.nRows = p->n_rows;
-    A.D = p->d; A.MB = p->max_bodies; A.R = p->n_rays; A.H = p->hidden; A.G = p->n_sets; A.act = p->activation;
-    A.scale = p->scale;
     Q.memory = q->memory; Q.reset = q->reset; Q.K = q->context;
-    const bool v1 = p->hidden % 4 == 0 && (uintptr_t)p->w1 % 16 == 0;
-    const bool v2 = p->max_bodies % 4 == 0 && (uintptr_t)p->w2 % 16 == 0;
-    const unsigned need = std::max((unsigned)(p->hidden + (v1 ? 3 : 0)) / (v1 ? 4u : 1u), (unsigned)(p->max_bodies + (v2 ? 3 : 0)) / (v2 ? 4u : 1u));
-    const unsigned lpr = std::min((unsigned)WAVE, std::max((unsigned)POL_MIN_LPR, pow2_at_least(need)));
-    A.lpr = (int)lpr;
-    const unsigned rpw = WAVE / lpr;
-    const long long blocks = (p->n_rows + rpw - 1) / rpw;
-    if (blocks > 0x7fffffffLL) return fail(REM2D_E_INVALID, "recurrent: too many rows for one launch");
-    const size_t lds = (size_t)rpw * (size_t)(p->d + p->hidden) * sizeof(float);
-    if (nm) {
-        void (*normed)(RecurrentArgs, PolNorm) = v1 ? (v2 ? rem2d_recurrent_forward_kernel<4, 4, true> : rem2d_recurrent_forward_kernel<4, 1, true>)
-                                                 : (v2 ? rem2d_recurrent_forward_kernel<1, 4, true> : rem2d_recurrent_forward_kernel<1, 1, true>);
-        hipLaunchKernelGGL(normed, dim3((unsigned)blocks), dim3(WAVE), lds, st, Q, *nm);
-        HIP_TRY(hipGetLastError());
-        return REM2D_OK;
-    }
-    void (*kernel)(RecurrentArgs, PolNoNorm) = v1 ? (v2 ? rem2d_recurrent_forward_kernel<4, 4> : rem2d_recurrent_forward_kernel<4, 1>)
-                                       : (v2 ? rem2d_recurrent_forward_kernel<1, 4> : rem2d_recurrent_forward_kernel<1, 1>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), lds, st, Q, PolNoNorm());
-    HIP_TRY(hipGetLastError());
-    return REM2D_OK;
+    return forward_launch<RecurrentKernels>("recurrent", &q->p, Q, Q.P, nm, st);
 }
 extern "C" int rem2d_recurrent_forward(const rem2d_recurrent *q, void *stream) {
-    const int rc = recurrent_ok("recurrent", q);
-    if (rc != REM2D_OK) return rc;
+    OK_TRY(recurrent_ok("recurrent", q));
     return recurrent_launch(q, (hipStream_t)stream);
 }
 extern "C" int rem2d_worlds_act_recurrent(rem2d_world *const *worlds, int32_t n_worlds, const rem2d_recurrent *q,
                                           const double *ray_offsets_dev, void *stream) {
-    // (rem2d_worlds_act's order: arguments first, worlds after, everything before the first launch)
-    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "act_recurrent: no worlds");
-    int rc = recurrent_ok("act_recurrent", q);
-    if (rc != REM2D_OK) return rc;
-    const rem2d_policy *p = &q->p;
-    if (p->n_rays > 0 && !ray_offsets_dev) return fail(REM2D_E_INVALID, "act_recurrent: NULL device pointer (ray offsets)");
-    for (int32_t i = 0; i < n_worlds; ++i)
-        if (!worlds[i]) return fail(REM2D_E_INVALID, "act_recurrent: world " + std::to_string(i) + " is NULL");
-    rc = control_worlds_ok("act_recurrent", worlds, n_worlds, p->max_bodies, p->n_rows, p->obs);
-    if (rc != REM2D_OK) return rc;
-    if (p->n_rays > 0)
-        for (int32_t i = 0; i < n_worlds; ++i)
-            if (!worlds[i]->haveTerrain) return fail(REM2D_E_STATE, "act_recurrent: rem2d_world_set_terrain must be called first");
-    rc = rem2d_worlds_observe(worlds, n_worlds, p->max_bodies, const_cast<float *>(p->obs), p->n_rows, stream);
-    if (rc != REM2D_OK) return rc;
-    if (p->n_rays > 0) {
-        rc = rem2d_worlds_sense(worlds, n_worlds, ray_offsets_dev, p->n_rays, const_cast<float *>(p->frac), nullptr, p->n_rows, stream);
-        if (rc != REM2D_OK) return rc;
-    }
-    rc = recurrent_launch(q, (hipStream_t)stream);
-    if (rc != REM2D_OK) return rc;
-    return rem2d_worlds_control(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, stream);
+    OK_TRY(worlds_given("act_recurrent: ", worlds, n_worlds));
+    OK_TRY(recurrent_ok("act_recurrent", q));
+    return act("act_recurrent: ", worlds, n_worlds, &q->p, ray_offsets_dev, (hipStream_t)stream,
+               [&] { return recurrent_launch(q, (hipStream_t)stream); });
 }
 
 // ---- episode boundaries (include/rem2d_episode.h, csrc/rem2d_episode.h) ----
 extern "C" int rem2d_episode_abi_version(void) { return REM2D_EPISODE_ABI_VERSION; }
 static_assert(sizeof(CtlTable) + sizeof(EpTable) + sizeof(EpArgs) + 16 <= 4096, "rem2d_reset_where_kernel: kernel arguments within the 4 KB kernarg limit");
+static bool morph_complete(const rem2d_morph *m) {
+    return m->shape && m->hx && m->hy && m->x && m->y && m->angle && m->parent && m->jround && m->ax && m->ay && m->bx && m->by &&
+           m->torque && m->lower && m->upper && m->amp && m->phase && m->freq && m->offset && m->istate;
+}
+// What reset_where and refill refuse of their morphologies and of `when`, each in the call's own place.
+static int morphs_complete(const std::string &p, const rem2d_morph *morphs, int32_t n_worlds) {
+    for (int32_t i = 0; i < n_worlds; ++i)
+        if (!morph_complete(morphs + i)) return fail(REM2D_E_INVALID, p + "morphology " + std::to_string(i) + " has NULL arrays");
+    return REM2D_OK;
+}
+static int when_bits_ok(const std::string &p, uint32_t when) {
+    if (when & ~(uint32_t)(REM2D_WHEN_DONE | REM2D_WHEN_FROZEN | REM2D_WHEN_STEPS))
+        return fail(REM2D_E_INVALID, p + "unknown bits in `when` (" + std::to_string(when) + ")");
+    return REM2D_OK;
+}
+static int when_steps_ok(const std::string &p, uint32_t when, int32_t max_steps) {
+    if ((when & REM2D_WHEN_STEPS) && max_steps <= 0)
+        return fail(REM2D_E_INVALID, p + "REM2D_WHEN_STEPS needs max_steps > 0, not " + std::to_string(max_steps));
+    return REM2D_OK;
+}
 extern "C" int rem2d_worlds_reset_where(rem2d_world *const *worlds, const rem2d_morph *morphs, int32_t n_worlds, const uint8_t *mask_dev,
                                         uint32_t when, int32_t max_steps, const rem2d_episode_out *out, int64_t n_rows, void *stream) {
     // (arguments first, worlds after, everything before the first launch)
-    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "reset_where: no worlds");
-    if (!morphs) return fail(REM2D_E_INVALID, "reset_where: NULL morphologies");
-    if (when & ~(uint32_t)(REM2D_WHEN_DONE | REM2D_WHEN_FROZEN | REM2D_WHEN_STEPS))
-        return fail(REM2D_E_INVALID, "reset_where: unknown bits in `when` (" + std::to_string(when) + ")");
-    if ((when & REM2D_WHEN_STEPS) && max_steps <= 0)
-        return fail(REM2D_E_INVALID, "reset_where: REM2D_WHEN_STEPS needs max_steps > 0, not " + std::to_string(max_steps));
+    const std::string p = "reset_where: ";
+    OK_TRY(worlds_given(p, worlds, n_worlds));
+    if (!morphs) return fail(REM2D_E_INVALID, p + "NULL morphologies");
+    OK_TRY(when_bits_ok(p, when));
+    OK_TRY(when_steps_ok(p, when, max_steps));
     if (!mask_dev && when == 0)
-        return fail(REM2D_E_INVALID, "reset_where: no mask and no condition would reset every creature (that is rem2d_world_reset)");
-    if (n_rows < 0) return fail(REM2D_E_INVALID, "reset_where: negative row count");
-    for (int32_t i = 0; i < n_worlds; ++i)
-        if (!worlds[i]) return fail(REM2D_E_INVALID, "reset_where: world " + std::to_string(i) + " is NULL");
+        return fail(REM2D_E_INVALID, p + "no mask and no condition would reset every creature (that is rem2d_world_reset)");
+    OK_TRY(rows_ok(p, n_rows));
+    OK_TRY(worlds_present(p, worlds, n_worlds));
+    OK_TRY(morphs_complete(p, morphs, n_worlds));
     for (int32_t i = 0; i < n_worlds; ++i) {
-        const rem2d_morph *m = morphs + i;
-        if (!m->shape || !m->hx || !m->hy || !m->x || !m->y || !m->angle || !m->parent || !m->jround || !m->ax || !m->ay ||
-            !m->bx || !m->by || !m->torque || !m->lower || !m->upper || !m->amp || !m->phase || !m->freq || !m->offset ||
-            !m->istate)
-            return fail(REM2D_E_INVALID, "reset_where: morphology " + std::to_string(i) + " has NULL arrays");
+        OK_TRY(world_fits(p, worlds[i], worlds[0]));
+        OK_TRY(world_reset(p, worlds[i]));
     }
-    for (int32_t i = 0; i < n_worlds; ++i) {
-        if (worlds[i]->cfg.lanes > 64) return fail(REM2D_E_INVALID, "reset_where: more than 64 lanes per creature");
-        if (worlds[i]->cfg.device != worlds[0]->cfg.device) return fail(REM2D_E_INVALID, "reset_where: the worlds must share a device");
-        if (!worlds[i]->haveReset) return fail(REM2D_E_STATE, "reset_where: rem2d_world_reset (or adopt) must be called first");
-    }
-    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
     EpArgs A;
     memset(&A, 0, sizeof(A));
     A.mask = mask_dev;
@@ -1782,73 +1787,58 @@ extern "C" int rem2d_worlds_reset_where(rem2d_world *const *worlds, const rem2d_
     A.nRows = n_rows;
     A.when = when;
     A.maxSteps = max_steps;
-    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
-        CtlTable Tb;
+    return table_launches(CTL_TABLE, worlds, n_worlds, [&](int first, int n, const CtlTable &Tb, dim3 grid) {
         EpTable Te;
-        const int n = std::min(CTL_TABLE, (int)n_worlds - first);
-        const unsigned blocks = control_table(Tb, worlds, first, n);
         memset(&Te, 0, sizeof(Te));
         for (int i = 0; i < n; ++i) {
             Te.w[i].M = morphs[first + i];
             Te.w[i].env4 = worlds[first + i]->S.env4;
         }
-        const unsigned per = CTL_THREADS / WAVE;
-        hipLaunchKernelGGL(rem2d_reset_where_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Te, A);
-        HIP_TRY(hipGetLastError());
-    }
-    return REM2D_OK;
+        hipLaunchKernelGGL(rem2d_reset_where_kernel, grid, dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Te, A);
+    });
 }
 
 // ---- streaming evaluation (include/rem2d_stream.h, csrc/rem2d_stream.h) ----
 extern "C" int rem2d_stream_abi_version(void) { return REM2D_STREAM_ABI_VERSION; }
 static_assert(sizeof(CtlTable) + sizeof(StTable) + sizeof(StArgs) + 16 <= 4096, "rem2d_refill_kernel: kernel arguments within the 4 KB kernarg limit");
-static bool morph_complete(const rem2d_morph *m) {
-    return m->shape && m->hx && m->hy && m->x && m->y && m->angle && m->parent && m->jround && m->ax && m->ay && m->bx && m->by &&
-           m->torque && m->lower && m->upper && m->amp && m->phase && m->freq && m->offset && m->istate;
-}
 extern "C" int rem2d_worlds_refill(rem2d_world *const *worlds, const rem2d_morph *morphs, int32_t n_worlds, const rem2d_feed *feeds,
                                    int32_t *occupant_dev, uint32_t when, int32_t max_steps, const rem2d_stream_out *out, int64_t n_ids,
                                    int64_t n_rows, void *stream) {
     // (arguments first, worlds after, everything before the first launch)
-    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "refill: no worlds");
-    if (!morphs) return fail(REM2D_E_INVALID, "refill: NULL morphologies");
-    if (!feeds) return fail(REM2D_E_INVALID, "refill: NULL feeds");
-    if (!occupant_dev) return fail(REM2D_E_INVALID, "refill: NULL occupant array");
-    if (when & ~(uint32_t)(REM2D_WHEN_DONE | REM2D_WHEN_FROZEN | REM2D_WHEN_STEPS))
-        return fail(REM2D_E_INVALID, "refill: unknown bits in `when` (" + std::to_string(when) + ")");
-    if (when == 0) return fail(REM2D_E_INVALID, "refill: no condition (`when` == 0): nobody's episode could end");
-    if ((when & REM2D_WHEN_STEPS) && max_steps <= 0)
-        return fail(REM2D_E_INVALID, "refill: REM2D_WHEN_STEPS needs max_steps > 0, not " + std::to_string(max_steps));
-    if (n_rows < 0) return fail(REM2D_E_INVALID, "refill: negative row count");
-    if (n_ids < 0) return fail(REM2D_E_INVALID, "refill: negative id count");
-    for (int32_t i = 0; i < n_worlds; ++i)
-        if (!worlds[i]) return fail(REM2D_E_INVALID, "refill: world " + std::to_string(i) + " is NULL");
-    for (int32_t i = 0; i < n_worlds; ++i)
-        if (!morph_complete(morphs + i)) return fail(REM2D_E_INVALID, "refill: morphology " + std::to_string(i) + " has NULL arrays");
+    const std::string p = "refill: ";
+    OK_TRY(worlds_given(p, worlds, n_worlds));
+    if (!morphs) return fail(REM2D_E_INVALID, p + "NULL morphologies");
+    if (!feeds) return fail(REM2D_E_INVALID, p + "NULL feeds");
+    if (!occupant_dev) return fail(REM2D_E_INVALID, p + "NULL occupant array");
+    OK_TRY(when_bits_ok(p, when));
+    if (when == 0) return fail(REM2D_E_INVALID, p + "no condition (`when` == 0): nobody's episode could end");
+    OK_TRY(when_steps_ok(p, when, max_steps));
+    OK_TRY(rows_ok(p, n_rows));
+    if (n_ids < 0) return fail(REM2D_E_INVALID, p + "negative id count");
+    OK_TRY(worlds_present(p, worlds, n_worlds));
+    OK_TRY(morphs_complete(p, morphs, n_worlds));
     for (int32_t i = 0; i < n_worlds; ++i) {
         const rem2d_feed *f = feeds + i;
-        if (f->count < 0) return fail(REM2D_E_INVALID, "refill: feed " + std::to_string(i) + " has a negative count");
-        if (!f->cursor) return fail(REM2D_E_INVALID, "refill: feed " + std::to_string(i) + " has no cursor");
+        if (f->count < 0) return fail(REM2D_E_INVALID, p + "feed " + std::to_string(i) + " has a negative count");
+        if (!f->cursor) return fail(REM2D_E_INVALID, p + "feed " + std::to_string(i) + " has no cursor");
         if (f->count > 0 && (!morph_complete(&f->M) || !f->id))
-            return fail(REM2D_E_INVALID, "refill: feed " + std::to_string(i) + " has pending creatures and NULL arrays");
+            return fail(REM2D_E_INVALID, p + "feed " + std::to_string(i) + " has pending creatures and NULL arrays");
     }
     for (int32_t i = 0; i < n_worlds; ++i) {
         const rem2d_world *w = worlds[i];
-        if (w->cfg.lanes > 64) return fail(REM2D_E_INVALID, "refill: more than 64 lanes per creature");
-        if (w->cfg.device != worlds[0]->cfg.device) return fail(REM2D_E_INVALID, "refill: the worlds must share a device");
+        OK_TRY(world_fits(p, w, worlds[0]));
         if (feeds[i].lanes != w->cfg.lanes)
-            return fail(REM2D_E_INVALID, "refill: feed " + std::to_string(i) + " holds creatures of " + std::to_string(feeds[i].lanes) +
+            return fail(REM2D_E_INVALID, p + "feed " + std::to_string(i) + " holds creatures of " + std::to_string(feeds[i].lanes) +
                                              " lanes, its world creatures of " + std::to_string(w->cfg.lanes));
     }
-    for (int32_t i = 0; i < n_worlds; ++i) {
+    for (int32_t i = 0; i < n_worlds; ++i) { // (the tile shape and the reset after every world's lanes: a loop of their own)
         const rem2d_world *w = worlds[i];
         if (!tile_shape(w->tileShape).flex)
-            return fail(REM2D_E_STATE, "refill: world " + std::to_string(i) + " is on the static tile shape " + std::to_string(w->tileShape) +
+            return fail(REM2D_E_STATE, p + "world " + std::to_string(i) + " is on the static tile shape " + std::to_string(w->tileShape) +
                                            ": the tile table of shapes 0 and 4 is planned from the joints of the creatures in it, "
                                            "so its slots cannot take other creatures (use a flexible shape: 1, 2 or 3)");
-        if (!w->haveReset) return fail(REM2D_E_STATE, "refill: rem2d_world_reset (or adopt) must be called first");
+        OK_TRY(world_reset(p, w));
     }
-    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
     StArgs A;
     memset(&A, 0, sizeof(A));
     A.occupant = occupant_dev;
@@ -1857,11 +1847,8 @@ extern "C" int rem2d_worlds_refill(rem2d_world *const *worlds, const rem2d_morph
     A.nRows = n_rows;
     A.when = when;
     A.maxSteps = max_steps;
-    for (int first = 0; first < n_worlds; first += STREAM_TABLE) {
-        CtlTable Tb;
+    return table_launches(STREAM_TABLE, worlds, n_worlds, [&](int first, int n, const CtlTable &Tb, dim3 grid) {
         StTable Ts;
-        const int n = std::min(STREAM_TABLE, (int)n_worlds - first);
-        const unsigned blocks = control_table(Tb, worlds, first, n);
         memset(&Ts, 0, sizeof(Ts));
         for (int i = 0; i < n; ++i) {
             const rem2d_feed &f = feeds[first + i];
@@ -1872,16 +1859,11 @@ extern "C" int rem2d_worlds_refill(rem2d_world *const *worlds, const rem2d_morph
             Ts.w[i].cursor = f.cursor;
             Ts.w[i].count = f.count;
         }
-        const unsigned per = CTL_THREADS / WAVE;
-        hipLaunchKernelGGL(rem2d_refill_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Ts, A);
-        HIP_TRY(hipGetLastError());
-    }
-    return REM2D_OK;
+        hipLaunchKernelGGL(rem2d_refill_kernel, grid, dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Ts, A);
+    });
 }
 
 // ---- what the search tiers below share on the host: net shapes, buffer spans, scratch, launches ----
-#define OK_TRY(expr) \
-    do { const int rc_ = (expr); if (rc_ != REM2D_OK) return rc_; } while (0)
 // The w1 / b1 / w2 / b2 members of a descriptor whose names begin with `pre` (which may be empty): the initialiser of an array of four.
 #define QUAD(e, pre) {(e)->pre##w1, (e)->pre##b1, (e)->pre##w2, (e)->pre##b2}
 static const char *const kNet[4] = {"w1", "b1", "w2", "b2"};
@@ -2276,22 +2258,18 @@ extern "C" int rem2d_worlds_describe(rem2d_world *const *worlds, int32_t n_world
     if (period < 1) return fail(REM2D_E_INVALID, "describe: period must be at least 1, not " + std::to_string(period));
     if (n_samples < 1 || n_samples > REM2D_NOVELTY_MAX_SAMPLES)
         return fail(REM2D_E_INVALID, "describe: n_samples must be 1.." + std::to_string(REM2D_NOVELTY_MAX_SAMPLES) + ", not " + std::to_string(n_samples));
-    const int rc = control_worlds_ok("describe", worlds, n_worlds, 1, out_rows, out_dev);
-    if (rc != REM2D_OK) return rc;
-    HIP_TRY(hipSetDevice(worlds[0]->cfg.device));
-    for (int first = 0; first < n_worlds; first += CTL_TABLE) {
-        CtlTable Tb;
+    const std::string p = "describe: "; // (observe's refusals without a max_bodies)
+    OK_TRY(worlds_given(p, worlds, n_worlds));
+    OK_TRY(buffer_given(p, out_dev));
+    OK_TRY(rows_ok(p, out_rows));
+    OK_TRY(worlds_ready(p, worlds, n_worlds));
+    return table_launches(CTL_TABLE, worlds, n_worlds, [&](int first, int n, const CtlTable &Tb, dim3 grid) {
         NvTable Te;
-        const int n = std::min(CTL_TABLE, (int)n_worlds - first);
-        const unsigned blocks = control_table(Tb, worlds, first, n);
         memset(&Te, 0, sizeof(Te));
         for (int i = 0; i < n; ++i) Te.env4[i] = worlds[first + i]->S.env4;
-        const unsigned per = CTL_THREADS / WAVE;
-        hipLaunchKernelGGL(rem2d_describe_kernel, dim3((blocks + per - 1) / per), dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Te,
-                           (int)period, (int)n_samples, out_dev, (long long)out_rows);
-        HIP_TRY(hipGetLastError());
-    }
-    return REM2D_OK;
+        hipLaunchKernelGGL(rem2d_describe_kernel, grid, dim3(CTL_THREADS), 0, (hipStream_t)stream, Tb, Te, (int)period, (int)n_samples, out_dev,
+                           (long long)out_rows);
+    });
 }
 enum { NV_SCORE = 1, NV_ADD = 2 };
 // Checks a novelty descriptor for the calls in `stages`.  Nothing it points to is read.
@@ -2861,28 +2839,19 @@ extern "C" int rem2d_obsnorm_forward_memory(const rem2d_obsnorm *n, const rem2d_
 }
 extern "C" int rem2d_worlds_act_normed(rem2d_world *const *worlds, int32_t n_worlds, const rem2d_obsnorm *n, const rem2d_policy *p,
                                        const double *ray_offsets_dev, int32_t accumulate) {
-    // (rem2d_worlds_act's order: arguments first, worlds after, everything before the first launch)
-    if (!worlds || n_worlds <= 0) return fail(REM2D_E_INVALID, "act_normed: no worlds");
+    OK_TRY(worlds_given("act_normed: ", worlds, n_worlds));
     rem2d_recurrent q;
     const bool memory = n && n->context > 0;
     OK_TRY(on_policy_ok("act_normed", n, p, memory, &q));
     rem2d_obsnorm acc = *n; // the accumulation reads what this call's observe and sense write
     acc.obs = p->obs; acc.frac = p->frac; acc.row_mask = p->row_mask; acc.n_rows = p->n_rows;
     if (accumulate) OK_TRY(on_ok("act_normed", &acc, ON_ACC));
-    if (p->n_rays > 0 && !ray_offsets_dev) return fail(REM2D_E_INVALID, "act_normed: NULL device pointer (ray offsets)");
-    for (int32_t i = 0; i < n_worlds; ++i)
-        if (!worlds[i]) return fail(REM2D_E_INVALID, "act_normed: world " + std::to_string(i) + " is NULL");
-    OK_TRY(control_worlds_ok("act_normed", worlds, n_worlds, p->max_bodies, p->n_rows, p->obs));
-    if (p->n_rays > 0)
-        for (int32_t i = 0; i < n_worlds; ++i)
-            if (!worlds[i]->haveTerrain) return fail(REM2D_E_STATE, "act_normed: rem2d_world_set_terrain must be called first");
-    void *stream = n->stream;
-    OK_TRY(rem2d_worlds_observe(worlds, n_worlds, p->max_bodies, const_cast<float *>(p->obs), p->n_rows, stream));
-    if (p->n_rays > 0) OK_TRY(rem2d_worlds_sense(worlds, n_worlds, ray_offsets_dev, p->n_rays, const_cast<float *>(p->frac), nullptr, p->n_rows, stream));
-    if (accumulate) OK_TRY(on_launch(&acc, ON_ACC, (hipStream_t)stream));
-    const PolNorm nm = on_tables(n);
-    OK_TRY(memory ? recurrent_launch(&q, (hipStream_t)stream, &nm) : policy_launch(p, (hipStream_t)stream, &nm));
-    return rem2d_worlds_control(worlds, n_worlds, REM2D_CTRL_TARGET, p->targets, p->max_bodies, p->n_rows, p->valid, stream);
+    const hipStream_t st = (hipStream_t)n->stream;
+    return act("act_normed: ", worlds, n_worlds, p, ray_offsets_dev, st, [&] {
+        if (accumulate) OK_TRY(on_launch(&acc, ON_ACC, st));
+        const PolNorm nm = on_tables(n);
+        return memory ? recurrent_launch(&q, st, &nm) : policy_launch(p, st, &nm);
+    });
 }
 
 extern "C" int rem2d_world_enable_timing(rem2d_world *w, int32_t on) {

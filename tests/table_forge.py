@@ -2,8 +2,8 @@
 (tests/test_world_tables_gpu.py) share.
 
 Every between-steps call that takes a list of worlds packs them into a kernel-argument table -- CTL_TABLE = 16 worlds, STREAM_TABLE = 8
-for rem2d_worlds_refill -- and launches once per table (csrc/rem2d.hip: `for (first = 0; first < n_worlds; first += TABLE)`), filling
-the shared CtlTable through control_table(.., first, n) and, for most calls, a second per-world table beside it (SenseTable: the
+for rem2d_worlds_refill -- and launches once per table (csrc/rem2d.hip, table_launches: `for (first = 0; first < n_worlds; first +=
+table)`), filling the shared CtlTable through control_table(.., first, n) and, for most calls, a second per-world table beside it (SenseTable: the
 terrain; NvTable: env4; EpTable / StTable: morphology, env4, feed).  ONE forged list of N_WORLDS = 33 small worlds under one population
 index serves all calls: a call with n worlds takes the first n.
 

@@ -17,8 +17,15 @@ Matrix (default build unless stated):
   describe       16 / 17 / 32 / 33 worlds, three calls at forged step words, a third of the creatures frozen
   refill         8 / 9 / 16 / 17 worlds, test_stream_gpu's forged-occupant protocol; worlds 7 + 8 and 15 + 16 share a feed and cursor
                  that runs short in the second of the two launches
-  refusals       8 calls x {NULL world at 16, never-reset world at 17}, refill also a feed of other lanes at 9: the documented text,
+  act_normed     17 / 33 worlds x {feed-forward, with memory under such a reset mask}, accumulate = 1, a normaliser of 64-row blocks
+                 (they straddle worlds and chunks) frozen after one accumulation: the same buffers and the sums, against
+                 obsnorm_model on top of the models above
+  act launches   one act / act_recurrent / act_normed over 17 worlds captured into a graph: 7, 7 and 8 kernel nodes
+  refusals       9 calls x {NULL world at 16, never-reset world at 17}, refill also a feed of other lanes at 9: the documented text,
                  and no byte of any arena or buffer moved (reset_where included: it shares the contract)
+  chains         9 calls x two orders of a list of good / never reset / NULL / no terrain (refill: / feed of other lanes / static
+                 tile shape) worlds, walked down fault by fault against tests/golden/world_call_refusals.json: code and text of
+                 every link, nothing moved (the host half of the record: tests/test_world_calls_host.py)
   split transparency, inside each id: the n-world call and n one-world calls from the same state leave identical bytes.  For refill
                  the comparison is of what the header specifies (cursors, the ids handed out, how many slots a world refilled and
                  retired): WHICH pending creature lands in which slot of one launch is unspecified (csrc/rem2d_stream.h)
@@ -27,9 +34,9 @@ Matrix (default build unless stated):
                  with step_groups = 4 (11 worlds: reset_stream cuts a bucket into a world per step group, and the worlds of a bucket
                  share its feed) through evaluate.run_stream against stream_model.run
 
-45 ids.  Measured on one MI355X: the whole module in 8 s of wall time -- 1.6 s of it the set-up of the 33 worlds (reset and 40 steps
-each), 1.4 s the streamed env, 0.8 s the slowest forge id (observe, 16 worlds, which also makes the cached models), every other id
-below 0.6 s.  What the two scratch mutants of the host loop fail is recorded in DESIGN.md section 14, "The world tables across their
+60 ids.  Measured on one MI355X: the whole module in 9 s of wall time -- 1.6 s of it the set-up of the 33 worlds (reset and 40 steps
+each), 1.4 s the streamed env, 0.8 s the slowest forge id (observe, 16 worlds, which also makes the cached models), 0.6 s the first
+act_normed id, every other id below 0.6 s; the nine chain ids together take a fraction of a second.  What the two scratch mutants of the host loop fail is recorded in DESIGN.md section 14, "The world tables across their
 launch split".
 """
 import ctypes as C
@@ -380,6 +387,192 @@ def test_act(gpu, sets, n, recurrent):
             same_arenas(many[1], after, what + ": under a row mask")
 
 
+# ----------------------------------------------------------------------------------------------------------------- act_normed
+NORM_GROUP = 64
+
+
+def normed_call(worlds, nd, p, rays, accumulate):
+    """rem2d_worlds_act_normed(worlds, n, &nd, &p, rays, accumulate) on the current stream, which travels in nd -> (code, text)"""
+    w0 = next(w for w in worlds if w is not None)
+    nd.stream = w0._stream()
+    rc = w0.L.rem2d_worlds_act_normed(TB.world_array(worlds), len(worlds), C.byref(nd), C.byref(p), ptr(rays), accumulate)
+    return rc, (w0.L.rem2d_last_error().decode() if rc else "")
+
+
+def run_act_normed(torch, s, n, pol, norm, sums0, rays, memory, mem0, reset, single, owned=False):
+    """test_act's run_act for rem2d_worlds_act_normed with accumulate = 1, from the sums `sums0`
+    -> ({name: host rows}, [count, s1, s2hi, s2lo], [arena])"""
+    import test_obsnorm_gpu as TO
+    b = act_buffers(torch, s.n_rows, memory)
+    for name, a in zip(("count", "s1", "s2hi", "s2lo"), sums0):
+        getattr(norm, name).copy_(dev(torch, a))
+    keep = [dev(torch, reset)] if memory else []
+    if memory:
+        b["memory"].inner.copy_(dev(torch, mem0))
+
+    def one(worlds):
+        mask = None
+        if owned:
+            own = np.zeros(s.n_rows, np.uint8)
+            for i in worlds:
+                r = s.rows[i]
+                own[r[(r >= 0) & (r < s.n_rows)]] = 1
+            mask = dev(torch, own)
+            keep.append(mask)
+        bufs = (b["obs"].inner, b["frac"].inner, b["targets"].inner, b["valid"].inner)
+        nd = norm.descriptor()
+        if memory:
+            q = pol.descriptor(*bufs, b["memory"].inner, keep[0], mask)
+            nd.context, nd.memory, nd.reset, p = q.context, q.memory, q.reset, q.p
+        else:
+            p = pol.descriptor(*bufs, mask)
+        rc, text = normed_call([s.worlds[i] for i in worlds], nd, p, rays, 1)
+        assert rc == 0, "act_normed: %d %s" % (rc, text)
+    if single:
+        for i in range(n):
+            one([i])
+    else:
+        one(range(n))
+    return {k: v.host() for k, v in b.items()}, TO.get_state(norm), s.arenas()
+
+
+@pytest.mark.parametrize("memory", [False, True], ids=["feed_forward", "memory"])
+@pytest.mark.parametrize("n", (TB.CTL_TABLE + 1, 2 * TB.CTL_TABLE + 1))
+def test_act_normed(gpu, sets, n, memory):
+    """test_act for rem2d_worlds_act_normed, accumulate = 1, feed-forward and with memory under a reset mask that selects creatures of
+    both chunks.  The normaliser's blocks are 64 rows, so they straddle worlds and chunks, and its tables were frozen after one
+    accumulation of forged rows, so every block has its own.  obs, frac, targets, valid, (memory,) the sums and the arenas against
+    observe_model -> cast -> obsnorm_model.accumulate / forward(_memory) -> the control write; then, both under a row mask of the
+    rows their worlds own, one call against one world at a time (the sums are exact, so n masked calls add up to the one)."""
+    torch = gpu
+    import obsnorm_model as OM
+    import test_obsnorm_gpu as TO
+    from gym_rem2d_amd import policy
+    s = sets()
+    rays = dev(torch, R.bipedal_rays())
+    cast = model_cast(s, R.bipedal_rays(), "10")
+    for short in (False, True):
+        s.restore()
+        n_rows = s.use_index(short)
+        before = s.arenas()
+        rng = np.random.default_rng(160 + n)
+        mem0 = reset = None
+        if memory:
+            pol = policy.RecurrentPolicy.random(n_rows, ACT_BODIES, ACT_HIDDEN, ACT_CONTEXT, seed=171 + n).to("cuda")
+            mem0 = rng.uniform(-0.9, 0.9, (n_rows, ACT_CONTEXT)).astype(f32)
+            reset = (rng.random(n_rows) < 0.3).astype(np.uint8)
+            for i in (1, 4, n - 1):
+                r = s.rows[i]
+                reset[r[(r >= 0) & (r < n_rows)][:2]] = 1
+            picked = [int(reset[r[(r >= 0) & (r < n_rows)]].sum()) for r in s.rows[:n]]
+            assert sum(picked[:TB.CTL_TABLE]) >= 4 and sum(picked[TB.CTL_TABLE:]) >= 2
+        else:
+            pol = policy.MLPPolicy.random(n_rows, ACT_BODIES, ACT_HIDDEN, seed=171 + n).to("cuda")
+        W = tuple(t.cpu().numpy() for t in pol.weights)
+        norm = policy.ObsNormalizer(-(-n_rows // NORM_GROUP), NORM_GROUP, ACT_BODIES, 10, min_count=2, device="cuda")
+        prior = (rng.standard_normal((n_rows, norm.width)) * np.linspace(0.2, 3.0, norm.n_blocks).repeat(NORM_GROUP)[:n_rows, None]).astype(f32)
+        norm.accumulate(*TO.split(torch, prior, ACT_BODIES))
+        norm.freeze()
+        sums0 = TO.get_state(norm)
+        mu, inv = (t.cpu().numpy().copy() for t in norm.tables)
+        assert len({mu[b].tobytes() for b in range(norm.n_blocks)}) == norm.n_blocks > 4 and (inv != 1).all()
+        got, sums, after = run_act_normed(torch, s, n, pol, norm, sums0, rays, memory, mem0, reset, False)
+        obs = scatter(s, n, model_obs(s, ACT_BODIES), (CM.width(ACT_BODIES),), FILL["obs"], f32)
+        frac = scatter(s, n, [m[0] for m in cast], (10,), FILL["frac"], f32)
+        x = PM.input_rows(obs, frac)
+        if memory:
+            tg, valid, mem = OM.forward_memory(x, mem0, mu, inv, norm.clip, NORM_GROUP, *W, reset=reset)
+        else:
+            tg, valid = OM.forward(x, mu, inv, norm.clip, NORM_GROUP, *W)
+        what = "act_normed%s, %d worlds%s" % (" with memory" if memory else "", n, ", short index" if short else "")
+        same_rows(got["obs"], obs, s, n, what + ": obs")
+        same_rows(got["frac"], frac, s, n, what + ": frac")
+        same_rows(PM.bits(got["targets"]), PM.bits(tg), s, n, what + ": targets")
+        same_rows(got["valid"], valid, s, n, what + ": valid")
+        if memory:
+            same_rows(RM.mem_bits(got["memory"]), RM.mem_bits(mem), s, n, what + ": memory")
+        st = OM.State(norm.n_blocks, norm.width)
+        st.count, st.s1, st.s2hi, st.s2lo = (a.copy() for a in sums0)
+        OM.accumulate(st, x, NORM_GROUP)
+        for name, g, w in zip(("count", "s1", "s2hi", "s2lo"), sums, st.words()):
+            assert np.array_equal(g, w.reshape(g.shape)), "%s: `%s`" % (what, name)
+        assert (sums[0] > sums0[0]).all()
+        assert np.array_equal(OM.tbits(norm.mu.cpu().numpy()), OM.tbits(mu)) and np.array_equal(OM.tbits(norm.inv.cpu().numpy()), OM.tbits(inv))
+        want, wrote = control_arenas(s, n, before, TB.CTRL_TARGET, tg, valid, ACT_BODIES)
+        same_arenas(after, want, what + ": the arenas")
+        assert wrote > 150 and valid.all()
+        plain = (RM.forward_model(x, mem0, *W, reset=reset) if memory else PM.forward_model(x, *W))[0]
+        assert (PM.bits(plain) != PM.bits(tg)).any(axis=1).mean() > 0.9                                  # the tables mattered
+        # one world at a time, both sides under a row mask of the rows their worlds own
+        s.restore()
+        many = run_act_normed(torch, s, n, pol, norm, sums0, rays, memory, mem0, reset, False, owned=True)
+        s.restore()
+        ones = run_act_normed(torch, s, n, pol, norm, sums0, rays, memory, mem0, reset, True, owned=True)
+        assert all(ones[0][k].tobytes() == many[0][k].tobytes() for k in got), what + ": one world at a time"
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(ones[1], many[1])), what + ": the sums, one world at a time"
+        same_arenas(ones[2], many[2], what + ": one world at a time")
+        own = scatter(s, n, [np.ones(len(r), np.uint8) for r in s.rows], (), 0, np.uint8) != 0
+        assert all(many[0][k][own].tobytes() == got[k][own].tobytes() for k in got) and own.sum() > 200
+        assert int((many[1][0] - sums0[0]).sum()) == int(own.sum())
+        same_arenas(many[2], after, what + ": under a row mask")
+
+
+# ------------------------------------------------------------------------------------------- the launches of one act call
+def captured_nodes(torch, queue):
+    """queue(stream) captured on a side stream through the process's own HIP runtime -> the node count of the graph; nothing runs"""
+    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
+    hip = C.CDLL(path)
+    side = torch.cuda.Stream()
+    st, graph, count = C.c_void_p(side.cuda_stream), C.c_void_p(), C.c_size_t()
+    torch.cuda.synchronize()
+    assert hip.hipStreamBeginCapture(st, 2) == 0                # hipStreamCaptureModeRelaxed: the mode is of no concern here
+    try:
+        with torch.cuda.stream(side):
+            queue()
+    finally:
+        assert hip.hipStreamEndCapture(st, C.byref(graph)) == 0
+    try:
+        assert hip.hipGraphGetNodes(graph, None, C.byref(count)) == 0
+    finally:
+        hip.hipGraphDestroy(graph)
+    return count.value
+
+
+def test_act_launches(gpu, sets):
+    """one act call over 17 worlds, captured: observe and sense, the forward pass and control are 2 + 2 + 1 + 2 kernel nodes -- a
+    launch per table of 16 worlds and call, one forward pass -- and the normalised call's accumulation is one more.  These are the
+    counts of the library as it was when every act call went through the public observe / sense / control; no buffer is written."""
+    torch = gpu
+    from gym_rem2d_amd import policy
+    s = sets()
+    n, n_rows = TB.CTL_TABLE + 1, s.n_rows
+    rays = dev(torch, R.bipedal_rays())
+    arenas = s.arenas()
+    for name, nodes in (("act", 7), ("act_recurrent", 7), ("act_normed", 8)):
+        rec = name == "act_recurrent"
+        b = act_buffers(torch, n_rows, rec)
+        bufs = (b["obs"].inner, b["frac"].inner, b["targets"].inner, b["valid"].inner)
+        if rec:
+            pol = policy.RecurrentPolicy.random(n_rows, ACT_BODIES, ACT_HIDDEN, ACT_CONTEXT, seed=5).to("cuda")
+            desc = pol.descriptor(*bufs, b["memory"].inner)
+        else:
+            pol = policy.MLPPolicy.random(n_rows, ACT_BODIES, ACT_HIDDEN, seed=5).to("cuda")
+            desc = pol.descriptor(*bufs)
+        norm = policy.ObsNormalizer(-(-n_rows // NORM_GROUP), NORM_GROUP, ACT_BODIES, 10, device="cuda")
+        held = [v.raw.clone() for v in b.values()]
+
+        def queue():
+            if name == "act_normed":
+                rc, text = normed_call(s.worlds[:n], norm.descriptor(), desc, rays, 1)
+            else:
+                rc, text = call(s.worlds[:n], name, (C.byref(desc), ptr(rays)))
+            assert rc == 0, text
+        assert captured_nodes(torch, queue) == nodes, name
+        torch.cuda.synchronize()
+        assert all(torch.equal(v.raw, h) for v, h in zip(b.values(), held)) and int(norm.count.sum()) == 0
+    same_arenas(s.arenas(), arenas, "captured act calls")
+
+
 # ------------------------------------------------------------------------------------------------------------------- describe
 @pytest.mark.parametrize("n", TB.CTL_COUNTS)
 def test_describe(gpu, sets, n):
@@ -594,7 +787,7 @@ def test_refill(gpu, sets, n):
 
 
 # ------------------------------------------------------------------------------------------------------------------ refusals
-REFUSED = ("observe", "control", "sense", "act", "act_recurrent", "describe", "reset_where", "refill")
+REFUSED = ("observe", "control", "sense", "act", "act_recurrent", "act_normed", "describe", "reset_where", "refill")
 N_REFUSED = TB.CTL_TABLE + 2
 
 
@@ -623,6 +816,13 @@ def refusal_call(torch, s, name):
             pol = policy.MLPPolicy.random(n_rows, ACT_BODIES, ACT_HIDDEN, seed=5).to("cuda")
             desc = pol.descriptor(b["obs"].inner, b["frac"].inner, b["targets"].inner, b["valid"].inner)
         return (lambda ws, _=None: call(ws, name, (C.byref(desc), ptr(rays)))), [v.raw for v in b.values()] + list(pol.weights)
+    if name == "act_normed":
+        b = act_buffers(torch, n_rows, False)
+        pol = policy.MLPPolicy.random(n_rows, ACT_BODIES, ACT_HIDDEN, seed=5).to("cuda")
+        norm = policy.ObsNormalizer(-(-n_rows // NORM_GROUP), NORM_GROUP, ACT_BODIES, 10, min_count=2, device="cuda")
+        desc = pol.descriptor(b["obs"].inner, b["frac"].inner, b["targets"].inner, b["valid"].inner)
+        return ((lambda ws, _=None: normed_call(ws, norm.descriptor(), desc, rays, 1)),
+                [v.raw for v in b.values()] + list(pol.weights) + [norm.count, norm.s1, norm.s2hi, norm.s2lo, norm.mu, norm.inv])
     if name == "describe":
         out = torch.full((n_rows, 8), -5.0, dtype=torch.float32, device="cuda")
         return (lambda ws, _=None: call(ws, name, (15, 4, ptr(out), n_rows))), [out]
@@ -689,6 +889,188 @@ def test_refusals_across_the_split(gpu, sets, name):
             assert not all(torch.equal(b, h) for b, h in zip(buffers, held))
     finally:
         raw.close()
+
+
+# ------------------------------------------------------------------------------------------------------------ refusal chains
+# The GPU half of tests/test_world_calls_host.py: which of several faulty WORLDS of one list a call names first.  The list is five
+# 2-lane one-block worlds' worth of faults -- a good world, one that was never reset, a NULL, one without terrain; for refill also a
+# good world whose feed holds creatures of other lanes and a world on the static tile shape 4 -- in two orders, so that a check
+# that runs world by world and one that runs in a loop of its own tell apart.  A link: call, record code and text, take the world
+# the text names out of the list (the first one with that fault); the chain ends, without a call, when the list holds nothing the
+# call refuses.  Every link is refused before a launch: after each one every arena and every buffer holds the bytes it held.
+LEFT_OUT = ("a world of more than 64 lanes per creature: rem2d_world_create takes 2, 4, 8, 16, 32 or 64 lanes, so the library cannot make one",)
+CHAIN_CALLS = ("observe", "control", "sense", "act", "act_recurrent", "act_normed", "describe", "reset_where", "refill")
+CHAIN_ORDERS = {"a": ("good", "raw", "null", "bare", "lanes", "static"), "b": ("good", "static", "lanes", "bare", "null", "raw")}
+CHAIN_FAULTS = (("is NULL", "null"), ("rem2d_world_set_terrain must be called first", "bare"),
+                ("rem2d_world_reset (or adopt) must be called first", "raw"), ("lanes, its world creatures of", "lanes"),
+                ("is on the static tile shape", "static"))
+NEEDS_TERRAIN = ("sense", "act", "act_recurrent", "act_normed")
+
+
+class ChainWorlds:
+    """good / raw (terrain, never reset) / bare (reset, no terrain) / lanes (good; its feed is of 4 lanes) / static (tile shape 4)"""
+
+    def __init__(self, torch):
+        from gym_rem2d_amd.world import BatchedWorld
+        self.torch, self.w = torch, {}
+        m = self.morph = TB.morphology(32)
+        assert (m.lanes, TB.blocks(32)) == (2, 1)
+        try:
+            for kind in ("good", "raw", "bare", "lanes", "static"):
+                w = self.w[kind] = BatchedWorld(m.n_envs, m.lanes, TB.CONT)
+                if kind != "bare":
+                    w.set_terrain(TB.terrain(32))
+                if kind != "raw":
+                    w.reset(m, tile_shape=4 if kind == "static" else None)
+            self.w["null"] = None
+            self.n_rows = 5 * m.n_envs
+            self.index = [torch.arange(k * m.n_envs, (k + 1) * m.n_envs, dtype=torch.int32, device="cuda") for k in range(5)]
+            self.reward, self.done = torch.zeros(self.n_rows, device="cuda"), torch.zeros(self.n_rows, dtype=torch.bool, device="cuda")
+            for w, idx in zip(self.real(), self.index):
+                w.set_outputs(self.reward, self.done, idx)
+            torch.cuda.synchronize()
+        except BaseException:
+            self.close()
+            raise
+
+    def real(self):
+        return [w for w in self.w.values() if w is not None]
+
+    def arenas(self):
+        return [w.arena.clone() for w in self.real()]
+
+    def close(self):
+        for w in self.real():
+            w.close()
+
+
+def chain_call(torch, cw, name):
+    """-> (run(kinds) -> (code, text), [device tensors the call could write])"""
+    from gym_rem2d_amd import _lib, policy
+    n_rows = cw.n_rows
+    rays = dev(torch, R.bipedal_rays())
+    some = {f: dev(torch, cw.morph.arrays[f]) for f in _lib.MORPH_FIELDS}
+
+    def ws(kinds):
+        return [cw.w[k] for k in kinds]
+
+    def morphs_of(kinds):
+        return (_lib.Morph * len(kinds))(*[morph_struct(some) for _ in kinds])
+    if name == "observe":
+        out = torch.full((n_rows, CM.width(4)), 7.5, dtype=torch.float32, device="cuda")
+        return (lambda kinds: call(ws(kinds), name, (4, ptr(out), n_rows))), [out]
+    if name == "control":
+        values = torch.full((n_rows, 4), 0.5, dtype=torch.float64, device="cuda")
+        return (lambda kinds: call(ws(kinds), name, (TB.CTRL_TARGET, ptr(values), 4, n_rows, None))), [values]
+    if name == "sense":
+        frac = torch.full((n_rows, 10), 7.5, dtype=torch.float32, device="cuda")
+        return (lambda kinds: call(ws(kinds), name, (ptr(rays), 10, ptr(frac), None, n_rows))), [frac]
+    if name == "describe":
+        out = torch.full((n_rows, 8), -5.0, dtype=torch.float32, device="cuda")
+        return (lambda kinds: call(ws(kinds), name, (15, 4, ptr(out), n_rows))), [out]
+    if name in ("act", "act_recurrent", "act_normed"):
+        rec = name == "act_recurrent"
+        b = act_buffers(torch, n_rows, rec)
+        bufs = (b["obs"].inner, b["frac"].inner, b["targets"].inner, b["valid"].inner)
+        held = [v.raw for v in b.values()]
+        if rec:
+            pol = policy.RecurrentPolicy.random(n_rows, ACT_BODIES, ACT_HIDDEN, ACT_CONTEXT, seed=5).to("cuda")
+            desc = pol.descriptor(*bufs, b["memory"].inner)
+        else:
+            pol = policy.MLPPolicy.random(n_rows, ACT_BODIES, ACT_HIDDEN, seed=5).to("cuda")
+            desc = pol.descriptor(*bufs)
+        if name == "act_normed":
+            norm = policy.ObsNormalizer(1, n_rows, ACT_BODIES, 10, device="cuda")
+            return ((lambda kinds: normed_call(ws(kinds), norm.descriptor(), desc, rays, 1)),
+                    held + list(pol.weights) + [norm.count, norm.s1, norm.s2hi, norm.s2lo, norm.mu, norm.inv])
+        return (lambda kinds: call(ws(kinds), name, (C.byref(desc), ptr(rays)))), held + list(pol.weights)
+    if name == "reset_where":
+        mask = torch.ones(n_rows, dtype=torch.uint8, device="cuda")
+        return (lambda kinds: call(ws(kinds), name, (ptr(mask), 0, 0, None, n_rows), (morphs_of(kinds),))), [mask] + list(some.values())
+    cursor = torch.zeros(1, dtype=torch.int32, device="cuda")
+    occupant = torch.arange(n_rows, dtype=torch.int32, device="cuda")
+    ids = torch.arange(cw.morph.n_envs, dtype=torch.int32, device="cuda")
+
+    def run(kinds):
+        feeds = (_lib.Feed * len(kinds))()
+        for f, k in zip(feeds, kinds):
+            f.M, f.id, f.count, f.cursor, f.lanes = morph_struct(some), ptr(ids), cw.morph.n_envs, ptr(cursor), 4 if k == "lanes" else 2
+        return call(ws(kinds), name, (feeds, ptr(occupant), _lib.WHEN["steps"], 1, None, n_rows, n_rows), (morphs_of(kinds),))
+    return run, [cursor, occupant, ids] + list(some.values())
+
+
+def chain_kinds(name, order):
+    return [k for k in CHAIN_ORDERS[order] if name == "refill" or k not in ("lanes", "static")]
+
+
+def refused(name, kinds):
+    """what the call refuses of a list, by the headers: NULL and never-reset worlds always, a world without terrain where rays are
+    cast, the feed of other lanes and the static tile shape in refill"""
+    return [k for k in kinds if k in ("null", "raw") or (k == "bare" and name in NEEDS_TERRAIN) or (k in ("lanes", "static") and name == "refill")]
+
+
+def walk_chain(torch, cw, name, order, check=None):
+    """[[code, text], ...] down to a list the call would take; check(): called after every link"""
+    run, _ = chain_call(torch, cw, name) if check is None else check[0]
+    kinds, out = chain_kinds(name, order), []
+    while refused(name, kinds) and len(out) < 8:
+        rc, text = run(kinds)
+        out.append([rc, text])
+        if check is not None:
+            check[1](kinds)
+        gone = [k for needle, k in CHAIN_FAULTS if needle in text and k in kinds]
+        if rc == 0 or len(gone) != 1:
+            break
+        kinds.remove(gone[0])
+    return out
+
+
+def record_chains(torch):
+    """for tests/test_world_calls_host.py --record: {call: {order: chain}}"""
+    cw = ChainWorlds(torch)
+    try:
+        return {name: {order: walk_chain(torch, cw, name, order) for order in CHAIN_ORDERS} for name in CHAIN_CALLS}
+    finally:
+        cw.close()
+
+
+@pytest.fixture(scope="module")
+def chain_worlds(gpu):
+    cw = ChainWorlds(gpu)
+    yield cw
+    cw.close()
+
+
+@pytest.mark.parametrize("name", CHAIN_CALLS)
+def test_refusal_chains(gpu, chain_worlds, name):
+    """both orders of the list, link by link against tests/golden/world_call_refusals.json (recorded before the calls were put on
+    shared helpers): code, text, and no byte of any arena or buffer moved.  The chains are no vacuous ones: each ends with nothing
+    left that the call refuses, and every fault the call knows was named once."""
+    import json
+    import test_world_calls_host as H
+    torch = gpu
+    cw = chain_worlds
+    with open(H.GOLDEN) as f:
+        record = json.load(f)
+    want = record["gpu"][name]
+    assert sorted(record["gpu"]) == sorted(CHAIN_CALLS) and record["gpu_left_out"] == list(LEFT_OUT)
+    run, buffers = chain_call(torch, cw, name)
+    torch.cuda.synchronize()
+    arenas, held = cw.arenas(), [b.clone() for b in buffers]
+
+    def untouched(kinds):
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(cw.arenas(), arenas)), "%s refused (%s): an arena moved" % (name, kinds)
+        assert all(torch.equal(b, h) for b, h in zip(buffers, held)), "%s refused (%s): a buffer was written" % (name, kinds)
+    for order in CHAIN_ORDERS:
+        got = walk_chain(torch, cw, name, order, ((run, buffers), untouched))
+        for i, (a, b) in enumerate(zip(got, want[order])):
+            assert a == b, "%s, order %s, link %d: %r, the record has %r" % (name, order, i, a, b)
+        assert len(got) == len(want[order]) == len(refused(name, chain_kinds(name, order))), (name, order, got)
+        assert all(rc in (-1, -3) and text.startswith(name + ": ") for rc, text in got)
+    # (the calls that look at a world's faults world by world name them in the list's order; the act calls and reset_where run a
+    # loop per fault, so the two orders give them one chain)
+    assert ([t for _, t in want["a"]] != [t for _, t in want["b"]]) == (name in ("observe", "control", "describe", "sense", "refill"))
 
 
 # ---------------------------------------------------------------------------------------------------------- through the facade

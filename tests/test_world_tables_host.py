@@ -30,10 +30,18 @@ def test_the_constants_are_the_headers():
     assert _define("include/rem2d_novelty.h", "REM2D_NOVELTY_MAX_SAMPLES") == TB.MAX_SAMPLES
     assert _define("include/rem2d_control.h", "REM2D_CTRL_TARGET") == TB.CTRL_TARGET
     assert _define("include/rem2d_control.h", "REM2D_CTRL_PARAMS") == TB.CTRL_PARAMS
-    # every chunked loop of the host layer steps by one of the two tables, and the two kernels' second tables are as long
+    # the host layer has ONE chunked loop over worlds, in table_launches, stepping by that helper's table-size parameter; the helper
+    # is called with one of the two tables, CTL_TABLE by five calls and STREAM_TABLE by one; and the two kernels' second tables are
+    # as long
     src = open(os.path.join(ROOT, "gym_rem2d_amd/csrc/rem2d.hip")).read()
-    steps = re.findall(r"for \(int first = 0; first < n_worlds; first \+= (\w+)\)", src)
-    assert sorted(steps) == ["CTL_TABLE"] * 5 + ["STREAM_TABLE"], steps
+    helper = re.search(r"static int table_launches\(int (\w+), rem2d_world \*const \*worlds, int n_worlds, Launch launch\) \{\n(.*?)\n\}\n", src, flags=re.S)
+    assert helper and helper.group(1) == "table"
+    assert re.findall(r"first \+= *(\w+)", src) == ["table"] and len(re.findall(r"\bfirst *\+=|\+= *(?:CTL|STREAM)_TABLE\b", src)) == 1
+    assert re.findall(r"for \(int first = 0; first < n_worlds; first \+= (\w+)\)", helper.group(2)) == ["table"]
+    assert "control_table(Tb, worlds, first, n)" in helper.group(2) and "std::min(table, n_worlds - first)" in helper.group(2)
+    calls = re.findall(r"\btable_launches\((?!int )([^,]*),", src)
+    assert sorted(calls) == ["CTL_TABLE"] * 5 + ["STREAM_TABLE"], calls
+    assert len(re.findall(r"\bcontrol_table\(", src)) == 2          # (its definition, and the helper)
     for path, member in (("rem2d_sense.h", r"SenseTerrain t\[CTL_TABLE\]"), ("rem2d_novelty.h", r"char \*env4\[CTL_TABLE\]"),
                          ("rem2d_episode.h", r"EpWorld w\[CTL_TABLE\]"), ("rem2d_stream.h", r"StWorld w\[STREAM_TABLE\]")):
         assert re.search(member, open(os.path.join(ROOT, "gym_rem2d_amd/csrc", path)).read()), path
