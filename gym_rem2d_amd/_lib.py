@@ -123,6 +123,9 @@ PARETO_MAX_WIDTH = 32       # REM2D_PARETO_MAX_WIDTH
 PARETO_MAX_K = 32           # REM2D_PARETO_MAX_K
 RECURRENT_ABI_VERSION = 1   # include/rem2d_recurrent.h
 RECURRENT_MAX_INPUTS = SENSE_MAX_RAYS   # n_rays + context: what a feed-forward set may have as ray inputs
+MODULAR_ABI_VERSION = 1     # include/rem2d_modular.h
+MODULAR_MAX_ROUNDS = 8      # REM2D_MODULAR_MAX_ROUNDS
+MODULAR_MAX_INPUTS = SENSE_MAX_RAYS   # REM2D_MODULAR_MAX_INPUTS: n_rays + 2 + 2 messages, a feed-forward set's ray inputs
 OBSNORM_ABI_VERSION = 1     # include/rem2d_obsnorm.h
 OBSNORM_MAX_CHUNK = 65536   # REM2D_OBSNORM_MAX_CHUNK
 OBSNORM_CAPACITY_LOG2 = 39  # REM2D_OBSNORM_CAPACITY_LOG2
@@ -194,6 +197,18 @@ class Policy(C.Structure):
 class Recurrent(C.Structure):
     """rem2d_recurrent (include/rem2d_recurrent.h): a rem2d_policy, the context width and the device memory the caller owns."""
     _fields_ = [("p", Policy), ("context", C.c_int32), ("reserved", C.c_int32), ("memory", C.c_void_p), ("reset", C.c_void_p)]
+
+
+class Topology(C.Structure):
+    """rem2d_topology (include/rem2d_modular.h): where the topology table goes, and the stream the call queues on."""
+    _fields_ = [("max_bodies", C.c_int32), ("reserved", C.c_int32), ("out", C.c_void_p), ("out_rows", C.c_int64), ("stream", C.c_void_p)]
+
+
+class Modular(C.Structure):
+    """rem2d_modular (include/rem2d_modular.h): a rem2d_policy, the message width, the rounds, the topology table, the device memory
+    the caller owns, and the stream the calls queue on."""
+    _fields_ = [("p", Policy), ("messages", C.c_int32), ("rounds", C.c_int32), ("topo", C.c_void_p), ("memory", C.c_void_p),
+                ("reset", C.c_void_p), ("stream", C.c_void_p)]
 
 
 class Obsnorm(C.Structure):
@@ -574,6 +589,13 @@ def lib(wide=False):
     L.rem2d_worlds_act_normed.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Obsnorm), C.POINTER(Policy), C.c_void_p, C.c_int32]
     if L.rem2d_obsnorm_abi_version() != OBSNORM_ABI_VERSION:
         raise Rem2dError("%s: obsnorm ABI version mismatch" % os.path.basename(path))
+    # modular device policies (include/rem2d_modular.h): the stream is a member of both descriptors
+    L.rem2d_modular_abi_version.restype = C.c_int
+    L.rem2d_worlds_topology.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Topology)]
+    L.rem2d_modular_forward.argtypes = [C.POINTER(Modular)]
+    L.rem2d_worlds_act_modular.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Modular), C.c_void_p]
+    if L.rem2d_modular_abi_version() != MODULAR_ABI_VERSION:
+        raise Rem2dError("%s: modular ABI version mismatch" % os.path.basename(path))
     # self-test of the collision geometry (include/rem2d_selftest.h)
     L.rem2d_selftest_abi_version.restype = C.c_int
     L.rem2d_selftest_static_box.argtypes = [C.c_void_p, C.c_void_p]

@@ -55,6 +55,7 @@
 #include <rem2d_pareto.h>  // (likewise)
 #include <rem2d_recurrent.h> // (likewise)
 #include <rem2d_obsnorm.h> // (likewise)
+#include <rem2d_modular.h> // (likewise)
 
 #define KC REM2D_CONTACT_SLOTS
 #define KT REM2D_SOLVER_SLOTS   // touching contacts per body that can enter the solver
@@ -114,6 +115,7 @@ enum { CF_VERTEX = 0, CF_FACE = 1 };
 #include "rem2d_obsnorm.h" // (before the two forward kernels, whose NORM instantiations stage their rows through it)
 #include "rem2d_policy.h"
 #include "rem2d_recurrent.h"
+#include "rem2d_modular.h"
 #include "rem2d_episode.h"
 #include "rem2d_stream.h"
 #include "rem2d_evolve.h"
@@ -1524,10 +1526,16 @@ template <typename Launch> static int table_launches(int table, rem2d_world *con
     }
     return REM2D_OK;
 }
-static int observe_launch(rem2d_world *const *worlds, int n_worlds, int max_bodies, float *out_dev, long long out_rows, hipStream_t st) {
+// The launches of a kernel that writes rows of max_bodies columns in population order: observe, and the topology table of
+// include/rem2d_modular.h, whose kernels take the same arguments.
+template <typename Kernel, typename T>
+static int rows_launch(Kernel kernel, rem2d_world *const *worlds, int n_worlds, int max_bodies, T *out_dev, long long out_rows, hipStream_t st) {
     return table_launches(CTL_TABLE, worlds, n_worlds, [&](int, int, const CtlTable &Tb, dim3 grid) {
-        hipLaunchKernelGGL(rem2d_observe_kernel, grid, dim3(CTL_THREADS), 0, st, Tb, max_bodies, out_dev, out_rows);
+        hipLaunchKernelGGL(kernel, grid, dim3(CTL_THREADS), 0, st, Tb, max_bodies, out_dev, out_rows);
     });
+}
+static int observe_launch(rem2d_world *const *worlds, int n_worlds, int max_bodies, float *out_dev, long long out_rows, hipStream_t st) {
+    return rows_launch(rem2d_observe_kernel, worlds, n_worlds, max_bodies, out_dev, out_rows, st);
 }
 static int control_launch(rem2d_world *const *worlds, int n_worlds, int mode, const double *values_dev, int max_bodies, long long n_rows,
                           const unsigned char *mask_dev, hipStream_t st) {
@@ -1677,7 +1685,7 @@ extern "C" int rem2d_policy_forward(const rem2d_policy *p, void *stream) {
     OK_TRY(policy_ok("policy", p));
     return policy_launch(p, (hipStream_t)stream);
 }
-// What rem2d_worlds_act, _act_recurrent and _act_normed do once their descriptors are checked: the ray offsets and the worlds
+// What rem2d_worlds_act, _act_recurrent, _act_normed and _act_modular do once their descriptors are checked: the ray offsets and the worlds
 // (everything before the first launch), then observe, sense, `forward()` and control on `st`, launches only.
 template <typename Forward>
 static int act(const std::string &s, rem2d_world *const *worlds, int32_t n_worlds, const rem2d_policy *p, const double *ray_offsets_dev,
@@ -1738,6 +1746,77 @@ extern "C" int rem2d_worlds_act_recurrent(rem2d_world *const *worlds, int32_t n_
     OK_TRY(recurrent_ok("act_recurrent", q));
     return act("act_recurrent: ", worlds, n_worlds, &q->p, ray_offsets_dev, (hipStream_t)stream,
                [&] { return recurrent_launch(q, (hipStream_t)stream); });
+}
+
+// ---- modular device policies (include/rem2d_modular.h, csrc/rem2d_modular.h) ----
+extern "C" int rem2d_modular_abi_version(void) { return REM2D_MODULAR_ABI_VERSION; }
+static_assert(REM2D_MODULAR_MAX_INPUTS == REM2D_SENSE_MAX_RAYS, "a modular set is an ordinary set of R + 2 + 2 K ray inputs");
+extern "C" int rem2d_worlds_topology(rem2d_world *const *worlds, int32_t n_worlds, const rem2d_topology *t) {
+    const std::string p = "topology: ";
+    OK_TRY(worlds_given(p, worlds, n_worlds));
+    if (!t) return fail(REM2D_E_INVALID, p + "NULL descriptor");
+    if (t->reserved != 0) return fail(REM2D_E_INVALID, p + "reserved must be 0, not " + std::to_string(t->reserved));
+    OK_TRY(table_call_ok(p, worlds, n_worlds, t->out, t->max_bodies, t->out_rows));
+    return rows_launch(rem2d_topology_kernel, worlds, n_worlds, (int)t->max_bodies, (int *)t->out, (long long)t->out_rows, (hipStream_t)t->stream);
+}
+// Checks a modular descriptor; `what` prefixes the message.  Nothing it points to is read.  policy_ok checks everything of q->p but
+// d, whose rule here is the per-body one.
+static int modular_ok(const char *what, const rem2d_modular *q) {
+    const std::string s = std::string(what) + ": ";
+    if (!q) return fail(REM2D_E_INVALID, s + "NULL modular policy");
+    rem2d_policy c = q->p;
+    c.d = REM2D_OBS_HEAD + REM2D_OBS_BODY * c.max_bodies + c.n_rays; // (what policy_ok wants of a feed-forward set: checked below instead)
+    const int rc = policy_ok(what, &c);
+    if (rc != REM2D_OK) return rc;
+    if (q->messages < 1 || q->messages > q->p.hidden)
+        return fail(REM2D_E_INVALID, s + "messages must be 1..hidden (" + std::to_string(q->p.hidden) + "), not " + std::to_string(q->messages));
+    if (q->p.n_rays + 2 + 2 * (int64_t)q->messages > REM2D_MODULAR_MAX_INPUTS)
+        return fail(REM2D_E_INVALID, s + "n_rays + 2 + 2 messages must be at most " + std::to_string(REM2D_MODULAR_MAX_INPUTS) + ", not " +
+                                         std::to_string(q->p.n_rays) + " + 2 + 2 * " + std::to_string(q->messages));
+    if (q->rounds < 1 || q->rounds > REM2D_MODULAR_MAX_ROUNDS)
+        return fail(REM2D_E_INVALID, s + "rounds must be 1.." + std::to_string(REM2D_MODULAR_MAX_ROUNDS) + ", not " + std::to_string(q->rounds));
+    const int dm = REM2D_OBS_HEAD + REM2D_OBS_BODY + q->p.n_rays + 2 + 2 * q->messages;
+    if (q->p.d != dm)
+        return fail(REM2D_E_INVALID, s + "d must be 8 + 6 + n_rays + 2 + 2 messages = " + std::to_string(dm) + ", not " + std::to_string(q->p.d));
+    if (!q->topo) return fail(REM2D_E_INVALID, s + "NULL device pointer (topo)");
+    if (!q->memory) return fail(REM2D_E_INVALID, s + "NULL device pointer (memory)");
+    return REM2D_OK;
+}
+// lanes per body for n units of which a lane owns v: a power of two, MOD_MIN_LPB .. 64
+static int modular_lpb(int n, int v) { return (int)std::min((unsigned)WAVE, std::max((unsigned)MOD_MIN_LPB, pow2_at_least((unsigned)((n + v - 1) / v)))); }
+static int modular_launch(const rem2d_modular *q) {
+    const rem2d_policy *p = &q->p;
+    if (p->n_rows == 0) return REM2D_OK;
+    if (p->n_rows > 0x7fffffffLL) return fail(REM2D_E_INVALID, "modular: too many rows for one launch");
+    ModularArgs Q;
+    memset(&Q, 0, sizeof(Q));
+    PolicyArgs &P = Q.P;
+    P.w1 = p->w1; P.b1 = p->b1; P.w2 = p->w2; P.b2 = p->b2;
+    P.index = p->index; P.rowMask = p->row_mask;
+    P.obs = p->obs; P.frac = p->frac; P.targets = p->targets; P.valid = p->valid;
+    P.nRows = p->n_rows;
+    P.D = p->d; P.MB = p->max_bodies; P.R = p->n_rays; P.H = p->hidden; P.G = p->n_sets; P.act = p->activation;
+    P.scale = p->scale;
+    Q.topo = q->topo; Q.memory = q->memory; Q.reset = q->reset; Q.K = q->messages; Q.rounds = q->rounds;
+    const bool v4 = p->hidden % 4 == 0; // (the weights are read from LDS, whose base is aligned)
+    const int V = v4 ? 4 : 1;
+    P.lpr = modular_lpb(p->hidden, V);
+    Q.lpbK = modular_lpb(std::min(p->hidden, (q->messages + V - 1) / V * V), V);
+    const size_t lds = (size_t)modular_lds(P.D, P.H, P.MB, P.R, Q.K, P.lpr, Q.lpbK).words * sizeof(float);
+    if (lds > 65536) return fail(REM2D_E_INVALID, "modular: the row does not fit the LDS of a workgroup"); // (no shape within the limits gets here)
+    if (v4) hipLaunchKernelGGL(rem2d_modular_forward_kernel<4>, dim3((unsigned)p->n_rows), dim3(WAVE), lds, (hipStream_t)q->stream, Q);
+    else hipLaunchKernelGGL(rem2d_modular_forward_kernel<1>, dim3((unsigned)p->n_rows), dim3(WAVE), lds, (hipStream_t)q->stream, Q);
+    HIP_TRY(hipGetLastError());
+    return REM2D_OK;
+}
+extern "C" int rem2d_modular_forward(const rem2d_modular *q) {
+    OK_TRY(modular_ok("modular", q));
+    return modular_launch(q);
+}
+extern "C" int rem2d_worlds_act_modular(rem2d_world *const *worlds, int32_t n_worlds, const rem2d_modular *q, const double *ray_offsets_dev) {
+    OK_TRY(worlds_given("act_modular: ", worlds, n_worlds));
+    OK_TRY(modular_ok("act_modular", q));
+    return act("act_modular: ", worlds, n_worlds, &q->p, ray_offsets_dev, (hipStream_t)q->stream, [&] { return modular_launch(q); });
 }
 
 // ---- episode boundaries (include/rem2d_episode.h, csrc/rem2d_episode.h) ----

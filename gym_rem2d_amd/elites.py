@@ -71,7 +71,7 @@ class EliteGrid:
         if n_blocks * C_ > 2 ** 31 - 1:
             raise ValueError("EliteGrid: %d blocks of %d cells are more than 2^31 - 1 slots" % (n_blocks, C_))
         self.n_blocks, self.width, self.n_cells, self.dims = n_blocks, width, C_, [tuple(d) for d in dims]
-        self.d, self.hidden, self.max_bodies = like.d, like.hidden, like.max_bodies
+        self.d, self.hidden, self.max_bodies = like.d, like.hidden, like.weight_bodies
         self.like = like
         dev = "cpu" if device is None else device
         slots = n_blocks * C_
@@ -83,8 +83,8 @@ class EliteGrid:
         self.winner = torch.full((n_blocks, C_), -1, dtype=torch.int32, device=dev)
         self.w1 = torch.zeros((slots, like.d, like.hidden), dtype=torch.float32, device=dev)
         self.b1 = torch.zeros((slots, like.hidden), dtype=torch.float32, device=dev)
-        self.w2 = torch.zeros((slots, like.hidden, like.max_bodies), dtype=torch.float32, device=dev)
-        self.b2 = torch.zeros((slots, like.max_bodies), dtype=torch.float32, device=dev)
+        self.w2 = torch.zeros((slots, like.hidden, like.weight_bodies), dtype=torch.float32, device=dev)
+        self.b2 = torch.zeros((slots, like.weight_bodies), dtype=torch.float32, device=dev)
         self.filled = torch.zeros(n_blocks, dtype=torch.int32, device=dev)     # n_filled as the last sample / emit wrote it
         self.scratch = torch.zeros((slots * 12 + 7) // 8, dtype=torch.int64, device=dev)
         self.cell = None
@@ -165,9 +165,9 @@ class EliteGrid:
     def _fits(self, what, policy, n_sets=None):
         if not isinstance(policy, MLPPolicy) or policy.index is not None:
             raise ValueError("%s: the policy must be an MLPPolicy without an index" % what)
-        if (policy.d, policy.hidden, policy.max_bodies) != (self.d, self.hidden, self.max_bodies):
+        if (policy.d, policy.hidden, policy.weight_bodies) != (self.d, self.hidden, self.max_bodies):
             raise ValueError("%s: the policy's sets are [%d, %d] -> [%d], the grid's [%d, %d] -> [%d]"
-                             % (what, policy.d, policy.hidden, policy.max_bodies, self.d, self.hidden, self.max_bodies))
+                             % (what, policy.d, policy.hidden, policy.weight_bodies, self.d, self.hidden, self.max_bodies))
         if policy.device != self.device:
             raise ValueError("%s: the policy must be on %s, not %s" % (what, self.device, policy.device))
         if n_sets is not None and policy.n_sets != n_sets:

@@ -645,12 +645,19 @@ class BatchedModular2D:
         creature that reset_where() has just restarted.  Streaming under a recurrent policy is not built: a slot's next creature
         would inherit its predecessor's context, so with a streamed evaluation in place this raises ValueError.
 
+        A ``policy.ModularPolicy`` -- one controller per body, messages along the tree; one weight set may drive creatures of
+        different trees -- gets its messages here, ``policy_memory`` float32 ``[N, max_bodies, messages]``, zeroed, and the
+        topology table of the creatures in place (``policy_topology``, as ``topology(policy.max_bodies)`` makes it); a new upload
+        drops both with the policy, and attaching the policy again makes them again.  act() then is rem2d_worlds_act_modular, under
+        the reset rules of a recurrent policy.  With a ``normalizer`` or a streamed evaluation this raises ValueError: neither is
+        built for modular policies.
+
         ``normalizer``: a ``policy.ObsNormalizer`` of the policy's ``max_bodies`` and rays on the env's device whose blocks cover the
         creatures (``n_blocks * group_size >= n_envs``; creature r belongs to block ``r // group_size``): act() then stages every
         row through the normaliser's tables as they stand (rem2d_worlds_act_normed) and, with ``accumulate``, first adds the rows
         it has just observed to the normaliser's sums -- one launch more; the tables move at the normaliser's next ``freeze()``,
         never by themselves.  Without a normaliser nothing changes."""
-        from .policy import ObsNormalizer, RecurrentPolicy
+        from .policy import ModularPolicy, ObsNormalizer, RecurrentPolicy
         self._act_args = None
         self._context_reset = False
         if policy is None:
@@ -664,6 +671,12 @@ class BatchedModular2D:
         if recurrent and self._stream_rec is not None:
             raise ValueError("set_policy: a RecurrentPolicy cannot be attached to a streamed evaluation (reset_stream): refill() "
                              "would hand a slot's context to the next creature -- streaming under recurrent policies is not built")
+        modular = isinstance(policy, ModularPolicy)
+        if modular and normalizer is not None:
+            raise ValueError("set_policy: a ModularPolicy takes no normalizer: observation normalisation of per-body rows is not built")
+        if modular and self._stream_rec is not None:
+            raise ValueError("set_policy: a ModularPolicy cannot be attached to a streamed evaluation (reset_stream): refill() would "
+                             "change a slot's tree under the topology table -- streaming under modular policies is not built")
         have = policy.n_sets if policy.index is None else int(policy.index.shape[0])
         if have != self.n_envs:
             raise ValueError("set_policy: the policy has %d %s for %d creatures"
@@ -682,16 +695,52 @@ class BatchedModular2D:
             frac=torch.ones((N, R), dtype=torch.float32, device=dev) if R else None,
             targets=torch.zeros((N, M), dtype=torch.float64, device=dev),
             valid=torch.zeros((N, M), dtype=torch.uint8, device=dev),
-            memory=policy.new_memory(N) if recurrent else None)
+            memory=policy.new_memory(N) if recurrent or modular else None,
+            topo=self.topology(M) if modular else None)
 
     @property
     def policy(self):
         return None if self._policy is None else self._policy["policy"]
 
+    def topology(self, max_bodies=None, out=None):
+        """The creatures' trees in body order: int32 ``[N, max_bodies, 2]`` on the device, rows in population order, body b the b-th
+        live lane exactly as observe() counts them.  Word 0 is the BODY index of body b's parent -- -1 for the root, for a body whose
+        parent has no column below ``max_bodies`` and for the slots beyond the creature's count --, word 1 the body's shape word
+        (non-zero: the slot is live; ``compiler`` SHAPE_BOX / SHAPE_CIRCLE).  One kernel of the library for the whole population
+        (rem2d_worlds_topology), queued on the current stream; nothing synchronises.  ``out``: a contiguous int32 tensor of that
+        shape to write into; without it a new one (-1 / 0 in the rows of creatures that compact() has retired).  The table changes
+        only when the creatures do: a reset_where() restarts the same trees."""
+        M = self._obs_bodies if max_bodies is None else int(max_bodies)
+        if not 1 <= M <= control.MAX_BODIES:
+            raise ValueError("topology: max_bodies must be 1..%d, not %r" % (control.MAX_BODIES, max_bodies))
+        if not self.worlds:
+            raise ValueError("topology: no population in place (reset first)")
+        dev = self.worlds[0][0].device
+        if out is None:
+            out = torch.zeros((self.n_envs, M, 2), dtype=torch.int32, device=dev)
+            out[:, :, 0] = -1
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (self.n_envs, M, 2)
+              or not out.is_contiguous() or out.device != dev):
+            raise ValueError("topology: out must be a contiguous torch.int32 [%d, %d, 2] tensor on %s" % (self.n_envs, M, dev))
+        worlds = self._control_worlds()
+        if worlds:
+            w0 = worlds[0]
+            t = _lib.Topology()
+            t.max_bodies, t.reserved, t.out, t.out_rows, t.stream = M, 0, out.data_ptr(), self.n_envs, w0._stream()
+            _lib.check(w0.L.rem2d_worlds_topology(_lib.world_array(worlds), len(worlds), C.byref(t)), w0.wide)
+        return out
+
+    @property
+    def policy_topology(self):
+        """The topology table of the attached ``policy.ModularPolicy``: int32 ``[N, max_bodies, 2]``, made by set_policy(); None
+        without one."""
+        return None if self._policy is None else self._policy.get("topo")
+
     @property
     def policy_memory(self):
         """The context words of the attached ``policy.RecurrentPolicy``: float32 ``[N, context]`` on the device, population order,
-        read and rewritten in place by every act() (clone what must last); None without one."""
+        read and rewritten in place by every act() (clone what must last); None without one.  Under a ``policy.ModularPolicy``: the
+        bodies' messages, float32 ``[N, max_bodies, messages]``."""
         return None if self._policy is None else self._policy["memory"]
 
     def act(self):
@@ -721,7 +770,9 @@ class BatchedModular2D:
                 for wi, (w, idx) in enumerate(self.worlds):
                     if wi not in self._inactive and getattr(w, "h", None):
                         mask[idx] = 1
-            if P["memory"] is None:
+            if P.get("topo") is not None:
+                desc = P["policy"].descriptor(P["obs"], P["frac"], P["targets"], P["valid"], P.get("topo"), P["memory"], None, mask)
+            elif P["memory"] is None:
                 desc = P["policy"].descriptor(P["obs"], P["frac"], P["targets"], P["valid"], mask)
             else:
                 desc = P["policy"].descriptor(P["obs"], P["frac"], P["targets"], P["valid"], P["memory"], None, mask)
@@ -730,7 +781,15 @@ class BatchedModular2D:
         if worlds:
             w0 = worlds[0]
             rays = None if P["rays"] is None else P["rays"].data_ptr()
-            if P["normalizer"] is not None:
+            if P.get("topo") is not None:   # (the stream and the reset mask are this one call's, as below)
+                desc.stream = w0._stream()
+                desc.reset = self._episodes.ended.data_ptr() if self._context_reset else None
+                self._context_reset = False
+                try:
+                    _lib.check(w0.L.rem2d_worlds_act_modular(arr, len(worlds), C.byref(desc), rays), w0.wide)
+                finally:
+                    desc.reset = None
+            elif P["normalizer"] is not None:
                 self._act_normed(P, worlds, arr, desc, rays)
             elif P["memory"] is None:
                 _lib.check(w0.L.rem2d_worlds_act(arr, len(worlds), C.byref(desc), rays, w0._stream()), w0.wide)
@@ -971,6 +1030,9 @@ class BatchedModular2D:
         rec = self._stream_rec
         if rec is None:
             raise ValueError("refill: no streamed evaluation in place (reset_stream first)")
+        if self._policy is not None and self._policy.get("topo") is not None:
+            raise ValueError("refill: a ModularPolicy is attached: a slot's next creature would have another tree than the topology "
+                             "table holds -- streaming under modular policies is not built")
         if self._policy is not None and self._policy["memory"] is not None:
             raise ValueError("refill: a RecurrentPolicy is attached: a slot's next creature would inherit its predecessor's context "
                              "-- streaming under recurrent policies is not built")

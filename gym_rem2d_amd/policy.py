@@ -11,6 +11,9 @@ every build of the library: what a policy computes is as reproducible as a step.
 
 ``RecurrentPolicy`` is the same controller with memory (include/rem2d_recurrent.h): K of its hidden activations are
 input words of the next step, carried per creature in device memory that its own kernel reads and rewrites in place.
+
+``ModularPolicy`` is one controller per BODY (include/rem2d_modular.h): the same small network runs for every module
+of a creature and exchanges K message words with the module's parent and children, so that one weight set drives any tree.
 """
 import math
 
@@ -116,6 +119,7 @@ class MLPPolicy:
         self.scale = DEFAULT_SCALE if scale is None else float(np.float32(scale))
         self.index, self.rays = index, rays
         self.n_sets, self.d, self.hidden, self.max_bodies, self.n_rays = G, D, H, MB, R
+        self.weight_bodies = MB  # w2's last axis: what the search operators call max_bodies (a ModularPolicy's is 1, whatever its rows)
         self.parents = None     # int32 [G] on a policy that evolve() made: the set each of its sets came from
         self.util = None        # int32 [M S] on a mean that es_update() made: the utilities of the children it was moved by
 
@@ -157,7 +161,7 @@ class MLPPolicy:
 
     def _shapes(self, n):
         """the shapes of w1, b1, w2, b2 of ``n`` sets of this policy's per-set shapes"""
-        D, H, MB = self.d, self.hidden, self.max_bodies
+        D, H, MB = self.d, self.hidden, self.weight_bodies
         return (n, D, H), (n, H), (n, H, MB), (n, MB)
 
     def _sets(self, n, zeroed=False, device=None):
@@ -211,7 +215,7 @@ class MLPPolicy:
 
     def weight_bytes(self):
         """Bytes of one weight set."""
-        return 4 * (self.d * self.hidden + self.hidden + self.hidden * self.max_bodies + self.max_bodies)
+        return 4 * (self.d * self.hidden + self.hidden + self.hidden * self.weight_bodies + self.weight_bodies)
 
     # ---- the library's descriptor ----
     def descriptor(self, obs, frac, targets, valid, row_mask=None):
@@ -298,7 +302,7 @@ class MLPPolicy:
         elif child.parents is None or child.parents is self.parents:
             child.parents = torch.empty(G, dtype=torch.int32, device=dev)
         e = _lib.Evolve()
-        e.d, e.hidden, e.max_bodies, e.n_sets, e.group_size = self.d, self.hidden, self.max_bodies, G, S
+        e.d, e.hidden, e.max_bodies, e.n_sets, e.group_size = self.d, self.hidden, self.weight_bodies, G, S
         e.tournsize, e.elite, e.generation = int(tournsize), int(elite), int(generation)
         e.rate_threshold, e.seed, e.sigma, e.reserved = _tier.rate_threshold(rate), int(seed), float(sigma), 0
         e.fitness = fitness.data_ptr()
@@ -322,7 +326,7 @@ class MLPPolicy:
         if int(pair_chunk) < 0:
             raise ValueError("%s: pair_chunk must be at least 0, not %r" % (what, pair_chunk))
         e = _lib.Es()
-        e.d, e.hidden, e.max_bodies, e.n_means, e.group_size = self.d, self.hidden, self.max_bodies, self.n_sets, int(group_size)
+        e.d, e.hidden, e.max_bodies, e.n_means, e.group_size = self.d, self.hidden, self.weight_bodies, self.n_sets, int(group_size)
         e.pair_chunk, e.generation, e.reserved, e.seed = int(pair_chunk), int(generation), 0, int(seed)
         return e
 
@@ -472,6 +476,94 @@ class RecurrentPolicy(MLPPolicy):
         return out
 
 
+class ModularPolicy(MLPPolicy):
+    """G shared modular controllers (include/rem2d_modular.h): ONE small network that runs once per body of a creature
+    instead of once per creature.  It reads the 8 head words of the observation row, the 6 words of its own body, the R ray
+    fractions, the body's shape word, its number of children, the sum of its children's ``messages`` = K message words and its
+    parent's K message words, and writes that body's joint target and its own next message (its first K hidden activations);
+    ``rounds`` = P such exchanges happen per control step.  A weight set is tied to no body column: one set drives creatures of
+    any tree.
+
+    The weights have the shapes of an ``MLPPolicy`` of ``max_bodies = 1`` with ``D = 8 + 6 + R + 2 + 2 K`` input rows: w1 ``[G, D, H]``,
+    b1 ``[G, H]``, w2 ``[G, H, 1]``, b2 ``[G, 1]``; ``1 <= K <= H``, ``R + 2 + 2 K <= 64``, ``1 <= P <= 8``.  ``max_bodies`` is the ROW
+    side's: the body columns of the observation rows, the targets and the topology table (default 16); ``weight_bodies`` is 1.  The
+    messages are not part of the policy: they are a float32 ``[N, max_bodies, K]`` tensor per population (``new_memory``;
+    ``BatchedModular2D.set_policy`` keeps one as ``env.policy_memory``), which ``forward`` reads and rewrites in place.  To everything
+    that only moves weights about -- ``take``, ``to``, ``evolve``, ``es_sample`` / ``es_update``, ``SeparableES``, ``EliteGrid`` /
+    ``CentroidArchive`` -- it is an ordinary weight set of one body and R + 2 + 2 K ray inputs, and what those return stays a
+    ``ModularPolicy`` of the same K, P and ``max_bodies``.  GRU cells, observation normalisation, streaming and a CPU twin are not
+    built."""
+
+    def __init__(self, w1, b1, w2, b2, messages, rounds=1, max_bodies=16, activation="softsign", scale=None, index=None, rays=None):
+        if isinstance(messages, bool) or not isinstance(messages, (int, np.integer)) or int(messages) < 1:
+            raise ValueError("messages (K, the hidden units handed to the neighbours) must be an integer of at least 1, not %r" % (messages,))
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= int(rounds) <= _lib.MODULAR_MAX_ROUNDS:
+            raise ValueError("rounds (P, message exchanges per control step) must be an integer in 1..%d, not %r"
+                             % (_lib.MODULAR_MAX_ROUNDS, rounds))
+        if isinstance(max_bodies, bool) or not isinstance(max_bodies, (int, np.integer)) or not 1 <= int(max_bodies) <= control.MAX_BODIES:
+            raise ValueError("max_bodies (the body columns of a row) must be an integer in 1..%d, not %r" % (control.MAX_BODIES, max_bodies))
+        self.messages, self.rounds = int(messages), int(rounds)
+        super().__init__(w1, b1, w2, b2, activation, scale, index, rays)
+        if self.weight_bodies != 1:
+            raise ValueError("a modular weight set drives one body: w2's last axis must be 1, not %d" % self.weight_bodies)
+        if self.messages > self.hidden:
+            raise ValueError("messages = %d is more than the %d hidden units there are to hand on" % (self.messages, self.hidden))
+        self.max_bodies = int(max_bodies)
+
+    def _ray_inputs(self, D, MB):
+        K = self.messages
+        R = D - control.width(1) - 2 - 2 * K
+        if R < 0 or R + 2 + 2 * K > _lib.MODULAR_MAX_INPUTS:
+            raise ValueError("w1 has %d input rows: with messages = %d that must be %d + R + 2 + %d, R in 0..%d"
+                             % (D, K, control.width(1), 2 * K, _lib.MODULAR_MAX_INPUTS - 2 - 2 * K))
+        return R
+
+    @classmethod
+    def random(cls, n_sets, hidden, messages, rounds=1, max_bodies=16, n_rays=10, seed=0, std=(0.3, 0.3, 0.5, 0.3), **kw):
+        """As ``MLPPolicy.random``, with ``2 + 2 * messages`` more input rows in w1 and one body on the weight side: the same draw
+        as ``MLPPolicy.random(n_sets, 1, hidden, n_rays + 2 + 2 * messages)``."""
+        return cls._random(n_sets, 1, hidden, n_rays, seed, std, kw, 2 + 2 * int(messages), (messages, rounds, max_bodies))
+
+    def _like(self, w1, b1, w2, b2, index):
+        return ModularPolicy(w1, b1, w2, b2, self.messages, self.rounds, self.max_bodies, self.activation, self.scale, index, self.rays)
+
+    def new_memory(self, n_rows):
+        """Zeroed messages for ``n_rows`` population rows: float32 ``[n_rows, max_bodies, messages]`` on the policy's device."""
+        return torch.zeros((int(n_rows), self.max_bodies, self.messages), dtype=torch.float32, device=self.device)
+
+    # ---- the library's descriptor ----
+    def descriptor(self, obs, frac, targets, valid, topo, memory, reset=None, row_mask=None):
+        """rem2d_modular over these buffers (checked as ``MLPPolicy.descriptor`` checks its own; ``topo`` int32 ``[N, max_bodies, 2]``,
+        ``memory`` float32 ``[N, max_bodies, K]``, ``reset`` uint8 or bool ``[N]`` or None).  The stream is not set."""
+        p = super().descriptor(obs, frac, targets, valid, row_mask)
+        dev, N = self.device, int(obs.shape[0])
+        if not _tier.is_tensor(topo, torch.int32, (N, self.max_bodies, 2), dev):
+            raise ValueError("policy: topo must be a contiguous torch.int32 %r tensor on %s" % ((N, self.max_bodies, 2), dev))
+        if not _tier.is_tensor(memory, torch.float32, (N, self.max_bodies, self.messages), dev):
+            raise ValueError("policy: memory must be a contiguous torch.float32 %r tensor on %s" % ((N, self.max_bodies, self.messages), dev))
+        if reset is not None and not _tier.is_tensor(reset, (torch.uint8, torch.bool), (N,), dev):
+            raise ValueError("policy: reset must be a contiguous torch.uint8 or torch.bool %r tensor on %s" % ((N,), dev))
+        q = _lib.Modular()
+        q.p, q.messages, q.rounds = p, self.messages, self.rounds
+        q.topo, q.memory, q.reset = topo.data_ptr(), memory.data_ptr(), (None if reset is None else reset.data_ptr())
+        return q
+
+    def forward(self, obs, frac, topo, memory, reset=None, out=None, row_mask=None, wide=False):
+        """The modular forward pass alone (rem2d_modular_forward) on the current stream: ``obs``, ``frac``, ``out``, ``row_mask`` and
+        ``wide`` as ``MLPPolicy.forward`` takes them; ``topo`` int32 ``[N, max_bodies, 2]`` is the creatures' tree in body order
+        (``BatchedModular2D.topology``: the parent's body index or -1, and the shape word whose being non-zero makes a slot live;
+        any values are safe); ``memory`` float32 ``[N, max_bodies, messages]`` is the bodies' messages, read and then overwritten IN
+        PLACE; ``reset`` uint8 / bool ``[N]``: a row whose entry is set reads +0 for its messages whatever memory holds (a new
+        episode).  A row that is skipped keeps its memory too; the slots of a row that are not live get target 0, valid 0 and zero
+        messages.  Returns ``(targets, valid)``."""
+        if out is None:
+            out = self._targets(int(obs.shape[0]))
+        q = self.descriptor(obs, frac, out[0], out[1], topo, memory, reset, row_mask)
+        if int(obs.shape[0]):       # (no row: nothing to do, and an empty tensor has no address to hand over)
+            _tier.launch(_lib.lib(wide).rem2d_modular_forward, q, self.device, wide, stream_member=True)
+        return out
+
+
 class SeparableES:
     """An adaptive evolution strategy around an ``MLPPolicy`` as the mean (include/rem2d_snes.h): the antithetic sampling of
     ``MLPPolicy.es_sample`` with a step size PER PARAMETER -- a sigma tensor of the mean's shapes, adapted every update from the
@@ -556,7 +648,7 @@ class SeparableES:
             raise ValueError("%s: pair_chunk must be at least 0, not %r" % (what, pair_chunk))
         m = self.mean
         e = _lib.Snes()
-        e.d, e.hidden, e.max_bodies, e.n_means, e.group_size = m.d, m.hidden, m.max_bodies, m.n_sets, self.group_size
+        e.d, e.hidden, e.max_bodies, e.n_means, e.group_size = m.d, m.hidden, m.weight_bodies, m.n_sets, self.group_size
         e.pair_chunk, e.generation, e.flags, e.seed = int(pair_chunk), int(generation), self.flags, int(seed)
         return e
 
